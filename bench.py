@@ -27,7 +27,16 @@ relays rank 0's JSON line and exits with the worst child status.  `--dry-collect
 barriers, root all_gather and max-reduce on CPU tensors with the GPU work stubbed out (the CPU test of the N > 1 plumbing;
 its line carries "dry_run": true and value 0).
 
-The JSON line also carries
+A plain run (`python bench.py --gpus 1 --steps K --warmup W`) does only what the headline needs: it sets up, warms up, times the K
+steps, writes the last step's outputs if `--dump-outputs DIR` is given, and prints the line.  Everything else this file measures or
+checks — the verification of every timed proof, the instrumented replay, the extra figures, the other configurations, the host-blob
+and reconstruction blocks, the CPU baseline and the single-process multi-GPU leg — runs only with `--full`.
+
+`--dump-outputs DIR` writes what the timed path returned for its last blob (rank 0's) into DIR: `root.npy` (the 32-byte commitment)
+and, for a proof, `proof.npy` (the proof's serialized image), one float32 element per byte, so that two builds can be compared output for
+output (the inputs are the same from run to run: splitmix64 seeds and the fixed configuration).
+
+With `--full` the JSON line also carries
   roofline     — the dominant launch (dominant_launch(): longest average launch among the kernel families within a factor two of the
                  largest summed HIP-event time on the kernels' own stream, instrumented replay of
                  the same K steps): achieved = algorithmic bytes / time against the 8 TB/s HBM peak;
@@ -81,6 +90,20 @@ def splitmix64_bytes(seed, n):
 
 def blob_len_for(log_domain, log_blowup=4):
     return (4 << (log_domain - log_blowup)) * 30 // 8
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays):
+    """`--dump-outputs DIR`: every byte string in `arrays` (name -> bytes) as DIR/<name>.npy, one float32 element per byte (exact)."""
+    out = {name: np.frombuffer(bytes(b), dtype=np.uint8).astype(np.float32) for name, b in arrays.items()}
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes would exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def algorithmic_bytes(n, workload, log_blowup=4, log_last=0):
@@ -784,7 +807,16 @@ def parse_args(argv=None):
     ap.add_argument("--spm-blobs-per-gpu", type=int, default=8, help="headline-size blobs per device in the single-process leg (units of 1 + 4 + 3 per device, two in flight)")
     ap.add_argument("--spm-timeout", type=float, default=150.0, help="seconds the single-process leg may take (it needs ~20 s on 8 GPUs; a hung RCCL bring-up must not cost the line)")
     ap.add_argument("--no-single-process-multi", action="store_true", help="skip the single_process_multi block of an N > 1 line")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: verification of the timed proofs, instrumented replay, extra figures, other "
+                         "configurations, host-blob and reconstruction blocks, CPU baseline, single-process multi-GPU leg (the --no-* options "
+                         "still skip single blocks)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (root.npy, and proof.npy for a proof: bytes as float32) under DIR")
     args = ap.parse_args(argv)
+    if not args.full:
+        args.no_by_config = args.no_end_to_end = args.no_cpu_baseline = args.no_reconstruct = args.no_single_process_multi = True
+        args.batch_extra = args.sequential_extra = 0
     if args.only_measured_loop:
         args.no_by_config = args.no_end_to_end = args.no_cpu_baseline = args.no_reconstruct = True
         args.batch_extra = args.sequential_extra = 0
@@ -1100,16 +1132,21 @@ def main():
         if args.workload == "prove":
             assert mine == b"".join(r for r, _ in results)
 
-    # correctness gate on what was just timed: EVERY one of the K proofs verifies, the K roots are distinct, and the first FRI
-    # root of blob 0 equals commit()'s
+    # what runs besides the measured loop: nothing in a plain run (--full off) or with --only-measured-loop
+    extras = args.full and not args.only_measured_loop
+    # correctness gate on what was just timed: the K roots are distinct and (--full) EVERY one of the K proofs verifies and the first
+    # FRI root of blob 0 equals commit()'s
     verified = None
     if args.workload == "prove":
         assert len(results) == K and len({r for r, _ in results}) == K, "the K timed blobs must give K distinct roots"
-        for r, p in results:
-            assert p.commitment == r and frieda_amd.verify(p, seed), "a timed proof does not verify"
-        verified = K
+        if args.full:
+            for r, p in results:
+                assert p.commitment == r and frieda_amd.verify(p, seed), "a timed proof does not verify"
+            verified = K
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, {"root": results[-1][0], "proof": results[-1][1].serialize()})
         root, proof = results[0]
-        if not args.only_measured_loop:
+        if extras:
             ctx.commit_device(blob.data_ptr(), blob_len, 4, roots_dev.data_ptr())
             ctx.synchronize()
             assert bytes(roots_dev.cpu().numpy()) == root, "first FRI root != commit() root"
@@ -1122,6 +1159,8 @@ def main():
     else:
         ctx.synchronize()
         root = bytes(roots_all[:32].cpu().numpy())
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, {"root": bytes(roots_all[32 * (K - 1) : 32 * K].cpu().numpy())})
 
     host_phases = ctx.last_prove_phases() if args.workload == "prove" else None
     elems = 4.0 * (1 << n)
@@ -1129,7 +1168,7 @@ def main():
 
     # ---- instrumented replay: per-kernel HIP-event durations on the kernels' own stream ----
     kern = []
-    if not args.only_measured_loop:
+    if extras:
         ctx.set_kernel_timing(True)
         for _ in range(args.steps):
             step()
@@ -1238,7 +1277,7 @@ def main():
 
     # ---- extra figure: twiddles regenerated on every call, as the reference does (src/commit.rs:15, src/proof.rs:47) ----
     uncached = None
-    if not args.no_twiddle_cache and world == 1 and not args.only_measured_loop:
+    if not args.no_twiddle_cache and world == 1 and extras:
         ctx.set_twiddle_cache(False)
         reps = max(3, args.steps // 4)
         step()
@@ -1261,7 +1300,7 @@ def main():
     # NOT in the ideal time and which runs at 4 waves per SIMD where the ceiling kernel runs at 8, so that fraction is a lower bound
     # on the hashing efficiency) and the fused fold + tree of the first FRI layer.
     valu = None
-    if args.only_measured_loop:
+    if not extras:
         ceil = {"leaf_per_s": 1.0, "node_per_s": 1.0, "node_clock_ghz": 0.0, "leaf_cycles_per_wave_compression": 0.0, "node_cycles_per_wave_compression": 0.0}
     else:
         ceil = ctx.blake2s_ceiling_ex()  # measured now, on this device, with the clock read inside the kernel (frieda_ctx_blake2s_ceiling_ex)
@@ -1295,7 +1334,7 @@ def main():
 
     if args.only_measured_loop:
         valu = {"skipped": "--only-measured-loop: neither the ceiling nor the per-kernel replay was measured"}
-    elif n >= 16:
+    elif args.full and n >= 16:
         first = valu_entry("ntt_last_tree7", float(1 << n), 7, "leaf + 6 node levels; the launch also runs 12 transform layers on 4 columns") or \
             valu_entry("tree5_leaf", float(1 << n), 5, "leaf + 4 node levels")
         fold = valu_entry("tree5_fold_circle", float(1 << (n - 1)), 5, "fold + leaf + 4 node levels of the first FRI layer") if args.workload == "prove" else None
@@ -1317,6 +1356,7 @@ def main():
         "vs_baseline": None,
         "dtype": "u32",
         "data": "synthetic",
+        "full": args.full,
         "config": {
             "workload": f"commit_and_generate_proof, 2^{n} domain" if args.workload == "prove" else f"commit, 2^{n} domain",
             "log_domain": n,
@@ -1340,9 +1380,9 @@ def main():
             "algorithmic_bytes_per_step": path_bytes,
             "achieved_GBps_wall": path_bytes / (dt / args.steps) / 1e9,
             "frac_of_hbm_peak_wall": path_bytes / (dt / args.steps) / 1e9 / HBM_PEAK_GBS,
-            "gpu_kernel_ms_per_step": gpu_ms,
-            "launches_per_lone_proof": sum(k["launches"] for k in kern) / args.steps,
-            "launches_per_blob_in_measured_loop": sum(k["launches"] for k in kern) / args.steps / (max(batch_cut(K)) if BSZ != 1 else 1),
+            "gpu_kernel_ms_per_step": gpu_ms if kern else None,  # (None: no instrumented replay in this run)
+            "launches_per_lone_proof": sum(k["launches"] for k in kern) / args.steps if kern else None,
+            "launches_per_blob_in_measured_loop": sum(k["launches"] for k in kern) / args.steps / (max(batch_cut(K)) if BSZ != 1 else 1) if kern else None,
             "host_phase_marks_ms_last_step": host_phases,
             "frac_of_hbm_peak_kernels": (path_bytes / (gpu_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if gpu_ms > 0 else None,
             "kernels": [

@@ -4,7 +4,11 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
+
+from conftest import splitmix64_bytes
+from util import blob_len_for
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -26,7 +30,7 @@ def _bench(argv, env_extra=None):
 @pytest.mark.parametrize("extra", [[], ["--batch", "1"], ["--batch", "1", "--in-flight", "1"], ["--workload", "commit"], ["--no-twiddle-cache"]],
                          ids=["default", "single_in_flight2", "one_at_a_time", "commit", "uncached"])
 def test_bench_line_small_domain(extra):
-    d = _bench(["--log-domain", "16", "--cpu-sample-log", "16", "--steps", "9", "--warmup", "2"] + extra)
+    d = _bench(["--full", "--log-domain", "16", "--cpu-sample-log", "16", "--steps", "9", "--warmup", "2"] + extra)
     for k in REQUIRED:
         assert k in d, k
     assert d["n_gpus"] == 1 and d["steps"] == 9 and d["warmup"] == 2 and d["higher_is_better"] is True and d["scaling"] == "weak"
@@ -51,10 +55,36 @@ def test_bench_line_small_domain(extra):
     assert d["by_config"] == []  # nothing at or below 2^16 in BASELINE.json's configurations
 
 
+@pytest.mark.parametrize("workload", ["prove", "commit"])
+def test_plain_bench_line_is_lean_and_dumps_the_last_step(workload, tmp_path, oracle):
+    """A plain run (no --full) carries the headline and nothing that takes runs of its own; --dump-outputs writes what the timed path
+    returned for its LAST blob (generator seed 100 + K - 1): root (and proof) byte-identical to the oracle's for that blob."""
+    K, out = 5, tmp_path / "out"
+    d = _bench(["--gpus", "1", "--log-domain", "16", "--steps", str(K), "--warmup", "2", "--workload", workload, "--dump-outputs", str(out)])
+    assert d["full"] is False and d["n_gpus"] == 1 and d["steps"] == K and d["warmup"] == 2
+    assert d["metric"] == "M31 field-elems/s committed (NTT+FRI+Merkle)" and d["unit"] == "M31 field-elems/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "u32" and d["value"] > 0 and abs(d["value"] - 4.0 * (1 << 16) * K / (d["ms_per_step"] * K * 1e-3)) / d["value"] < 1e-6
+    assert d["roofline"] is None and d["roofline_valu"] is None and d["cpu_baseline"] is None and d["verified_proofs"] is None
+    assert d["sequential"] is None and d["batched"] is None and d["uncached_twiddles"] is None and d["path"]["kernels"] == []
+    for k in ("end_to_end", "reconstruct", "by_config", "value_fixed_batch4", "single_process_multi"):
+        assert k not in d, k
+    data = splitmix64_bytes(100 + K - 1, blob_len_for(16))
+    root = np.load(out / "root.npy")
+    assert root.dtype == np.float32 and root.shape == (32,)
+    if workload == "prove":
+        o_root, o_proof = oracle.commit_and_generate_proof(data, data.size, oracle.make_config(20, 4, 0, 20))
+        proof = np.load(out / "proof.npy")
+        assert proof.dtype == np.float32 and bytes(proof.astype(np.uint8)) == o_proof.serialize()
+    else:
+        o_root = oracle.commit(data, 4)
+        assert not (out / "proof.npy").exists()
+    assert bytes(root.astype(np.uint8)) == bytes(o_root)
+
+
 def test_bench_line_carries_the_other_baseline_configs():
     """by_config: the 2^20 proof stream and the 2^22 commit stream beside a 2^22 headline (the driver's default run carries 2^20, 2^22 and
     the 2^24 commit beside the 2^24 headline)."""
-    d = _bench(["--log-domain", "22", "--cpu-sample-log", "16", "--steps", "8", "--warmup", "1", "--batch-extra", "0", "--sequential-extra", "4"])
+    d = _bench(["--full", "--log-domain", "22", "--cpu-sample-log", "16", "--steps", "8", "--warmup", "1", "--batch-extra", "0", "--sequential-extra", "4"])
     cfg2 = [r for r in d["by_config"] if r["workload"].startswith("configs[1]")]
     assert len(cfg2) == 1 and cfg2[0]["log_domain"] == 20 and cfg2[0]["ms_per_pass"] > 0 and 0 < cfg2[0]["frac_of_hbm_peak_wall"] < 1
     rows = {(r["log_domain"], r["workload"]): r for r in d["by_config"] if not r["workload"].startswith("configs[1]")}
@@ -82,7 +112,7 @@ def test_bench_forced_collective_one_rank():
     """RCCL init, root all_gather, barrier and max-reduce with a single rank: the N > 1 code path on a one-GPU box.  The line of that
     path is self-sufficient: cpu_baseline (computed by rank 0 after the process group is gone), roofline, roofline_valu, and the
     single-process frieda_prove_many leg from a fresh child process with its roots checked against the per-rank run's."""
-    d = _bench(["--gpus", "1", "--log-domain", "16", "--cpu-sample-log", "16", "--steps", "6", "--warmup", "1", "--batch-extra", "0", "--sequential-extra", "0"],
+    d = _bench(["--full", "--gpus", "1", "--log-domain", "16", "--cpu-sample-log", "16", "--steps", "6", "--warmup", "1", "--batch-extra", "0", "--sequential-extra", "0"],
                env_extra={"FRIEDA_BENCH_FORCE_DIST": "1"})
     assert d["n_gpus"] == 1 and d["verified_proofs"] == 6
     assert d["cpu_baseline"]["root_equals_gpu_root"] is True and d["cpu_baseline"]["multi_core_all"]["all_usable_cores"] is True

@@ -323,3 +323,31 @@ def test_traffic_fingerprint_is_one_function():
     val, src, per_blob = b.traffic_from_profiles("tree5_leaf", 24, "prove")  # (the dominant launch of a proof since round 5)
     assert val and val > 1e8 and "collected at commit" in src and ("unchanged since" in src or "STALE" in src)
     assert b.traffic_from_profiles("tree5_leaf", 22, "prove")[0] is None
+
+
+def test_bench_plain_run_leaves_the_extras_to_full(tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` runs the headline alone: every extra block is off unless --full asks for it.
+    --dump-outputs writes byte strings as float32 arrays, exactly, and refuses more than 64 MB."""
+    import importlib.util
+    import os
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(root, "bench.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    plain = b.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert plain.steps == 7 and plain.warmup == 2 and not plain.full and plain.dump_outputs is None
+    assert plain.no_cpu_baseline and plain.no_by_config and plain.no_end_to_end and plain.no_reconstruct and plain.no_single_process_multi
+    assert plain.batch_extra == 0 and plain.sequential_extra == 0
+    full = b.parse_args(["--full", "--dump-outputs", str(tmp_path)])
+    assert full.full and full.dump_outputs == str(tmp_path)
+    assert not (full.no_cpu_baseline or full.no_by_config or full.no_end_to_end or full.no_reconstruct or full.no_single_process_multi)
+    assert full.batch_extra == 4 and full.sequential_extra == 20
+    img = bytes(range(256)) * 3
+    b.dump_outputs(str(tmp_path / "d"), {"root": img[:32], "proof": img})
+    got = np.load(tmp_path / "d" / "proof.npy")
+    assert got.dtype == np.float32 and bytes(got.astype(np.uint8)) == img
+    assert bytes(np.load(tmp_path / "d" / "root.npy").astype(np.uint8)) == img[:32]
+    with pytest.raises(RuntimeError):
+        b.dump_outputs(str(tmp_path / "big"), {"x": bytes(b.DUMP_LIMIT_BYTES // 4 + 1)})
+    assert not (tmp_path / "big").exists()

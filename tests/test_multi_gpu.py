@@ -164,7 +164,7 @@ def _run_bench(argv, env_extra=None, timeout=300):
 def test_bench_self_launches_its_ranks(gpus):
     """`python bench.py --gpus N` (no torch.distributed.run, no WORLD_SIZE) spawns its N ranks itself and relays rank 0's single
     JSON line.  `--dry-collective gloo` keeps the launcher, rendezvous, barriers, root all_gather and max-reduce and stubs the GPU."""
-    r, docs = _run_bench(["--gpus", str(gpus), "--steps", "5", "--warmup", "1", "--dry-collective", "gloo", "--cpu-sample-log", "12"])
+    r, docs = _run_bench(["--full", "--gpus", str(gpus), "--steps", "5", "--warmup", "1", "--dry-collective", "gloo", "--cpu-sample-log", "12"])
     assert r.returncode == 0, r.stderr[-2000:]
     assert len(docs) == 1 and r.stdout.count("\n") == 1
     d = docs[0]
@@ -180,9 +180,17 @@ def test_bench_self_launches_its_ranks(gpus):
     assert "roofline" in d and "roofline_valu" in d
 
 
+def test_bench_plain_self_launch_carries_the_headline_only():
+    """Without --full an N > 1 line is the headline alone: no CPU legs, no single-process leg (those are what --full adds)."""
+    r, docs = _run_bench(["--gpus", "2", "--steps", "3", "--warmup", "1", "--dry-collective", "gloo"])
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert len(docs) == 1 and docs[0]["n_gpus"] == 2 and docs[0]["roots_gathered"] == 6 and docs[0]["steps"] == 3
+    assert docs[0]["cpu_baseline"] is None and "single_process_multi" not in docs[0]
+
+
 def test_bench_single_process_leg_failure_is_reported_in_place():
     """The extra leg must never cost the line its headline: a child that cannot start its devices is an `error` entry."""
-    r, docs = _run_bench(["--gpus", "2", "--steps", "2", "--dry-collective", "gloo", "--no-cpu-baseline", "--spm-timeout", "0.001"])
+    r, docs = _run_bench(["--full", "--gpus", "2", "--steps", "2", "--dry-collective", "gloo", "--no-cpu-baseline", "--spm-timeout", "0.001"])
     assert r.returncode == 0 and len(docs) == 1
     assert "error" in docs[0]["single_process_multi"] and docs[0]["n_gpus"] == 2 and docs[0]["cpu_baseline"] is None
 
@@ -193,7 +201,7 @@ def test_bench_under_an_external_launcher_does_not_respawn():
 
     port = _free_port()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port",
-           str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--dry-collective", "gloo", "--cpu-sample-log", "10"]
+           str(port), os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "3", "--warmup", "1", "--dry-collective", "gloo", "--cpu-sample-log", "10"]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=env)
     assert r.returncode == 0, r.stderr[-2000:]

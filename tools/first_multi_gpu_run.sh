@@ -3,7 +3,7 @@
 # No N > 1 hardware run has happened in six rounds (the pool hands out one-GPU boxes): everything multi-GPU is rehearsed against an RCCL
 # test double and gloo.  Whoever gets a node runs this from the repository root; it needs no network and writes under gpurun_out/multi/.
 #   1. the GPU tests that skip below two visible GPUs (real RCCL root gather from C++ and Python, BASELINE configs[3] as written)
-#   2. bench.py --gpus 1 / 2 / 4 / 8 --steps 20, each in a fresh process (one rank per GPU over RCCL; bench.py starts its own ranks)
+#   2. bench.py --full --gpus 1 / 2 / 4 / 8 --steps 20, each in a fresh process (one rank per GPU over RCCL; bench.py starts its own ranks)
 #   3. the single-process path over all GPUs (frieda_prove_many / frieda_commit_many: one process, ncclCommInitAll)
 # and prints, per N: ranks RCCL saw, roots equal on every rank, aggregate M31 elems/s, efficiency against N = 1.
 # Every step runs under its own timeout and the script stops at the first GPU step that fails or times out (no retries).
@@ -27,7 +27,7 @@ rc=$?; tail -3 $OUT/tests.log
 echo "== 2. bench.py, one rank per GPU"
 for N in 1 2 4 8; do
   [ "$N" -gt "$MAX" ] && continue
-  timeout -k 10 1500 python3 bench.py --gpus $N --steps 20 --warmup 3 > $OUT/bench_n$N.json 2> $OUT/bench_n$N.err
+  timeout -k 10 1500 python3 bench.py --full --gpus $N --steps 20 --warmup 3 > $OUT/bench_n$N.json 2> $OUT/bench_n$N.err
   rc=$?
   if [ $rc -ne 0 ]; then echo "bench.py --gpus $N failed (rc $rc): $OUT/bench_n$N.err"; tail -5 $OUT/bench_n$N.err; exit 1; fi
 done

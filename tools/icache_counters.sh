@@ -5,7 +5,7 @@
 export TMPDIR=/tmp
 for kv in "$@"; do export "$kv"; done
 rm -rf gpurun_out/pmc_ic
-ONE="--no-cpu-baseline --no-by-config --no-end-to-end --no-reconstruct --batch 1 --in-flight 1 --batch-extra 0 --sequential-extra 0"
+ONE="--full --no-cpu-baseline --no-by-config --no-end-to-end --no-reconstruct --batch 1 --in-flight 1 --batch-extra 0 --sequential-extra 0"
 rocprofv3 --kernel-trace --pmc SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES SQC_ICACHE_MISSES_DUPLICATE SQ_IFETCH SQ_WAVE_CYCLES SQ_WAIT_INST_ANY --output-format csv -d gpurun_out/pmc_ic -- python3 bench.py --steps 3 --warmup 1 $ONE > /dev/null 2> gpurun_out/pmc_ic_err.txt
 python3 - <<PY
 import csv, glob, collections, re

@@ -11,7 +11,7 @@ COMMIT=${2:-}
 OUT=gpurun_out/refresh
 mkdir -p $OUT
 export TMPDIR=/tmp
-ONE="--no-cpu-baseline --no-by-config --no-end-to-end --no-reconstruct --batch 1 --in-flight 1 --batch-extra 0 --sequential-extra 0"
+ONE="--full --no-cpu-baseline --no-by-config --no-end-to-end --no-reconstruct --batch 1 --in-flight 1 --batch-extra 0 --sequential-extra 0"
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -- python3 bench.py --steps 2 --warmup 1 $ONE > /dev/null 2> $OUT/pmc_fetch_err.txt
 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $OUT/pmc_write -- python3 bench.py --steps 2 --warmup 1 $ONE > /dev/null 2> $OUT/pmc_write_err.txt
 # the same two passes in the measured loop's mode with 4 blobs per call, 2 calls in flight: launches cover 4 blobs each
@@ -25,11 +25,11 @@ cp $(ls $OUT/pmc_write/*/*counter_collection.csv | head -1) $OUT/${TAG}_prove24_
 cp $(ls $OUT/pmc_fetch_b/*/*counter_collection.csv | head -1) $OUT/${TAG}_prove24_batched_pmc_FETCH_SIZE.csv
 cp $(ls $OUT/pmc_write_b/*/*counter_collection.csv | head -1) $OUT/${TAG}_prove24_batched_pmc_WRITE_SIZE.csv
 if [ -z "${ONLY_PROF:-}" ]; then
-python bench.py > $OUT/${TAG}_prove24_bench.json 2> $OUT/prove_err.txt
-python bench.py --workload commit > $OUT/${TAG}_commit24_bench.json 2> $OUT/commit_err.txt
-python bench.py --log-domain 22 --cpu-sample-log 22 > $OUT/${TAG}_prove22_bench.json 2> $OUT/prove22_err.txt
-python bench.py --log-domain 20 --cpu-sample-log 20 > $OUT/${TAG}_prove20_bench.json 2> $OUT/prove20_err.txt
-python bench.py --workload commit --log-domain 22 --cpu-sample-log 22 > $OUT/${TAG}_commit22_bench.json 2> $OUT/commit22_err.txt
+python bench.py --full > $OUT/${TAG}_prove24_bench.json 2> $OUT/prove_err.txt
+python bench.py --full --workload commit > $OUT/${TAG}_commit24_bench.json 2> $OUT/commit_err.txt
+python bench.py --full --log-domain 22 --cpu-sample-log 22 > $OUT/${TAG}_prove22_bench.json 2> $OUT/prove22_err.txt
+python bench.py --full --log-domain 20 --cpu-sample-log 20 > $OUT/${TAG}_prove20_bench.json 2> $OUT/prove20_err.txt
+python bench.py --full --workload commit --log-domain 22 --cpu-sample-log 22 > $OUT/${TAG}_commit22_bench.json 2> $OUT/commit22_err.txt
 fi
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 bench.py --steps 10 --warmup 3 $ONE > $OUT/stats_run.json 2> $OUT/stats_err.txt
 cp $(ls $OUT/stats/*/*kernel_stats.csv | head -1) $OUT/${TAG}_prove24_kernel_stats.csv
