@@ -128,6 +128,36 @@ extern "C" {
     /// Column::at for a BaseField column / a SecureColumn (SoA); synchronises the ctx stream
     pub fn frieda_dev_at(ctx: *mut frieda_ctx, d_col: *const u32, index: usize, out: *mut u32) -> c_int;
     pub fn frieda_dev_at_secure(ctx: *mut frieda_ctx, d_cols: *const u32, stride: usize, index: usize, out: *mut u32) -> c_int;
+    pub fn frieda_dev_gather(ctx: *mut frieda_ctx, d_cols: *const u32, stride: usize, ncols: u32, idx: *const u64, n: usize, out: *mut u32) -> c_int;
+    pub fn frieda_dev_gather_hashes(ctx: *mut frieda_ctx, d_layer: *const c_void, layer_len: usize, idx: *const u64, n: usize, out: *mut u8) -> c_int;
+    pub fn frieda_dev_gather_device(ctx: *mut frieda_ctx, d_cols: *const u32, stride: usize, ncols: u32, d_idx: *const u64, n: usize, d_out: *mut u32) -> c_int;
+    pub fn frieda_merkle_decommit(
+        ctx: *mut frieda_ctx,
+        d_layers: *const *const c_void,
+        log_size: u32,
+        d_cols: *const u32,
+        ncols: u32,
+        stride: usize,
+        positions: *const u32,
+        n_pos: usize,
+        out_values: *mut u32,
+        out_hashes: *mut u8,
+        cap_hashes: usize,
+        n_hashes: *mut usize,
+    ) -> c_int;
+    pub fn frieda_merkle_decommit_device(
+        ctx: *mut frieda_ctx,
+        d_layers: *const *const c_void,
+        log_size: u32,
+        d_cols: *const u32,
+        ncols: u32,
+        stride: usize,
+        d_positions: *const u32,
+        n_pos: usize,
+        d_out_values: *mut u32,
+        d_out_hashes: *mut c_void,
+        d_n_hashes: *mut u32,
+    ) -> c_int;
     /// ColumnOps::bit_reverse_column, in place (ncols = 1: BaseField column; 4: SecureColumn)
     pub fn frieda_bit_reverse_column(ctx: *mut frieda_ctx, d_cols: *mut u32, stride: usize, ncols: u32, log_size: u32) -> c_int;
     pub fn frieda_codec_shape(len: usize, n_felts: *mut usize, n_padded: *mut usize, log_size: *mut u32) -> c_int;

@@ -145,6 +145,11 @@ def lib():
         "frieda_dev_download": (C.c_int, [vp, vp, vp, sz]),
         "frieda_dev_at": (C.c_int, [vp, vp, sz, C.POINTER(u32)]),
         "frieda_dev_at_secure": (C.c_int, [vp, vp, sz, sz, C.POINTER(u32)]),
+        "frieda_dev_gather": (C.c_int, [vp, vp, sz, u32, vp, sz, vp]),
+        "frieda_dev_gather_hashes": (C.c_int, [vp, vp, sz, vp, sz, vp]),
+        "frieda_dev_gather_device": (C.c_int, [vp, vp, sz, u32, vp, sz, vp]),
+        "frieda_merkle_decommit": (C.c_int, [vp, pp, u32, vp, u32, sz, vp, sz, vp, vp, sz, C.POINTER(sz)]),
+        "frieda_merkle_decommit_device": (C.c_int, [vp, pp, u32, vp, u32, sz, vp, sz, vp, vp, vp]),
         "frieda_bit_reverse_column": (C.c_int, [vp, vp, sz, u32, u32]),
         "frieda_codec_shape": (C.c_int, [sz, C.POINTER(sz), C.POINTER(sz), C.POINTER(u32)]),
         "frieda_unpack30": (C.c_int, [vp, vp, sz, vp, sz]),

@@ -65,6 +65,11 @@ def _seed_ptr(seed):
     return C.byref(C.c_uint64(seed)) if seed is not None else None
 
 
+def _ptr(p):
+    """a device pointer given as int, c_void_p or None -> int or None"""
+    return p.value if isinstance(p, C.c_void_p) else p
+
+
 def _as_bytes(data):
     if isinstance(data, np.ndarray):
         return np.ascontiguousarray(data, dtype=np.uint8)
@@ -159,6 +164,48 @@ class Context:
     def commit_device(self, d_ptr, length, log_blowup_factor, d_root_ptr):
         """Blob and 32-byte root both in device memory; asynchronous on the context stream."""
         _check(self._L.frieda_commit_device(self._h, d_ptr, length, log_blowup_factor, d_root_ptr), self._h)
+
+    # ---- Level B openings over caller device buffers (pointers as int or c_void_p; host arrays in, numpy / bytes out) ----
+    def dev_gather(self, d_cols, stride, ncols, idx):
+        """Batched Column::at (frieda_dev_gather): uint32[n, ncols], row r = the values of the ncols columns (`stride` words apart,
+        `stride` words long) at idx[r].  Any order, repeats allowed; an index >= stride raises FriedaError."""
+        ix = np.ascontiguousarray(idx, dtype=np.uint64).reshape(-1)
+        out = np.zeros((ix.size, ncols), dtype=np.uint32)
+        _check(self._L.frieda_dev_gather(self._h, _ptr(d_cols), stride, ncols, ix.ctypes.data, ix.size, out.ctypes.data), self._h)
+        return out
+
+    def dev_gather_hashes(self, d_layer, layer_len, idx):
+        """The 32-byte hashes at idx of a layer of layer_len hashes (frieda_dev_gather_hashes), concatenated."""
+        ix = np.ascontiguousarray(idx, dtype=np.uint64).reshape(-1)
+        out = np.zeros(32 * ix.size, dtype=np.uint8)
+        _check(self._L.frieda_dev_gather_hashes(self._h, _ptr(d_layer), layer_len, ix.ctypes.data, ix.size, out.ctypes.data), self._h)
+        return out.tobytes()
+
+    def merkle_decommit(self, d_layers, log_size, d_cols, ncols, stride, positions):
+        """MerkleProver::decommit of a tree whose columns all sit on the leaf layer (frieda_merkle_decommit).  d_layers: log_size + 1
+        device pointers by layer log; positions strictly ascending, < 2^log_size.  -> (values uint32[n_pos, ncols], hash witness bytes
+        in stwo's order)."""
+        pos = np.ascontiguousarray(positions, dtype=np.uint32).reshape(-1)
+        layers = (C.c_void_p * (log_size + 1))(*[_ptr(p) for p in d_layers])
+        vals = np.zeros((pos.size, ncols), dtype=np.uint32)
+        n = C.c_size_t(0)
+
+        def call(buf, cap):
+            return self._L.frieda_merkle_decommit(
+                self._h, layers, log_size, _ptr(d_cols), ncols, stride, pos.ctypes.data, pos.size, vals.ctypes.data, buf, cap, C.byref(n)
+            )
+
+        # no witness is longer than sum_s min(n_pos, 2^(log_size - s)); where that bound is large (dense lists, whose witness is short)
+        # the length is asked for first
+        cap = sum(min(pos.size, 1 << (log_size - s)) for s in range(1, log_size + 1))
+        if cap > (1 << 21):
+            st = call(None, 0)
+            if st != _lib.ERR_ARG:
+                _check(st, self._h)
+            cap = n.value
+        hashes = np.zeros(max(32 * cap, 1), dtype=np.uint8)
+        _check(call(hashes.ctypes.data, cap), self._h)
+        return vals, hashes[: 32 * n.value].tobytes()
 
     # ---- reconstruction side (host arrays in, bytes out; the device entry points are frieda_reconstruct_*_device) ----
     def _dev_call_with_upload(self, host_arr, n_out_bytes, call):

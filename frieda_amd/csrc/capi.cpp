@@ -599,6 +599,184 @@ int frieda_dev_at_secure(frieda_ctx* ctx, const uint32_t* d_cols, size_t stride,
     FR_HIP(&ctx->c, hipStreamSynchronize(ctx->c.stream));
     return FRIEDA_OK;
 }
+// ---- Level B openings (opening.hip): batched Column::at and MerkleProver::decommit ----
+// The host forms stage the index / position list and the results through the arena and the pinned block: one upload, the
+// launches, one download, one synchronisation.
+int frieda_dev_gather(frieda_ctx* ctx, const uint32_t* d_cols, size_t stride, uint32_t ncols, const uint64_t* idx, size_t n, uint32_t* out) {
+    if (!ctx) return FRIEDA_ERR_ARG;
+    if (n == 0) return FRIEDA_OK;
+    if (!d_cols || !idx || !out || ncols == 0 || ncols > 65535) return FRIEDA_ERR_ARG;
+    for (size_t i = 0; i < n; i++)
+        if (idx[i] >= stride) return ctx->c.fail(FRIEDA_ERR_ARG, "gather index " + std::to_string(idx[i]) + " >= column length " + std::to_string(stride));
+    FR_NO_JOB(&ctx->c);
+    FR_GUARD_BEGIN
+    FR_HIP(&ctx->c, hipSetDevice(ctx->c.device));
+    const size_t ib = sizeof(uint64_t) * n, ob = sizeof(uint32_t) * n * ncols;
+    ArenaPlan ap;
+    const size_t a_idx = ap.take(ib), a_out = ap.take(ob);
+    int rc = ctx->c.ensure_arena(ap.off);
+    if (rc) return rc;
+    const size_t p_out = (ib + 255) & ~(size_t)255;
+    rc = ensure_pinned(&ctx->c, p_out + ob);
+    if (rc) return rc;
+    hipStream_t s = ctx->c.stream;
+    uint8_t* pin = static_cast<uint8_t*>(ctx->c.pinned);
+    memcpy(pin, idx, ib);
+    FR_HIP(&ctx->c, hipMemcpyAsync(ctx->c.arena + a_idx, pin, ib, hipMemcpyHostToDevice, s));
+    k::gather_rows(ctx->c.launch(), d_cols, stride, ncols, reinterpret_cast<const uint64_t*>(ctx->c.arena + a_idx), n,
+                   reinterpret_cast<uint32_t*>(ctx->c.arena + a_out));
+    FR_HIP(&ctx->c, hipGetLastError());
+    FR_HIP(&ctx->c, hipMemcpyAsync(pin + p_out, ctx->c.arena + a_out, ob, hipMemcpyDeviceToHost, s));
+    FR_HIP(&ctx->c, hipStreamSynchronize(s));
+    memcpy(out, pin + p_out, ob);
+    return FRIEDA_OK;
+    FR_GUARD_END(ctx)
+}
+
+int frieda_dev_gather_device(frieda_ctx* ctx, const uint32_t* d_cols, size_t stride, uint32_t ncols, const uint64_t* d_idx, size_t n,
+                             uint32_t* d_out) {
+    if (!ctx) return FRIEDA_ERR_ARG;
+    if (n == 0) return FRIEDA_OK;
+    if (!d_cols || !d_idx || !d_out || ncols == 0 || ncols > 65535) return FRIEDA_ERR_ARG;
+    FR_HIP(&ctx->c, hipSetDevice(ctx->c.device));
+    k::gather_rows(ctx->c.launch(), d_cols, stride, ncols, d_idx, n, d_out);
+    FR_HIP(&ctx->c, hipGetLastError());
+    return FRIEDA_OK;
+}
+
+int frieda_dev_gather_hashes(frieda_ctx* ctx, const void* d_layer, size_t layer_len, const uint64_t* idx, size_t n, uint8_t* out) {
+    if (!ctx) return FRIEDA_ERR_ARG;
+    if (n == 0) return FRIEDA_OK;
+    if (!d_layer || !idx || !out) return FRIEDA_ERR_ARG;
+    if (reinterpret_cast<uintptr_t>(d_layer) & 15) return ctx->c.fail(FRIEDA_ERR_ARG, "hash layer not 16-byte aligned");
+    for (size_t i = 0; i < n; i++)
+        if (idx[i] >= layer_len) return ctx->c.fail(FRIEDA_ERR_ARG, "hash index " + std::to_string(idx[i]) + " >= layer length " + std::to_string(layer_len));
+    FR_NO_JOB(&ctx->c);
+    FR_GUARD_BEGIN
+    FR_HIP(&ctx->c, hipSetDevice(ctx->c.device));
+    const size_t ib = sizeof(uint64_t) * n, ob = 32 * n;
+    ArenaPlan ap;
+    const size_t a_idx = ap.take(ib), a_out = ap.take(ob);
+    int rc = ctx->c.ensure_arena(ap.off);
+    if (rc) return rc;
+    const size_t p_out = (ib + 255) & ~(size_t)255;
+    rc = ensure_pinned(&ctx->c, p_out + ob);
+    if (rc) return rc;
+    hipStream_t s = ctx->c.stream;
+    uint8_t* pin = static_cast<uint8_t*>(ctx->c.pinned);
+    memcpy(pin, idx, ib);
+    FR_HIP(&ctx->c, hipMemcpyAsync(ctx->c.arena + a_idx, pin, ib, hipMemcpyHostToDevice, s));
+    k::gather_hashes(ctx->c.launch(), static_cast<const uint8_t*>(d_layer), layer_len, reinterpret_cast<const uint64_t*>(ctx->c.arena + a_idx), n,
+                     ctx->c.arena + a_out);
+    FR_HIP(&ctx->c, hipGetLastError());
+    FR_HIP(&ctx->c, hipMemcpyAsync(pin + p_out, ctx->c.arena + a_out, ob, hipMemcpyDeviceToHost, s));
+    FR_HIP(&ctx->c, hipStreamSynchronize(s));
+    memcpy(out, pin + p_out, ob);
+    return FRIEDA_OK;
+    FR_GUARD_END(ctx)
+}
+
+namespace {
+// shape checks shared by the two decommit forms; fills everything of `a` but the position / output pointers
+int decommit_shape(frieda::Ctx* c, const void* const* d_layers, uint32_t log_size, const uint32_t* d_cols, uint32_t ncols, size_t stride,
+                   size_t n_pos, k::DecommitOpen& a) {
+    if (!d_layers || log_size > FRIEDA_MAX_LOG_DOMAIN || ncols > 65535 || (ncols && !d_cols)) return FRIEDA_ERR_ARG;
+    if (ncols > 1 && stride < ((size_t)1 << log_size)) return c->fail(FRIEDA_ERR_ARG, "column stride smaller than the leaf layer");
+    if (n_pos > ((size_t)1 << log_size)) return c->fail(FRIEDA_ERR_ARG, "more positions than leaves");
+    a = k::DecommitOpen{};
+    for (uint32_t j = 0; j <= log_size; j++) {
+        a.tree.layers[j] = static_cast<const uint8_t*>(d_layers[j]);
+        if (j >= 1 && (!d_layers[j] || (reinterpret_cast<uintptr_t>(d_layers[j]) & 15)))
+            return c->fail(FRIEDA_ERR_ARG, "tree layer " + std::to_string(j) + " is null or not 16-byte aligned");
+    }
+    a.log_size = log_size;
+    a.n = (uint32_t)n_pos;
+    a.ncols = ncols;
+    a.cols = d_cols;
+    a.stride = ncols > 1 ? stride : ((size_t)1 << log_size);
+    return FRIEDA_OK;
+}
+}  // namespace
+
+int frieda_merkle_decommit(frieda_ctx* ctx, const void* const* d_layers, uint32_t log_size, const uint32_t* d_cols, uint32_t ncols, size_t stride,
+                           const uint32_t* positions, size_t n_pos, uint32_t* out_values, uint8_t* out_hashes, size_t cap_hashes, size_t* n_hashes) {
+    if (!ctx || !n_hashes || (n_pos && !positions) || (n_pos && ncols && !out_values)) return FRIEDA_ERR_ARG;
+    k::DecommitOpen a;
+    int rc = decommit_shape(&ctx->c, d_layers, log_size, d_cols, ncols, stride, n_pos, a);
+    if (rc) return rc;
+    for (size_t i = 0; i < n_pos; i++)
+        if ((positions[i] >> log_size) != 0 || (i > 0 && positions[i - 1] >= positions[i]))
+            return ctx->c.fail(FRIEDA_ERR_ARG, "positions must be strictly ascending and below 2^log_size (position " + std::to_string(i) + ")");
+    *n_hashes = 0;
+    if (n_pos == 0) return FRIEDA_OK;
+    FR_NO_JOB(&ctx->c);
+    FR_GUARD_BEGIN
+    FR_HIP(&ctx->c, hipSetDevice(ctx->c.device));
+    // the device writes at most `keep` hashes; a longer witness is reported through *n_hashes (and FRIEDA_ERR_ARG)
+    const uint64_t keep = std::min<uint64_t>(out_hashes ? cap_hashes : 0, k::decommit_hash_bound(n_pos, log_size));
+    const size_t pb = sizeof(uint32_t) * n_pos, vb = sizeof(uint32_t) * n_pos * ncols, vb_r = (vb + 255) & ~(size_t)255, hb = 32 * keep;
+    // arena: positions | count word (256 B) | values | hashes | scratch — the three results contiguous, for one download
+    ArenaPlan ap;
+    const size_t a_pos = ap.take(pb), a_res = ap.take(256 + vb_r + hb), a_scr = ap.take(k::decommit_scratch_bytes(a.n, log_size));
+    rc = ctx->c.ensure_arena(ap.off);
+    if (rc) return rc;
+    const size_t p_res = (pb + 255) & ~(size_t)255;
+    rc = ensure_pinned(&ctx->c, p_res + 256 + vb_r + hb);
+    if (rc) return rc;
+    hipStream_t s = ctx->c.stream;
+    uint8_t* pin = static_cast<uint8_t*>(ctx->c.pinned);
+    uint8_t* res = ctx->c.arena + a_res;
+    memcpy(pin, positions, pb);
+    FR_HIP(&ctx->c, hipMemcpyAsync(ctx->c.arena + a_pos, pin, pb, hipMemcpyHostToDevice, s));
+    a.pos = reinterpret_cast<const uint32_t*>(ctx->c.arena + a_pos);
+    a.count = reinterpret_cast<uint32_t*>(res);
+    a.values = reinterpret_cast<uint32_t*>(res + 256);
+    a.hashes = reinterpret_cast<uint4*>(res + 256 + vb_r);
+    a.max_hashes = keep;
+    k::merkle_decommit(ctx->c.launch(), a, ctx->c.tuning.open_small_max, ctx->c.arena + a_scr);
+    FR_HIP(&ctx->c, hipGetLastError());
+    FR_HIP(&ctx->c, hipMemcpyAsync(pin + p_res, res, 256 + vb_r + hb, hipMemcpyDeviceToHost, s));
+    FR_HIP(&ctx->c, hipStreamSynchronize(s));
+    uint32_t total;
+    memcpy(&total, pin + p_res, sizeof(total));
+    if (total == k::OPEN_BAD_COUNT) return ctx->c.fail(FRIEDA_ERR_INVARIANT, "the device refused positions the host accepted");
+    *n_hashes = total;
+    if (total > keep) return ctx->c.fail(FRIEDA_ERR_ARG, "hash witness of " + std::to_string(total) + " hashes exceeds cap_hashes");
+    if (vb) memcpy(out_values, pin + p_res + 256, vb);
+    if (total) memcpy(out_hashes, pin + p_res + 256 + vb_r, 32 * (size_t)total);
+    return FRIEDA_OK;
+    FR_GUARD_END(ctx)
+}
+
+int frieda_merkle_decommit_device(frieda_ctx* ctx, const void* const* d_layers, uint32_t log_size, const uint32_t* d_cols, uint32_t ncols,
+                                  size_t stride, const uint32_t* d_positions, size_t n_pos, uint32_t* d_out_values, void* d_out_hashes,
+                                  uint32_t* d_n_hashes) {
+    if (!ctx || !d_n_hashes || (n_pos && !d_positions) || (n_pos && ncols && !d_out_values) || (n_pos && log_size && !d_out_hashes))
+        return FRIEDA_ERR_ARG;
+    if (reinterpret_cast<uintptr_t>(d_out_hashes) & 15) return ctx->c.fail(FRIEDA_ERR_ARG, "hash output not 16-byte aligned");
+    k::DecommitOpen a;
+    int rc = decommit_shape(&ctx->c, d_layers, log_size, d_cols, ncols, stride, n_pos, a);
+    if (rc) return rc;
+    FR_GUARD_BEGIN
+    FR_HIP(&ctx->c, hipSetDevice(ctx->c.device));
+    a.pos = d_positions;
+    a.count = d_n_hashes;
+    a.values = d_out_values;
+    a.hashes = static_cast<uint4*>(d_out_hashes);
+    a.max_hashes = (uint64_t)n_pos * log_size;
+    void* scratch = nullptr;
+    if (!k::decommit_small_route(a.n, log_size, ctx->c.tuning.open_small_max)) {  // the multi-block route keeps its counts in the arena
+        FR_NO_JOB(&ctx->c);
+        rc = ctx->c.ensure_arena(k::decommit_scratch_bytes(a.n, log_size));
+        if (rc) return rc;
+        scratch = ctx->c.arena;
+    }
+    k::merkle_decommit(ctx->c.launch(), a, ctx->c.tuning.open_small_max, scratch);
+    FR_HIP(&ctx->c, hipGetLastError());
+    return FRIEDA_OK;
+    FR_GUARD_END(ctx)
+}
+
 int frieda_bit_reverse_column(frieda_ctx* ctx, uint32_t* d_cols, size_t stride, uint32_t ncols, uint32_t log_size) {
     if (!ctx || !d_cols || ncols == 0 || ncols > 65535 || log_size > FRIEDA_MAX_LOG_DOMAIN) return FRIEDA_ERR_ARG;
     if (ncols > 1 && stride < ((size_t)1 << log_size)) return ctx->c.fail(FRIEDA_ERR_ARG, "column stride smaller than the column");

@@ -143,6 +143,9 @@ struct ArenaPlan {
     }
 };
 
+// the pinned staging block (Ctx::pinned) of at least `bytes` (reallocated when smaller; callers hold no job: FR_NO_JOB)
+int ensure_pinned(Ctx* ctx, size_t bytes);
+
 // ---- prover / verifier ----
 int commit_device(Ctx* ctx, const uint8_t* d_data, size_t len, uint32_t log_blowup, uint8_t* d_root, bool data_in_arena);
 int commit_host(Ctx* ctx, const uint8_t* data, size_t len, uint32_t log_blowup, uint8_t out_root[32]);

@@ -48,6 +48,7 @@ struct Tuning {
     uint32_t tail_run_log = 9;           // FRIEDA_TAIL_RUN_LOG: layers of more than 2^v points use the multi-workgroup kernels
     bool host_decommit = false;          // FRIEDA_HOST_DECOMMIT: openings by the host planner + gather launch
     bool gather_copy = false;            // FRIEDA_GATHER_COPY: fallback path stages lists and results through device memory + copies
+    uint32_t open_small_max = 512;       // FRIEDA_OPEN_SMALL_MAX: largest position list frieda_merkle_decommit* opens in one workgroup (0: every list multi-block)
     uint32_t test_grind_first_log = 0;   // test hook (frieda_ctx_test_set_grind_first_log): a short first nonce range (0 = off)
     // batch policy (host.h, "batch policy"): workspace bytes a batched call may keep in flight, and the fewest calls a context gets
     uint32_t batch_budget_mb = 0;        // FRIEDA_BATCH_BUDGET_MB: 0 = the default (sixteen proofs of a 2^24 domain, ~43 GB)
@@ -328,6 +329,35 @@ struct DecommitArgs {
     uint32_t skip_log;  // trees of >= 2^skip_log leaves: the two levels above the leaves are re-hashed from vals, not read (Tuning::tree_skip_log)
 };
 void decommit(const Launch& L, const DecommitArgs& a, uint32_t wgs_per_blob);
+
+// ---- opening.hip: Level B openings (frieda_dev_gather*, frieda_merkle_decommit*) ----
+constexpr uint32_t OPEN_BAD_WORD = 0xFFFFFFFFu;   // gathered word of an out-of-range index (device forms only; not a canonical M31)
+constexpr uint32_t OPEN_BAD_COUNT = 0xFFFFFFFFu;  // decommit count word: the positions were not strictly ascending and in range
+constexpr uint32_t OPEN_MAX_LOG = 28;             // = FRIEDA_MAX_LOG_DOMAIN
+constexpr uint32_t OPEN_SMALL_MAX_LIMIT = 512;    // largest position list of the single-workgroup route (Tuning::open_small_max)
+// out[r][c] = d_cols[c * stride + d_idx[r]] for r < n, c < ncols (rows of indices >= stride: OPEN_BAD_WORD)
+void gather_rows(const Launch& L, const uint32_t* d_cols, size_t stride, uint32_t ncols, const uint64_t* d_idx, size_t n, uint32_t* d_out);
+// out[r] = the 32 bytes of hash d_idx[r] of d_layer (layer_len hashes, 16-byte aligned; d_out too)
+void gather_hashes(const Launch& L, const uint8_t* d_layer, size_t layer_len, const uint64_t* d_idx, size_t n, uint8_t* d_out);
+struct OpenTree {
+    const uint8_t* layers[OPEN_MAX_LOG + 1];  // by layer log: 2^j hashes of 32 bytes each (16-byte aligned); layer 0 is never read
+};
+struct DecommitOpen {
+    OpenTree tree;
+    uint32_t log_size, n, ncols;
+    const uint32_t* pos;  // n positions, strictly ascending, < 2^log_size
+    const uint32_t* cols;  // leaf columns, ncols x 2^log_size words, `stride` words apart
+    size_t stride;
+    uint32_t* values;     // out: n x ncols
+    uint4* hashes;        // out: the hash witness, 2 uint4 per hash; at most max_hashes are written
+    uint64_t max_hashes;
+    uint32_t* count;      // out: the witness length (OPEN_BAD_COUNT: malformed positions, nothing else written)
+};
+// sum over s of min(n_pos, 2^(log_size - s)): no witness is longer
+uint64_t decommit_hash_bound(uint64_t n_pos, uint32_t log_size);
+bool decommit_small_route(uint32_t n_pos, uint32_t log_size, uint32_t small_max);
+size_t decommit_scratch_bytes(uint32_t n_pos, uint32_t log_size);  // d_scratch of the multi-block route
+void merkle_decommit(const Launch& L, const DecommitOpen& a, uint32_t small_max, void* d_scratch);
 
 // ---- polyops.hip: PolyOps::{extend, eval_at_point}, FriOps::decompose (trait completeness; not on frieda's path) ----
 struct EvalFactors {

@@ -30,6 +30,8 @@ void hash_to_words(const uint8_t* h, uint32_t (&w)[8]) {
         w[i] = (uint32_t)h[4 * i] | ((uint32_t)h[4 * i + 1] << 8) | ((uint32_t)h[4 * i + 2] << 16) | ((uint32_t)h[4 * i + 3] << 24);
 }
 
+}  // namespace
+
 int ensure_pinned(Ctx* ctx, size_t bytes) {
     if (ctx->pinned_bytes >= bytes) return FRIEDA_OK;
     if (ctx->pinned) FR_HIP(ctx, hipHostFree(ctx->pinned));
@@ -39,6 +41,8 @@ int ensure_pinned(Ctx* ctx, size_t bytes) {
     ctx->pinned_bytes = bytes;
     return FRIEDA_OK;
 }
+
+namespace {
 
 // Small host blobs (the fused small-domain kernel, tree.hip) are not copied to the device at all: they are placed in a page-locked
 // block that the kernel reads directly (one PCIe read per workgroup instead of a copy command in front of the first launch).

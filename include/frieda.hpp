@@ -170,6 +170,32 @@ class Context {
         if (len) check(frieda_dev_download(h_, out.data(), d_out.ptr, len), h_);
         return out;
     }
+    // Level B openings over caller device buffers (frieda_dev_gather, frieda_dev_gather_hashes, frieda_merkle_decommit)
+    // rows[i * ncols + c] = column c at idx[i]
+    std::vector<uint32_t> dev_gather(const uint32_t* d_cols, size_t stride, uint32_t ncols, const std::vector<uint64_t>& idx) {
+        std::vector<uint32_t> out(idx.size() * ncols);
+        check(frieda_dev_gather(h_, d_cols, stride, ncols, idx.data(), idx.size(), out.data()), h_);
+        return out;
+    }
+    std::vector<std::array<uint8_t, 32>> dev_gather_hashes(const void* d_layer, size_t layer_len, const std::vector<uint64_t>& idx) {
+        std::vector<std::array<uint8_t, 32>> out(idx.size());
+        check(frieda_dev_gather_hashes(h_, d_layer, layer_len, idx.data(), idx.size(), idx.empty() ? nullptr : out.data()->data()), h_);
+        return out;
+    }
+    // MerkleProver::decommit of a leaf-columns tree: {queried values [n_pos * ncols], hash witness}
+    std::pair<std::vector<uint32_t>, std::vector<std::array<uint8_t, 32>>> merkle_decommit(const std::vector<const void*>& d_layers, uint32_t log_size,
+                                                                                           const uint32_t* d_cols, uint32_t ncols, size_t stride,
+                                                                                           const std::vector<uint32_t>& positions) {
+        std::vector<uint32_t> values(positions.size() * ncols);
+        size_t n = 0;
+        const size_t bound = positions.size() * (size_t)log_size;
+        std::vector<std::array<uint8_t, 32>> hashes(bound);
+        check(frieda_merkle_decommit(h_, d_layers.data(), log_size, d_cols, ncols, stride, positions.data(), positions.size(), values.data(),
+                                     bound ? hashes.data()->data() : nullptr, bound, &n),
+              h_);
+        hashes.resize(n);
+        return {values, hashes};
+    }
     frieda_ctx* handle() { return h_; }
 
   private:

@@ -136,7 +136,8 @@ int frieda_commit_and_generate_proof_device(frieda_ctx* ctx, const void* d_data,
  * point that sizes or writes the ctx's workspace or pinned block returns FRIEDA_ERR_ARG ("a proof is in flight on this
  * context") and leaves the proof untouched: frieda_commit*, frieda_commit_batch*, a second _begin, frieda_merkle_root,
  * frieda_merkle_commit_layer, frieda_grind, frieda_reconstruct*_device, frieda_circle_interpolate_cells,
- * frieda_ctx_release_workspace.  Level B calls that only read the twiddle cache and caller buffers stay available.
+ * frieda_ctx_release_workspace, frieda_dev_gather, frieda_dev_gather_hashes, frieda_merkle_decommit (and
+ * frieda_merkle_decommit_device beyond 512 positions).  Level B calls that only read the twiddle cache and caller buffers stay available.
  * A blob passed to _begin_device must stay valid until _finish returns. */
 int frieda_prove_begin(frieda_ctx* ctx, const uint8_t* data, size_t len, const uint64_t* seed, frieda_pcs_config cfg);
 int frieda_prove_begin_device(frieda_ctx* ctx, const void* d_data, size_t len, const uint64_t* seed, frieda_pcs_config cfg);
@@ -273,6 +274,44 @@ int frieda_dev_download(frieda_ctx* ctx, void* h_dst, const void* d_src, size_t 
  * frieda_dev_at: M31 column.  frieda_dev_at_secure: QM31 from a SecureColumn d_cols[4][stride] (SoA), out = 4 coordinates. */
 int frieda_dev_at(frieda_ctx* ctx, const uint32_t* d_col, size_t index, uint32_t* out);
 int frieda_dev_at_secure(frieda_ctx* ctx, const uint32_t* d_cols, size_t stride, size_t index, uint32_t out[4]);
+
+/* Batched Column::at — what frieda's evaluation gather (src/proof.rs:62-66, `column.at(q)` per query) and a HipBackend's openings
+ * want instead of one synchronised copy per value.  d_cols: ncols columns `stride` words apart, each `stride` words long (ncols = 4,
+ * stride = 2^log_size: a SecureColumn); idx: host array of n indices in any order, repeats allowed.  out[n][ncols] (host, row-major
+ * per index: with ncols = 4 each row is the QM31 frieda_dev_at_secure returns).  One upload of the indices through the context's
+ * pinned staging, one kernel, one download, one synchronisation.  Any index >= stride: FRIEDA_ERR_ARG before anything is launched,
+ * out untouched.  n = 0 is a no-op.  Uses the context's workspace: FRIEDA_ERR_ARG while a proof is in flight on it. */
+int frieda_dev_gather(frieda_ctx* ctx, const uint32_t* d_cols, size_t stride, uint32_t ncols, const uint64_t* idx, size_t n, uint32_t* out);
+/* the same for a column of 32-byte hashes (one layer of a stored tree: layer_len hashes, 16-byte aligned); out: n x 32 bytes (host) */
+int frieda_dev_gather_hashes(frieda_ctx* ctx, const void* d_layer, size_t layer_len, const uint64_t* idx, size_t n, uint8_t* out);
+/* asynchronous form on the ctx stream: d_idx[n] and d_out[n][ncols] in device memory.  Nothing is checked on the host: the row of an
+ * index >= stride is filled with 0xFFFFFFFF (not a canonical M31).  Available while a proof is in flight. */
+int frieda_dev_gather_device(frieda_ctx* ctx, const uint32_t* d_cols, size_t stride, uint32_t ncols, const uint64_t* d_idx, size_t n,
+                             uint32_t* d_out);
+
+/* MerkleProver::decommit (stwo core/vcs/prover.rs) for a tree whose columns all sit on the leaf layer — the shape of every tree
+ * frieda builds and of frieda_merkle_commit's.  Restriction: trees with columns above the leaf layer are not supported; for this
+ * shape the column witness is always empty, so it is not returned.
+ * d_layers: host array of log_size + 1 device pointers by layer log (layer j: 2^j hashes, 16-byte aligned; layer 0, the root, is not
+ * read) — either a frieda_merkle_commit buffer with pointers d_layers[j] = buf + frieda_merkle_layer_offset(log_size, j), or layers
+ * built one by one with frieda_merkle_commit_layer into separate buffers.  d_cols: the ncols leaf columns (2^log_size words each,
+ * `stride` words apart; ncols = 0: no values).  positions: host, strictly ascending, < 2^log_size (else FRIEDA_ERR_ARG before any
+ * launch); any count up to 2^log_size.  out_values[n_pos][ncols]: the queried column values.  out_hashes: the hash witness in
+ * stwo's order (bottom-up; per layer, per node in ascending order, the left then the right child's hash when that child is not
+ * already known).  *n_hashes receives its length; a cap_hashes smaller than that gives FRIEDA_ERR_ARG (out_hashes == NULL asks
+ * for the size).  No witness is longer than sum over s = 1 .. log_size of min(n_pos, 2^(log_size - s)) <= n_pos * log_size hashes.
+ * One upload, the launches, one download, one synchronisation; uses the context's workspace (FRIEDA_ERR_ARG while a proof is in
+ * flight on it). */
+int frieda_merkle_decommit(frieda_ctx* ctx, const void* const* d_layers, uint32_t log_size, const uint32_t* d_cols, uint32_t ncols, size_t stride,
+                           const uint32_t* positions, size_t n_pos, uint32_t* out_values, uint8_t* out_hashes, size_t cap_hashes, size_t* n_hashes);
+/* asynchronous form on the ctx stream, everything on the device: d_positions[n_pos] in, d_out_values[n_pos][ncols] and the hash witness
+ * (d_out_hashes, 16-byte aligned, sized by the caller for n_pos * log_size hashes) out; the witness length goes to the device word
+ * *d_n_hashes, 0xFFFFFFFF when the positions are not strictly ascending and below 2^log_size (then nothing else is written).  Lists of
+ * up to 512 positions take one launch and no workspace (option FRIEDA_OPEN_SMALL_MAX); longer ones use the context's workspace
+ * (FRIEDA_ERR_ARG while a proof is in flight).  Queue every layer's decommitment, then download once. */
+int frieda_merkle_decommit_device(frieda_ctx* ctx, const void* const* d_layers, uint32_t log_size, const uint32_t* d_cols, uint32_t ncols,
+                                  size_t stride, const uint32_t* d_positions, size_t n_pos, uint32_t* d_out_values, void* d_out_hashes,
+                                  uint32_t* d_n_hashes);
 /* ColumnOps::bit_reverse_column (stwo core/backend/mod.rs; the trait surface `CirclePoly::<CpuBackend>::new` and
  * `SecureCirclePoly` are instantiated over at src/utils.rs:21,28 and src/proof.rs:47-52): in place, v[i] <-> v[brev(i)] over
  * log_size bits, for each of ncols columns of 2^log_size words laid out `stride` words apart (ncols = 1: a BaseField
