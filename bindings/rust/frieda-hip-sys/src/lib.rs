@@ -17,6 +17,10 @@ pub struct frieda_multi {
 pub struct frieda_proof {
     _private: [u8; 0],
 }
+#[repr(C)]
+pub struct frieda_encoded {
+    _private: [u8; 0],
+}
 
 /// stwo `PcsConfig { pow_bits, fri_config: FriConfig { log_blowup_factor, log_last_layer_degree_bound, n_queries } }`
 #[repr(C)]
@@ -81,6 +85,17 @@ extern "C" {
     pub fn frieda_prove_batch_begin(ctx: *mut frieda_ctx, data: *const u8, stride: usize, len: usize, count: u32, seeds: *const u64, cfg: frieda_pcs_config) -> c_int;
     pub fn frieda_prove_batch_begin_device(ctx: *mut frieda_ctx, d_data: *const c_void, stride: usize, len: usize, count: u32, seeds: *const u64, cfg: frieda_pcs_config) -> c_int;
     pub fn frieda_prove_batch_finish(ctx: *mut frieda_ctx, count: u32, out_commitments: *mut u8, out_proofs: *mut *mut frieda_proof) -> c_int;
+    // one blob under many seeds: the seed-independent half of a proof (encode + first tree) kept on the device, then one proof per seed
+    pub fn frieda_encode(ctx: *mut frieda_ctx, data: *const u8, len: usize, log_blowup_factor: u32, out: *mut *mut frieda_encoded) -> c_int;
+    pub fn frieda_encode_device(ctx: *mut frieda_ctx, d_data: *const c_void, len: usize, log_blowup_factor: u32, out: *mut *mut frieda_encoded) -> c_int;
+    pub fn frieda_encoded_commitment(enc: *const frieda_encoded, out_root: *mut u8) -> c_int;
+    pub fn frieda_encoded_bytes(enc: *const frieda_encoded) -> usize;
+    pub fn frieda_encoded_free(enc: *mut frieda_encoded);
+    pub fn frieda_prove_seeds_begin(ctx: *mut frieda_ctx, enc: *const frieda_encoded, seeds: *const u64, n_seeds: u32, cfg: frieda_pcs_config) -> c_int;
+    pub fn frieda_prove_seeds_finish(ctx: *mut frieda_ctx, out_proofs: *mut *mut frieda_proof) -> c_int;
+    pub fn frieda_prove_seeds(ctx: *mut frieda_ctx, enc: *const frieda_encoded, seeds: *const u64, n_seeds: u32, cfg: frieda_pcs_config, out_proofs: *mut *mut frieda_proof) -> c_int;
+    pub fn frieda_commit_and_generate_proofs_for_seeds(ctx: *mut frieda_ctx, data: *const u8, len: usize, seeds: *const u64, n_seeds: u32, cfg: frieda_pcs_config, out_commitment: *mut u8, out_proofs: *mut *mut frieda_proof) -> c_int;
+    pub fn frieda_seeds_workspace_bytes(len: usize, cfg: frieda_pcs_config, n_seeds: u32) -> usize;
     pub fn frieda_commit_batch(ctx: *mut frieda_ctx, data: *const u8, stride: usize, len: usize, count: u32, log_blowup_factor: u32, out_roots: *mut u8) -> c_int;
     pub fn frieda_commit_batch_device(ctx: *mut frieda_ctx, d_data: *const c_void, stride: usize, len: usize, count: u32, log_blowup_factor: u32, out_roots: *mut u8) -> c_int;
     pub fn frieda_generate_proof(ctx: *mut frieda_ctx, data: *const u8, len: usize, seed: *const u64, cfg: frieda_pcs_config, out: *mut *mut frieda_proof) -> c_int;
@@ -221,10 +236,41 @@ impl Context {
         check(unsafe { frieda_commit_and_generate_proof(self.0, data.as_ptr(), data.len(), sp, cfg, root.as_mut_ptr(), &mut p) });
         (root, Proof(p))
     }
+    /// unpack + encode + first-layer tree, kept on the device: prove from it under any number of seeds
+    pub fn encode(&mut self, data: &[u8], log_blowup_factor: u32) -> Encoded {
+        let mut e = core::ptr::null_mut();
+        check(unsafe { frieda_encode(self.0, data.as_ptr(), data.len(), log_blowup_factor, &mut e) });
+        Encoded(e)
+    }
+    /// proof `i` is `commit_and_generate_proof(data, Some(seeds[i]), cfg).1`, byte for byte
+    pub fn prove_seeds(&mut self, enc: &Encoded, seeds: &[u64], cfg: frieda_pcs_config) -> Vec<Proof> {
+        let mut ps: Vec<*mut frieda_proof> = vec![core::ptr::null_mut(); seeds.len()];
+        check(unsafe { frieda_prove_seeds(self.0, enc.0, seeds.as_ptr(), seeds.len() as u32, cfg, ps.as_mut_ptr()) });
+        ps.into_iter().map(Proof).collect()
+    }
 }
 impl Drop for Context {
     fn drop(&mut self) {
         unsafe { frieda_ctx_destroy(self.0) };
+    }
+}
+
+/// An encoded blob on the device (`frieda_encoded`): only read by proving; freed on drop.
+pub struct Encoded(*mut frieda_encoded);
+impl Encoded {
+    /// `== Context::commit(data, log_blowup_factor)`
+    pub fn commitment(&self) -> [u8; 32] {
+        let mut root = [0u8; 32];
+        check(unsafe { frieda_encoded_commitment(self.0, root.as_mut_ptr()) });
+        root
+    }
+    pub fn bytes(&self) -> usize {
+        unsafe { frieda_encoded_bytes(self.0) }
+    }
+}
+impl Drop for Encoded {
+    fn drop(&mut self) {
+        unsafe { frieda_encoded_free(self.0) };
     }
 }
 

@@ -105,6 +105,16 @@ def lib():
         "frieda_prove_batch_begin": (C.c_int, [vp, vp, sz, sz, u32, u64p, PcsConfigC]),
         "frieda_prove_batch_begin_device": (C.c_int, [vp, vp, sz, sz, u32, u64p, PcsConfigC]),
         "frieda_prove_batch_finish": (C.c_int, [vp, u32, vp, pp]),
+        "frieda_encode": (C.c_int, [vp, vp, sz, u32, pp]),
+        "frieda_encode_device": (C.c_int, [vp, vp, sz, u32, pp]),
+        "frieda_encoded_commitment": (C.c_int, [vp, vp]),
+        "frieda_encoded_bytes": (sz, [vp]),
+        "frieda_encoded_free": (None, [vp]),
+        "frieda_prove_seeds_begin": (C.c_int, [vp, vp, u64p, u32, PcsConfigC]),
+        "frieda_prove_seeds_finish": (C.c_int, [vp, pp]),
+        "frieda_prove_seeds": (C.c_int, [vp, vp, u64p, u32, PcsConfigC, pp]),
+        "frieda_commit_and_generate_proofs_for_seeds": (C.c_int, [vp, vp, sz, u64p, u32, PcsConfigC, vp, pp]),
+        "frieda_seeds_workspace_bytes": (sz, [sz, PcsConfigC, u32]),
         "frieda_commit_batch": (C.c_int, [vp, vp, sz, sz, u32, u32, vp]),
         "frieda_commit_batch_device": (C.c_int, [vp, vp, sz, sz, u32, u32, vp]),
         "frieda_multi_create": (C.c_int, [C.POINTER(C.c_int), u32, pp]),

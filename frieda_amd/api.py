@@ -339,6 +339,53 @@ class Context:
         rb = bytes(roots)
         return [(rb[32 * i : 32 * i + 32], Proof(C.c_void_p(outs[i]))) for i in range(count)]
 
+    # ---- one blob under many seeds: encode once, prove per seed (a provider serving sampling clients) ----
+    def encode(self, data, log_blowup_factor):
+        """Unpack + encode + first-layer tree of `data`, kept on the device: an Encoded to prove from under any number of seeds."""
+        a = _as_bytes(data)
+        out = C.c_void_p()
+        _check(self._L.frieda_encode(self._h, a.ctypes.data if a.size else None, a.size, log_blowup_factor, C.byref(out)), self._h)
+        return Encoded(out, a.size, log_blowup_factor)
+
+    def encode_device(self, d_ptr, length, log_blowup_factor):
+        out = C.c_void_p()
+        _check(self._L.frieda_encode_device(self._h, d_ptr, length, log_blowup_factor, C.byref(out)), self._h)
+        return Encoded(out, length, log_blowup_factor)
+
+    def prove_seeds_begin(self, encoded, seeds, pcs_config):
+        """Enqueue len(seeds) proofs of the encoded blob; `encoded` must stay open until prove_seeds_finish() returns."""
+        seeds = [int(x) for x in seeds]
+        arr = (C.c_uint64 * max(1, len(seeds)))(*seeds)
+        _check(self._L.frieda_prove_seeds_begin(self._h, encoded._handle(), arr, len(seeds), pcs_config._c()), self._h)
+        self._seeds_in_flight = len(seeds)
+
+    def prove_seeds_finish(self):
+        count = getattr(self, "_seeds_in_flight", 0)
+        self._seeds_in_flight = 0
+        outs = (C.c_void_p * max(1, count))()
+        _check(self._L.frieda_prove_seeds_finish(self._h, outs), self._h)
+        return [Proof(C.c_void_p(outs[i])) for i in range(count)]
+
+    def prove_seeds(self, encoded, seeds, pcs_config):
+        """[Proof]: proof i is commit_and_generate_proof(data, seeds[i], pcs_config)[1], byte for byte."""
+        self.prove_seeds_begin(encoded, seeds, pcs_config)
+        return self.prove_seeds_finish()
+
+    def commit_and_generate_proofs_for_seeds(self, data, seeds, pcs_config):
+        """(commitment, [Proof]) for a caller that has every seed at once: encode, prove, free."""
+        a = _as_bytes(data)
+        seeds = [int(x) for x in seeds]
+        arr = (C.c_uint64 * max(1, len(seeds)))(*seeds)
+        root = (C.c_uint8 * 32)()
+        outs = (C.c_void_p * max(1, len(seeds)))()
+        _check(
+            self._L.frieda_commit_and_generate_proofs_for_seeds(
+                self._h, a.ctypes.data if a.size else None, a.size, arr, len(seeds), pcs_config._c(), root, outs
+            ),
+            self._h,
+        )
+        return bytes(root), [Proof(C.c_void_p(outs[i])) for i in range(len(seeds))]
+
     def commit_batch(self, blobs, log_blowup_factor):
         count = len(blobs)
         if count == 0:
@@ -365,6 +412,48 @@ class Context:
         _check(self._L.frieda_prove_finish(self._h, root, C.byref(out)), self._h)
         self._keep = None
         return bytes(root), Proof(out)
+
+
+class Encoded:
+    """An encoded blob on the device (frieda_encoded): evaluations + first-layer tree + root, in an allocation of its own that outlives
+    the context's workspace.  Only read by proving: several contexts of its device may prove from it at once.  close() frees it."""
+
+    def __init__(self, handle, length, log_blowup_factor):
+        self._h = handle
+        self.length = int(length)
+        self.log_blowup_factor = int(log_blowup_factor)
+
+    def _handle(self):
+        if not self._h:
+            raise ValueError("the encoded blob is closed")
+        return self._h
+
+    @property
+    def commitment(self):
+        root = (C.c_uint8 * 32)()
+        _check(_lib.lib().frieda_encoded_commitment(self._handle(), root))
+        return bytes(root)
+
+    @property
+    def nbytes(self):
+        return int(_lib.lib().frieda_encoded_bytes(self._handle()))
+
+    def close(self):
+        if self._h:
+            _lib.lib().frieda_encoded_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
 
 class Proof:
@@ -636,6 +725,11 @@ def workspace_bytes(length, log_blowup_factor, log_last_layer_degree_bound=0, pr
     return int(_lib.lib().frieda_workspace_bytes(length, log_blowup_factor, log_last_layer_degree_bound, int(bool(prove))))
 
 
+def seeds_workspace_bytes(length, pcs_config, n_seeds):
+    """Workspace a prove_seeds call of n_seeds seeds asks of its context, the Encoded excluded (frieda_seeds_workspace_bytes); 0: refused shape."""
+    return int(_lib.lib().frieda_seeds_workspace_bytes(length, pcs_config._c(), n_seeds))
+
+
 def batch_plan(length, count, pcs_config=None, in_flight=2, prove=True, ctx=None, log_blowup_factor=None):
     """The library's batch policy (frieda_batch_plan, include/frieda_hip.h "batch policy"): the blob count of each call, in order, for
     `count` equal-length blobs and `in_flight` contexts taking turns.  pcs_config for proofs, log_blowup_factor for commits."""
@@ -688,6 +782,11 @@ def generate_proof(data, seed, pcs_config):
 def commit_and_generate_proof(data, seed, pcs_config):
     """proof::commit_and_generate_proof (src/proof.rs:32)."""
     return default_context().commit_and_generate_proof(data, seed, pcs_config)
+
+
+def commit_and_generate_proofs_for_seeds(data, seeds, pcs_config):
+    """One blob, many seeds: (commitment, [Proof]) with proof i == commit_and_generate_proof(data, seeds[i], pcs_config)[1]."""
+    return default_context().commit_and_generate_proofs_for_seeds(data, seeds, pcs_config)
 
 
 def verify(proof, seed):

@@ -424,6 +424,93 @@ int frieda_commit_and_generate_proof_batch_device(frieda_ctx* ctx, const void* d
     return rc != FRIEDA_OK ? rc : batch_finish(ctx, count, out_commitments, out_proofs);
 }
 
+// ---- one blob under many seeds ----
+namespace {
+int encode_common(frieda_ctx* ctx, const void* data, size_t len, bool on_device, uint32_t log_blowup_factor, frieda_encoded** out) {
+    if (!ctx || !out || (!data && len)) return FRIEDA_ERR_ARG;
+    *out = nullptr;
+    FR_GUARD_BEGIN
+    Encoded* e = nullptr;
+    int rc = encode_blob(&ctx->c, static_cast<const uint8_t*>(data), len, on_device, log_blowup_factor, &e);
+    if (rc != FRIEDA_OK) return rc;
+    frieda_encoded* h = new (std::nothrow) frieda_encoded();
+    if (!h) {
+        encoded_free(e);
+        return FRIEDA_ERR_NOMEM;
+    }
+    h->e = *e;      // the handle owns the allocation from here on
+    e->d = nullptr;
+    encoded_free(e);
+    *out = h;
+    return FRIEDA_OK;
+    FR_GUARD_END(ctx)
+}
+}  // namespace
+
+int frieda_encode(frieda_ctx* ctx, const uint8_t* data, size_t len, uint32_t log_blowup_factor, frieda_encoded** out) {
+    return encode_common(ctx, data, len, false, log_blowup_factor, out);
+}
+int frieda_encode_device(frieda_ctx* ctx, const void* d_data, size_t len, uint32_t log_blowup_factor, frieda_encoded** out) {
+    return encode_common(ctx, d_data, len, true, log_blowup_factor, out);
+}
+int frieda_encoded_commitment(const frieda_encoded* enc, uint8_t out_root[32]) {
+    if (!enc || !out_root) return FRIEDA_ERR_ARG;
+    memcpy(out_root, enc->e.root, 32);
+    return FRIEDA_OK;
+}
+size_t frieda_encoded_bytes(const frieda_encoded* enc) { return enc ? enc->e.bytes : 0; }
+void frieda_encoded_free(frieda_encoded* enc) {
+    if (!enc) return;
+    encoded_release(enc->e);
+    delete enc;
+}
+
+int frieda_prove_seeds_begin(frieda_ctx* ctx, const frieda_encoded* enc, const uint64_t* seeds, uint32_t n_seeds, frieda_pcs_config cfg) {
+    if (!ctx) return FRIEDA_ERR_ARG;
+    FR_GUARD_BEGIN
+    return prove_seeds_begin(&ctx->c, enc ? &enc->e : nullptr, seeds, n_seeds, cfg);
+    FR_GUARD_END(ctx)
+}
+int frieda_prove_seeds_finish(frieda_ctx* ctx, frieda_proof** out_proofs) {
+    if (!ctx || !out_proofs) return FRIEDA_ERR_ARG;
+    const uint32_t count = job_count(&ctx->c);
+    if (!count) return ctx->c.fail(FRIEDA_ERR_ARG, "no proof in flight on this context");
+    std::vector<uint8_t> roots;
+    try {
+        roots.resize(32 * (size_t)count);
+    } catch (const std::bad_alloc&) {
+        return FRIEDA_ERR_NOMEM;
+    }
+    return batch_finish(ctx, count, roots.data(), out_proofs);
+}
+int frieda_prove_seeds(frieda_ctx* ctx, const frieda_encoded* enc, const uint64_t* seeds, uint32_t n_seeds, frieda_pcs_config cfg,
+                       frieda_proof** out_proofs) {
+    if (!out_proofs) return FRIEDA_ERR_ARG;
+    int rc = frieda_prove_seeds_begin(ctx, enc, seeds, n_seeds, cfg);
+    return rc != FRIEDA_OK ? rc : frieda_prove_seeds_finish(ctx, out_proofs);
+}
+int frieda_commit_and_generate_proofs_for_seeds(frieda_ctx* ctx, const uint8_t* data, size_t len, const uint64_t* seeds, uint32_t n_seeds,
+                                                frieda_pcs_config cfg, uint8_t out_commitment[32], frieda_proof** out_proofs) {
+    if (!ctx || !out_proofs) return FRIEDA_ERR_ARG;
+    // the argument rules first: nothing is encoded for a call that would be refused
+    if (!seeds) return ctx->c.fail(FRIEDA_ERR_ARG, "null seeds");
+    if (n_seeds == 0 || n_seeds > 65535) return ctx->c.fail(FRIEDA_ERR_ARG, "n_seeds out of range");
+    frieda_encoded* enc = nullptr;
+    int rc = frieda_encode(ctx, data, len, cfg.log_blowup_factor, &enc);
+    if (rc != FRIEDA_OK) return rc;
+    if (out_commitment) memcpy(out_commitment, enc->e.root, 32);
+    rc = frieda_prove_seeds(ctx, enc, seeds, n_seeds, cfg, out_proofs);
+    frieda_encoded_free(enc);
+    return rc;
+}
+size_t frieda_seeds_workspace_bytes(size_t len, frieda_pcs_config cfg, uint32_t n_seeds) {
+    try {
+        return seeds_workspace_bytes(len, cfg, n_seeds);
+    } catch (...) {
+        return 0;
+    }
+}
+
 int frieda_commit_batch(frieda_ctx* ctx, const uint8_t* data, size_t stride, size_t len, uint32_t count, uint32_t log_blowup_factor,
                         uint8_t* out_roots) {
     if (!ctx || !out_roots || (!data && len) || count == 0) return FRIEDA_ERR_ARG;

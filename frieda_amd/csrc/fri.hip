@@ -83,13 +83,19 @@ __global__ __launch_bounds__(FR_THREADS) void gather_kernel(const uint32_t* __re
                                                             const uint64_t* __restrict__ word_idx, size_t n_words,
                                                             uint32_t* __restrict__ out_words,
                                                             const uint64_t* __restrict__ hash_idx, size_t n_hashes,
-                                                            uint8_t* __restrict__ out_hashes) {
+                                                            uint8_t* __restrict__ out_hashes, const uint32_t* __restrict__ alt_words,
+                                                            const uint8_t* __restrict__ alt_hashes) {
     size_t t = (size_t)blockIdx.x * FR_THREADS + threadIdx.x;
-    if (t < n_words) out_words[t] = base[word_idx[t]];
+    if (t < n_words) {
+        const uint64_t ix = word_idx[t];
+        out_words[t] = (ix & GATHER_ALT) ? alt_words[ix & ~GATHER_ALT] : base[ix];
+    }
     // one thread per 16-byte half of a hash
     if (t < 2 * n_hashes) {
         size_t hsh = t >> 1, part = t & 1;
-        const uint4* srcp = reinterpret_cast<const uint4*>(reinterpret_cast<const uint8_t*>(base) + 32 * hash_idx[hsh]);
+        const uint64_t ix = hash_idx[hsh];
+        const uint8_t* hb = (ix & GATHER_ALT) ? alt_hashes : reinterpret_cast<const uint8_t*>(base);
+        const uint4* srcp = reinterpret_cast<const uint4*>(hb + 32 * (ix & ~GATHER_ALT));
         reinterpret_cast<uint4*>(out_hashes)[2 * hsh + part] = srcp[part];
     }
 }
@@ -150,14 +156,14 @@ void fold_line(const Launch& L, const uint32_t* d_src, size_t src_stride, uint32
 }
 
 void gather(const Launch& L, const uint32_t* d_base, const uint64_t* d_word_idx, size_t n_words, uint32_t* d_out_words,
-            const uint64_t* d_hash_idx, size_t n_hashes, uint8_t* d_out_hashes) {
+            const uint64_t* d_hash_idx, size_t n_hashes, uint8_t* d_out_hashes, const uint32_t* d_alt_words, const uint8_t* d_alt_hashes) {
     size_t threads = n_words > 2 * n_hashes ? n_words : 2 * n_hashes;
     if (threads == 0) return;
     hipStream_t s = L.stream;
     Scope scope(L, "gather", 16.0 * (double)n_words + 72.0 * (double)n_hashes);
     gather_kernel<<<(unsigned)((threads + FR_THREADS - 1) / FR_THREADS), FR_THREADS, 0, s>>>(d_base, d_word_idx, n_words,
                                                                                            d_out_words, d_hash_idx, n_hashes,
-                                                                                           d_out_hashes);
+                                                                                           d_out_hashes, d_alt_words, d_alt_hashes);
 }
 
 void grind_scan(const Launch& L, const uint32_t digest[8], uint32_t pow_bits, uint64_t base, uint64_t count,

@@ -164,6 +164,34 @@ int prove_begin_batch(Ctx* ctx, const uint8_t* data, size_t data_stride, size_t 
 int prove_begin_batch_ptrs(Ctx* ctx, const uint8_t* const* blobs, size_t len, uint32_t count, const uint64_t* seeds, frieda_pcs_config cfg);
 int prove_finish_batch(Ctx* ctx, uint8_t* out_commitments, std::vector<ProofData>& outs);
 uint32_t job_count(const Ctx* ctx);  // blobs of the job in flight (0: none)
+
+// ---- one blob proved under many seeds (a provider serving sampling clients: every sample is a proof of the same blob) ----
+// The seed enters the channel before the first root, so unpack + encode + the first-layer tree do not depend on it: an Encoded keeps
+// them on the device — one allocation of its own (not the context's arena: it survives other calls and release_workspace) holding the
+// 4 evaluation columns, the first-layer tree (leaves-first layout, leaf hashes unwritten, large trees without the two levels above
+// the leaves: `skip_log` is the threshold the tree was BUILT with) and the root.  Proving only reads it.
+struct Encoded {
+    int device = 0;
+    size_t len = 0;
+    uint32_t log_blowup = 0, n = 0, L = 0;
+    uint32_t skip_log = 0;
+    uint8_t* d = nullptr;  // [evaluation: 4 x 2^n words][tree: merkle_layer_offset(n, 0) + 32 bytes][root: 32 bytes], each from a 256-byte boundary
+    size_t bytes = 0, o_tree = 0, o_root = 0;
+    uint8_t root[32] = {0};
+    const uint32_t* eval() const { return reinterpret_cast<const uint32_t*>(d); }
+    const uint8_t* tree() const { return d + o_tree; }
+};
+size_t encoded_bytes(uint32_t n, size_t* o_tree = nullptr, size_t* o_root = nullptr);  // the size of that allocation for a 2^n domain
+// synchronous (the root comes back); the context's arena holds the blob and the coefficients meanwhile
+int encode_blob(Ctx* ctx, const uint8_t* data, size_t len, bool data_on_device, uint32_t log_blowup, Encoded** out);
+void encoded_release(Encoded& e);  // frees the device allocation
+void encoded_free(Encoded* e);     // release + delete
+// n_seeds proofs of enc's blob, proof i under seeds[i]: the batch machinery with the first layer at stride 0 (the per-seed workspace
+// holds the inner layers, the last layer and the nonce only).  n_seeds > 1 needs the device channel, as every batch does.  Finished by
+// prove_finish_batch (the commitments it writes are n_seeds copies of enc's root).
+int prove_seeds_begin(Ctx* ctx, const Encoded* enc, const uint64_t* seeds, uint32_t n_seeds, frieda_pcs_config cfg);
+// arena bytes prove_seeds_begin asks for (the Encoded excluded); 0: a shape the prover refuses
+size_t seeds_workspace_bytes(size_t len, frieda_pcs_config cfg, uint32_t n_seeds);
 int commit_batch(Ctx* ctx, const uint8_t* data, size_t data_stride, size_t len, uint32_t count, bool data_on_device, uint32_t log_blowup,
                  uint8_t* out_roots, const uint8_t* const* host_ptrs = nullptr);
 // split form (frieda_commit_many alternates two contexts: the upload of one unit runs under the kernels of the other): _begin
@@ -234,6 +262,9 @@ struct frieda_ctx {
         if (ctxptr) (ctxptr)->c.err = e.what();                       \
         return FRIEDA_ERR_INVARIANT;                                  \
     }
+struct frieda_encoded {
+    frieda::Encoded e;
+};
 struct frieda_proof {
     frieda::ProofData p;
     std::shared_ptr<ProofPool> home;  // set while the object is out with the caller; null inside the pool and for clones / parsed proofs

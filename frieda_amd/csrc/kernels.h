@@ -58,6 +58,9 @@ struct Tuning {
                                          // in the decommitment whatever the size; a batch shares it, a lone proof pays it: worth it from 2^23 on)
     uint32_t tp_min_wgs = 768;           // FRIEDA_TP_MIN_WGS: launches of at least this many 256-thread workgroups hash in the throughput form (blake2s.h)
     uint32_t grind_iters = 0;            // FRIEDA_GRIND_ITERS: nonces per lane and claim in the batched grind (window = 256 x this); 0 = by batch size
+    uint32_t seeds_fold_group = 0;       // FRIEDA_SEEDS_FOLD_GROUP: proofs of one encoded blob under many seeds (prove_seeds): seeds per workgroup of the
+                                         // seed-looped first fold (route B: the evaluation is read once per group); 0 = route A, the batch kernels
+                                         // with every seed re-reading the shared evaluation (measured: profiles/r08_prove_seeds.txt)
     uint32_t batch_calls_per_ctx = 1;    // FRIEDA_BATCH_CALLS_PER_CTX: a stream is cut into at least this many calls per context in flight
                                          // (measured, profiles/r05_batch_policy_sweep.txt: 1 beats 2 by 3 % at 2^20 and 30 % at 1 KiB blobs, equal at 2^22 / 2^24)
     // facts about the context's device, recorded at creation (not knobs: tuning_set does not reach them)
@@ -292,13 +295,20 @@ void encode_and_first_tree(const Launch& L, const uint32_t* d_coef, size_t coef_
                            DevTranscript* tr, const DevTranscript* tr_init = nullptr, size_t tr_init_pitch = 0);
 // fold the layer `src` (log size src_log; circle evaluation or line layer) with the alpha in tr into dst_vals and build the
 // tree of the folded layer in the same launches (leaf hashes not written, as above); finishes with the channel step
+// shared_src (prove_seeds: the blobs of the launch are the seeds of ONE encoded blob): `src` is the same for every blob (stride 0) while
+// dst_vals, d_layers and tr keep the batch stride; seeds_group > 0 with a circle source: the seed-looped kernel (one workgroup folds and
+// hashes for `seeds_group` consecutive seeds from one read of the source) where the launch has the register-subtree shape
 void fold_and_tree(const Launch& L, bool circle, const uint32_t* src, size_t src_stride, uint32_t src_log, uint32_t n,
-                   const uint32_t* d_itw, DomainScalars ds, uint32_t* dst_vals, uint8_t* d_layers, DevTranscript* tr);
+                   const uint32_t* d_itw, DomainScalars ds, uint32_t* dst_vals, uint8_t* d_layers, DevTranscript* tr, bool shared_src = false,
+                   uint32_t seeds_group = 0);
+// prove_seeds: the first root exists already (d_root, 8 words, shared by the blobs of the launch): initialise every blob's device transcript
+// from tr_init (pinned host memory, blob b at tr_init + b * tr_init_pitch bytes), mix the root and draw the first alpha
+void channel_after_shared_root(const Launch& L, const uint8_t* d_root, DevTranscript* tr, const DevTranscript* tr_init, size_t tr_init_pitch);
 // all remaining layers (each <= 2048 points) in one workgroup, ending with the last-layer interpolation + mix_felts
 constexpr uint32_t TAIL_LOG = 11;
 void fri_tail(const Launch& L, const uint32_t* src, size_t src_stride, uint32_t src_log, bool src_is_circle, uint32_t n,
               const uint32_t* d_itw, DomainScalars ds, uint32_t last_log, uint32_t last, uint32_t n_layers, uint32_t* const* vals,
-              uint8_t* const* trees, DevTranscript* tr, uint32_t* d_gnext = nullptr);
+              uint8_t* const* trees, DevTranscript* tr, uint32_t* d_gnext = nullptr, bool shared_src = false);
 // proof-of-work scan keyed by tr->ch.digest; atomicMin into tr->nonce
 // d_next: L.batch * GRIND_NEXT_STRIDE words of scratch (the per-blob window counters, one 128-byte line each: 2048 workgroups claim
 // windows with atomics, and counters sharing a line serialise in one L2 channel; zeroed here unless next_zeroed: fri_tail did it)
@@ -327,6 +337,9 @@ struct DecommitArgs {
     const uint32_t* vals[DECOMMIT_MAX_LAYERS];  // blob 0's layers: 4 columns of 2^(n - li) words, column stride 2^(n - li)
     const uint8_t* trees[DECOMMIT_MAX_LAYERS];  // their trees (leaves-first layout)
     uint32_t skip_log;  // trees of >= 2^skip_log leaves: the two levels above the leaves are re-hashed from vals, not read (Tuning::tree_skip_log)
+    // prove_seeds: layer 0 (vals[0], trees[0]) belongs to the encoded blob every seed shares — no batch stride, and the threshold its
+    // tree was built with.  Everywhere else first_shared = 0 and skip_log0 = skip_log.
+    uint32_t first_shared, skip_log0;
 };
 void decommit(const Launch& L, const DecommitArgs& a, uint32_t wgs_per_blob);
 
@@ -382,8 +395,11 @@ void fold_circle_into_line(const Launch& L, uint32_t* d_dst, size_t dst_stride, 
 void fold_line(const Launch& L, const uint32_t* d_src, size_t src_stride, uint32_t m, uint32_t n, const uint32_t* d_itw,
                DomainScalars ds, Alpha alpha, uint32_t* d_dst, size_t dst_stride);
 // out_words[i] = base_words[word_idx[i]];  out_hashes[i] = 32 bytes at base + 32 * hash_idx[i]
+// an index with GATHER_ALT set is relative to d_alt_words / d_alt_hashes instead (prove_seeds: the encoded blob's evaluation and tree)
+constexpr uint64_t GATHER_ALT = (uint64_t)1 << 63;
 void gather(const Launch& L, const uint32_t* d_base, const uint64_t* d_word_idx, size_t n_words, uint32_t* d_out_words,
-            const uint64_t* d_hash_idx, size_t n_hashes, uint8_t* d_out_hashes);
+            const uint64_t* d_hash_idx, size_t n_hashes, uint8_t* d_out_hashes, const uint32_t* d_alt_words = nullptr,
+            const uint8_t* d_alt_hashes = nullptr);
 // scans nonces [base, base + count) for trailing_zeros(compress(digest, nonce)) >= pow_bits; atomicMin into *d_result
 void grind_scan(const Launch& L, const uint32_t digest[8], uint32_t pow_bits, uint64_t base, uint64_t count,
                 unsigned long long* d_result);

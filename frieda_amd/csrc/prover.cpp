@@ -280,7 +280,8 @@ struct GatherPlan {
 };
 
 // compute_decommitment_positions_and_witness_evals (fold_step = 1): positions + requests for the witness values
-std::vector<uint32_t> plan_witness(const std::vector<uint32_t>& queries, const FriLayerDev& lay, GatherPlan& g, size_t& n_witness) {
+// `tag` (0 or k::GATHER_ALT) is set on every index pushed: the layer lives in an encoded blob, not in the arena (prove_seeds)
+std::vector<uint32_t> plan_witness(const std::vector<uint32_t>& queries, const FriLayerDev& lay, GatherPlan& g, size_t& n_witness, uint64_t tag = 0) {
     std::vector<uint32_t> pos;
     n_witness = 0;
     const size_t stride = (size_t)1 << lay.log;
@@ -295,7 +296,7 @@ std::vector<uint32_t> plan_witness(const std::vector<uint32_t>& queries, const F
                 kq++;
                 continue;
             }
-            for (int c = 0; c < 4; c++) g.word_idx.push_back(lay.o_vals / 4 + (size_t)c * stride + p);
+            for (int c = 0; c < 4; c++) g.word_idx.push_back((lay.o_vals / 4 + (size_t)c * stride + p) | tag);
             n_witness++;
         }
         i = j;
@@ -307,7 +308,7 @@ std::vector<uint32_t> plan_witness(const std::vector<uint32_t>& queries, const F
 // stwo walks the layers from the leaves up; on layer l it visits, in increasing order, every node that has a queried leaf or a
 // visited child below it, and emits the hash of each child that was not visited itself (left before right).  `positions` are
 // the queried leaves (sorted, unique).  Two scratch vectors are reused across calls (this runs ~25 times per proof).
-size_t plan_merkle_decommit(const std::vector<uint32_t>& positions, const FriLayerDev& lay, GatherPlan& g) {
+size_t plan_merkle_decommit(const std::vector<uint32_t>& positions, const FriLayerDev& lay, GatherPlan& g, uint64_t tag = 0) {
     static thread_local std::vector<uint32_t> buf_a, buf_b;
     std::vector<uint32_t>* below = &buf_a;  // visited nodes of the layer below (children), sorted
     std::vector<uint32_t>* here = &buf_b;
@@ -325,11 +326,11 @@ size_t plan_merkle_decommit(const std::vector<uint32_t>& positions, const FriLay
             const bool has_right = i < nc && c[i] == 2 * node + 1;
             if (has_right) i++;
             if (!has_left) {
-                g.hash_idx.push_back(child_base + 2 * (size_t)node);
+                g.hash_idx.push_back((child_base + 2 * (size_t)node) | tag);
                 n_hashes++;
             }
             if (!has_right) {
-                g.hash_idx.push_back(child_base + 2 * (size_t)node + 1);
+                g.hash_idx.push_back((child_base + 2 * (size_t)node + 1) | tag);
                 n_hashes++;
             }
             here->push_back(node);
@@ -363,6 +364,10 @@ struct ProveJob {
     // the tree-skip threshold the trees of THIS job were built with (k::tree_skip_threshold at begin): the openings — device kernel
     // and host-planner fallback — must use the same one even if frieda_ctx_set_option moved the knob between _begin and _finish
     uint32_t skip_log = 0;
+    // prove_seeds: the `count` blobs are seeds of ONE encoded blob.  Layer 0 (values, tree) is enc's, at stride 0, with the threshold
+    // ITS tree was built with; `first` then holds no arena offsets and the per-seed workspace starts at the first inner layer
+    const Encoded* enc = nullptr;
+    uint32_t first_skip_log = 0;
     struct Blob {
         Channel ch{};
         std::vector<Hash32> roots;
@@ -380,13 +385,19 @@ void ProveJobDeleter::operator()(ProveJob* j) const { delete j; }
 
 namespace {
 // the per-blob part of a proof's workspace (one plan for the prover and for the batch policy, which divides its budget by plan.off)
+// shared_first (prove_seeds): blob, coefficients, evaluation and first tree live in the encoded blob — the per-seed part begins at the inner layers
 void plan_prove_blob(ArenaPlan& plan, const Shape& sh, uint32_t last_log, size_t host_len, size_t& o_data, size_t& o_coef, FriLayerDev& first,
-                     std::vector<FriLayerDev>& inner, size_t& o_lastv, size_t& o_nonce) {
+                     std::vector<FriLayerDev>& inner, size_t& o_lastv, size_t& o_nonce, bool shared_first = false) {
     const uint32_t n = sh.n, n_inner = (n - 1) - last_log;
-    o_data = plan.take(host_len);
-    o_coef = plan.take(sizeof(uint32_t) * sh.cs.n_padded);
-    first = FriLayerDev{plan.take(sizeof(uint32_t) * 4 * sh.N), 0, n};
-    first.o_tree = plan.take(k::merkle_layer_offset(n, 0) + 32);
+    if (shared_first) {
+        o_data = o_coef = 0;
+        first = FriLayerDev{0, 0, n};
+    } else {
+        o_data = plan.take(host_len);
+        o_coef = plan.take(sizeof(uint32_t) * sh.cs.n_padded);
+        first = FriLayerDev{plan.take(sizeof(uint32_t) * 4 * sh.N), 0, n};
+        first.o_tree = plan.take(k::merkle_layer_offset(n, 0) + 32);
+    }
     inner.resize(n_inner);
     for (uint32_t kx = 0; kx < n_inner; kx++) {
         uint32_t lg = n - 1 - kx;
@@ -398,6 +409,18 @@ void plan_prove_blob(ArenaPlan& plan, const Shape& sh, uint32_t last_log, size_t
     o_nonce = plan.take(8);
 }
 }  // namespace
+
+// Capacity of a job's opening lists.  Words: per layer <= 2 positions per query (+ the evaluations).  Hashes: a batch keeps its
+// long-standing loose bound, 2 * queries * (n + 1) per layer; a prove_seeds job — whose point is memory per seed — the exact one: in a
+// tree of 2^m leaves opened at pairs, every level below the root has at most `queries` visited nodes and each emits at most one sibling,
+// the leaf level none: queries * (m - 1) <= queries * (n - li) for layer li.
+size_t opening_max_words(uint32_t n_queries, uint32_t n_inner) { return (size_t)n_queries * 4 * (1 + (n_inner + 1)); }
+size_t opening_max_hashes(uint32_t n_queries, uint32_t n, uint32_t n_inner, bool seeds) {
+    if (!seeds) return (size_t)n_queries * 2 * (size_t)(n + 1) * (n_inner + 1);
+    size_t h = 0;
+    for (uint32_t li = 0; li <= n_inner; li++) h += (size_t)n_queries * (n - li);
+    return h;
+}
 
 // Device workspace one blob of `len` bytes adds to a batched call (what ensure_arena is asked for, per blob): the figure the batch
 // policy (batch_plan below) divides its budget by.  0: the shape is outside what the prover accepts.
@@ -506,8 +529,10 @@ static void launch_decommit(Ctx* ctx, const ProveJob& J, const k::Launch& LN) {
     a.max_words = J.dec_max_words;
     a.max_hashes = J.dec_max_hashes;
     a.skip_log = J.skip_log;
-    a.vals[0] = reinterpret_cast<const uint32_t*>(A + J.first.o_vals);
-    a.trees[0] = A + J.first.o_tree;
+    a.skip_log0 = J.first_skip_log;
+    a.first_shared = J.enc ? 1 : 0;
+    a.vals[0] = J.enc ? J.enc->eval() : reinterpret_cast<const uint32_t*>(A + J.first.o_vals);
+    a.trees[0] = J.enc ? J.enc->tree() : A + J.first.o_tree;
     for (uint32_t kx = 0; kx < J.n_inner; kx++) {
         a.vals[1 + kx] = reinterpret_cast<const uint32_t*>(A + J.inner[kx].o_vals);
         a.trees[1 + kx] = A + J.inner[kx].o_tree;
@@ -528,12 +553,30 @@ int prove_begin_batch_ptrs(Ctx* ctx, const uint8_t* const* blobs, size_t len, ui
 }
 
 // `count` blobs of `len` bytes each, blob b at data + b * data_stride (or, host blobs only, at host_ptrs[b]); seeds: null or one per blob
+static int prove_begin_impl(Ctx* ctx, const uint8_t* data, size_t data_stride, size_t len, uint32_t count, bool data_on_device,
+                            const uint64_t* seeds, frieda_pcs_config cfg, const uint8_t* const* host_ptrs, const Encoded* enc);
+
 int prove_begin_batch(Ctx* ctx, const uint8_t* data, size_t data_stride, size_t len, uint32_t count, bool data_on_device,
                       const uint64_t* seeds, frieda_pcs_config cfg, const uint8_t* const* host_ptrs) {
+    return prove_begin_impl(ctx, data, data_stride, len, count, data_on_device, seeds, cfg, host_ptrs, nullptr);
+}
+
+int prove_seeds_begin(Ctx* ctx, const Encoded* enc, const uint64_t* seeds, uint32_t n_seeds, frieda_pcs_config cfg) {
+    if (!enc || !enc->d) return ctx->fail(FRIEDA_ERR_ARG, "null encoded blob");
+    if (!seeds) return ctx->fail(FRIEDA_ERR_ARG, "null seeds");
+    if (n_seeds == 0 || n_seeds > 65535) return ctx->fail(FRIEDA_ERR_ARG, "n_seeds out of range");
+    if (cfg.log_blowup_factor != enc->log_blowup) return ctx->fail(FRIEDA_ERR_ARG, "log_blowup_factor differs from the one the blob was encoded with");
+    if (enc->device != ctx->device) return ctx->fail(FRIEDA_ERR_ARG, "the encoded blob lives on another device");
+    return prove_begin_impl(ctx, nullptr, 0, enc->len, n_seeds, true, seeds, cfg, nullptr, enc);
+}
+
+// enc non-null: prove_seeds — `count` seeds of one encoded blob (data unused; seeds non-null)
+static int prove_begin_impl(Ctx* ctx, const uint8_t* data, size_t data_stride, size_t len, uint32_t count, bool data_on_device,
+                            const uint64_t* seeds, frieda_pcs_config cfg, const uint8_t* const* host_ptrs, const Encoded* enc) {
     const auto t_entry = std::chrono::steady_clock::now();
     FR_NO_JOB(ctx);  // a proof or a commit batch in flight owns the arena and the pinned block
     if (count == 0 || count > 65535) return ctx->fail(FRIEDA_ERR_ARG, "batch count out of range");
-    if (count > 1 && data_stride < len) return ctx->fail(FRIEDA_ERR_ARG, "batch stride smaller than the blob length");
+    if (!enc && count > 1 && data_stride < len) return ctx->fail(FRIEDA_ERR_ARG, "batch stride smaller than the blob length");
     const uint32_t B = cfg.log_blowup_factor, last = cfg.log_last_layer_degree_bound;
     // both arrive unchecked: bound them before `last + B` and the shifts that use it are formed
     if (last > 10) return ctx->fail(FRIEDA_ERR_ARG, "log_last_layer_degree_bound > 10");
@@ -553,6 +596,8 @@ int prove_begin_batch(Ctx* ctx, const uint8_t* data, size_t data_stride, size_t 
     J.last = last;
     J.count = count;
     J.skip_log = k::tree_skip_threshold(ctx->tuning, count);
+    J.enc = enc;
+    J.first_skip_log = enc ? enc->skip_log : J.skip_log;
     J.blobs.resize(count);
     const uint32_t n = J.n = sh.n, last_log = J.last_log = last + B;
     const size_t N = J.N = sh.N;
@@ -563,7 +608,7 @@ int prove_begin_batch(Ctx* ctx, const uint8_t* data, size_t data_stride, size_t 
     size_t o_data = 0, o_coef = 0;
     FriLayerDev& first = J.first;
     std::vector<FriLayerDev>& inner = J.inner;
-    plan_prove_blob(plan, sh, last_log, data_on_device ? 0 : len, o_data, o_coef, first, inner, J.o_lastv, J.o_nonce);
+    plan_prove_blob(plan, sh, last_log, data_on_device ? 0 : len, o_data, o_coef, first, inner, J.o_lastv, J.o_nonce, enc != nullptr);
     const size_t o_lastv = J.o_lastv, o_nonce = J.o_nonce;
     // everything above is per blob; what follows is shared by the batch
     const size_t bstride = J.bstride = plan.off;  // a multiple of 256
@@ -571,8 +616,8 @@ int prove_begin_batch(Ctx* ctx, const uint8_t* data, size_t data_stride, size_t 
     const size_t o_tr = J.o_tr = plan.take(sizeof(DevTranscript) * count);
     J.o_gnext = plan.take(sizeof(uint32_t) * k::GRIND_NEXT_STRIDE * count);  // grind window counters, one cache line per blob
     // decommit gather: per layer <= 2 positions per query; hashes <= 2 * queries * log per layer
-    J.max_words = (size_t)cfg.n_queries * 4 * (1 + (n_inner + 1)) * count;
-    J.max_hashes = (size_t)cfg.n_queries * 2 * (size_t)(n + 1) * (n_inner + 1) * count;
+    J.max_words = opening_max_words(cfg.n_queries, n_inner) * count;
+    J.max_hashes = opening_max_hashes(cfg.n_queries, n, n_inner, enc != nullptr) * count;
     J.o_widx = plan.take(8 * J.max_words);
     J.o_hidx = plan.take(8 * J.max_hashes);
     J.o_wout = plan.take(4 * J.max_words);
@@ -615,7 +660,7 @@ int prove_begin_batch(Ctx* ctx, const uint8_t* data, size_t data_stride, size_t 
     const uint8_t* d_data = data;
     size_t d_data_stride = data_stride;
     const bool small = k::small_domain_shape(ctx->tuning, sh.L, n) && !ctx->host_channel && last_log <= k::TAIL_LOG;
-    if (!data_on_device) {
+    if (!data_on_device && !enc) {
         if (small && count == 1 && len <= SMALL_HOST_IN_BYTES) {
             // a lone small blob is not copied to the device: the first kernel reads it from page-locked host memory
             rc = ensure_pinned_in(ctx);
@@ -636,8 +681,9 @@ int prove_begin_batch(Ctx* ctx, const uint8_t* data, size_t data_stride, size_t 
         }
     }
     uint32_t* coef = reinterpret_cast<uint32_t*>(A + o_coef);
-    uint32_t* eval = reinterpret_cast<uint32_t*>(A + first.o_vals);
-    if (!small) k::unpack30(LN, d_data, len, coef, sh.cs.n_padded, d_data_stride);
+    // the first layer's columns: in the workspace, or (prove_seeds) the encoded blob's, only ever read
+    uint32_t* eval = enc ? const_cast<uint32_t*>(enc->eval()) : reinterpret_cast<uint32_t*>(A + first.o_vals);
+    if (!small && !enc) k::unpack30(LN, d_data, len, coef, sh.cs.n_padded, d_data_stride);
     ctx->phase_ms[5] = ms_since(t_entry);  // set-up before the first launch (workspace plan, twiddle lookup, ...) + that launch call
 
     for (uint32_t b = 0; b < count; b++) {
@@ -646,10 +692,9 @@ int prove_begin_batch(Ctx* ctx, const uint8_t* data, size_t data_stride, size_t 
         J.blobs[b].roots.assign(1 + n_inner, Hash32{});
     }
     Channel& ch = J.blobs[0].ch;  // (the host-channel path below is single-blob)
-    const uint64_t* seed = seeds;
-    (void)seed;
 
-    auto cols = [&](const FriLayerDev& lay, int c) { return reinterpret_cast<uint32_t*>(A + lay.o_vals) + ((size_t)c << lay.log); };
+    auto cols = [&](const FriLayerDev& lay, int c) { return (&lay == &first ? eval : reinterpret_cast<uint32_t*>(A + lay.o_vals)) + ((size_t)c << lay.log); };
+    const uint32_t seeds_group = enc ? ctx->tuning.seeds_fold_group : 0;
     std::vector<Hash32>& roots = J.blobs[0].roots;
     std::vector<QM31>& lastv = J.blobs[0].lastv;
     if (dev_channel) {
@@ -669,7 +714,9 @@ int prove_begin_batch(Ctx* ctx, const uint8_t* data, size_t data_stride, size_t 
         }
         // the encode's last pass runs fused with FriProver::commit_first_layer's leaf hashing (src/proof.rs:48-52); small domains: unpack +
         // encode + first tree in one launch, straight from the blob
-        if (small)
+        if (enc)  // the first tree and its root exist: only the transcripts' step behind that root — mix_root, first alpha — per seed
+            k::channel_after_shared_root(LN, enc->d + enc->o_root, d_tr, reinterpret_cast<const DevTranscript*>(ctx->pinned), tr_host_pitch);
+        else if (small)
             k::small_encode_and_first_tree(LN, d_data, len, d_data_stride, sh.L, n, tw.d_tw, tw.ds, eval, N, A + first.o_tree, nullptr, nullptr, d_tr,
                                            reinterpret_cast<const DevTranscript*>(ctx->pinned), tr_host_pitch);
         else
@@ -684,7 +731,7 @@ int prove_begin_batch(Ctx* ctx, const uint8_t* data, size_t data_stride, size_t 
         const uint32_t tail_run_log = ctx->tuning.tail_run_log;
         while (kx < n_inner && inner[kx].log > tail_run_log) {
             k::fold_and_tree(LN, circle, cols(*cur, 0), (size_t)1 << cur->log, cur->log, n, tw.d_itw, tw.ds, cols(inner[kx], 0),
-                             A + inner[kx].o_tree, d_tr);
+                             A + inner[kx].o_tree, d_tr, enc && circle, circle ? seeds_group : 0);
             cur = &inner[kx];
             circle = false;
             kx++;
@@ -702,7 +749,7 @@ int prove_begin_batch(Ctx* ctx, const uint8_t* data, size_t data_stride, size_t 
         ttrees[n_tail - 1] = nullptr;
         uint32_t* d_gnext = reinterpret_cast<uint32_t*>(A + J.o_gnext);
         k::fri_tail(LN, cols(*cur, 0), (size_t)1 << cur->log, cur->log, circle, n, tw.d_itw, tw.ds, last_log, last, n_tail, tvals, ttrees,
-                    d_tr, d_gnext);
+                    d_tr, d_gnext, enc && circle);
         // grind (src/proof.rs:58), keyed by the digest now sitting in the device transcript: first chunk + transcript download
         J.grind_base = 0;
         // first range: 16x the expected search (a miss has probability e^-16; workgroups without work leave at once)
@@ -726,10 +773,14 @@ int prove_begin_batch(Ctx* ctx, const uint8_t* data, size_t data_stride, size_t 
         };
 
         // ---- FriProver::commit_first_layer ----
-        k::circle_evaluate(LN, coef, (size_t)1 << sh.L, 4, sh.L, n, tw.d_tw, tw.ds, eval, N);
-        k::merkle_tree4(LN, cols(first, 0), cols(first, 1), cols(first, 2), cols(first, 3), n, A + first.o_tree);
-        rc = fetch_root(first, roots[0]);
-        if (rc) return rc;
+        if (enc) {
+            memcpy(roots[0].data(), enc->root, 32);  // (prove_seeds, one seed: the commitment was made by encode_blob)
+        } else {
+            k::circle_evaluate(LN, coef, (size_t)1 << sh.L, 4, sh.L, n, tw.d_tw, tw.ds, eval, N);
+            k::merkle_tree4(LN, cols(first, 0), cols(first, 1), cols(first, 2), cols(first, 3), n, A + first.o_tree);
+            rc = fetch_root(first, roots[0]);
+            if (rc) return rc;
+        }
         uint32_t rw[8];
         hash_to_words(roots[0].data(), rw);
         ch.mix_root(rw);
@@ -908,6 +959,24 @@ int prove_finish_batch(Ctx* ctx, uint8_t* out_commitments, std::vector<ProofData
     if (!from_device) {
         // The host plans against COMPLETE trees; the large ones were built without the two levels above their leaves (the device
         // decommitment re-hashes those, tree.hip TreeArgs::skip_bc): rebuild such a tree from its layer's values first (a rare path).
+        // prove_seeds: the encoded blob is only ever read (other contexts may be proving from it), so when ITS tree lacks those levels
+        // a complete copy is built in a temporary allocation (a rare path twice over) and layer 0's hashes are gathered from there
+        struct TempTree {
+            uint8_t* d = nullptr;
+            ~TempTree() {
+                if (d) (void)hipFree(d);
+            }
+        } first_full;
+        const uint8_t* first_tree_alt = J.enc ? J.enc->tree() : nullptr;
+        if (J.enc && first.log >= J.first_skip_log) {
+            if (hipMalloc((void**)&first_full.d, k::merkle_layer_offset(n, 0) + 32) != hipSuccess) {
+                (void)hipGetLastError();
+                return ctx->fail(FRIEDA_ERR_NOMEM, "no device memory for the complete first-layer tree of the host decommitment");
+            }
+            const uint32_t* c0 = J.enc->eval();
+            k::merkle_tree4(ctx->launch(), c0, c0 + N, c0 + 2 * N, c0 + 3 * N, n, first_full.d);
+            first_tree_alt = first_full.d;
+        }
         {
             k::Launch Lb = ctx->launch();  // single-blob launches
             for (uint32_t b = 0; b < count; b++) {
@@ -918,7 +987,7 @@ int prove_finish_batch(Ctx* ctx, uint8_t* out_commitments, std::vector<ProofData
                     const size_t cs = (size_t)1 << lay.log;
                     k::merkle_tree4(Lb, c0, c0 + cs, c0 + 2 * cs, c0 + 3 * cs, lay.log, A + lay.o_tree + boff);
                 };
-                rebuild(first);
+                if (!J.enc) rebuild(first);
                 for (uint32_t kx = 0; kx < n_inner; kx++) rebuild(inner[kx]);
             }
         }
@@ -941,12 +1010,14 @@ int prove_finish_batch(Ctx* ctx, uint8_t* out_commitments, std::vector<ProofData
             };
             LayerCounts* cnt = &counts[(size_t)b * (1 + n_inner)];
             // Proof.evaluations (src/proof.rs:62-66)
+            // (prove_seeds: `first` holds offsets 0 — indices relative to the encoded blob's columns / tree, marked GATHER_ALT)
+            const uint64_t tag0 = J.enc ? k::GATHER_ALT : 0;
+            const FriLayerDev lay0 = J.enc ? first : shifted(first);
             for (uint32_t q : queries)
-                for (int c = 0; c < 4; c++) g.word_idx.push_back((first.o_vals + boff) / 4 + (size_t)c * N + q);
+                for (int c = 0; c < 4; c++) g.word_idx.push_back((lay0.o_vals / 4 + (size_t)c * N + q) | tag0);
             {
-                const FriLayerDev lay = shifted(first);
-                std::vector<uint32_t> pos = plan_witness(queries, lay, g, cnt[0].n_witness);
-                cnt[0].n_hashes = plan_merkle_decommit(pos, lay, g);
+                std::vector<uint32_t> pos = plan_witness(queries, lay0, g, cnt[0].n_witness, tag0);
+                cnt[0].n_hashes = plan_merkle_decommit(pos, lay0, g, tag0);
             }
             std::vector<uint32_t> lq = fold_queries(queries, 1);
             for (uint32_t kx = 0; kx < n_inner; kx++) {
@@ -971,11 +1042,13 @@ int prove_finish_batch(Ctx* ctx, uint8_t* out_commitments, std::vector<ProofData
         if (out_bytes <= ((size_t)1 << 20) && !ctx->tuning.gather_copy) {
             // small openings (the usual case): the kernel reads its index lists from, and writes its results to, the pinned
             // staging block directly over PCIe — one launch instead of copy + launch + copy (each copy costs 10-20 us of setup)
-            k::gather(L1, reinterpret_cast<const uint32_t*>(A), hidx, nw, reinterpret_cast<uint32_t*>(hp), hidx + nw, nh, hp + wbytes);
+            k::gather(L1, reinterpret_cast<const uint32_t*>(A), hidx, nw, reinterpret_cast<uint32_t*>(hp), hidx + nw, nh, hp + wbytes,
+                      J.enc ? J.enc->eval() : nullptr, first_tree_alt);
         } else {
             FR_HIP(ctx, hipMemcpyAsync(A + J.o_widx, hidx, 8 * (nw + nh), hipMemcpyHostToDevice, s));
             k::gather(L1, reinterpret_cast<const uint32_t*>(A), reinterpret_cast<const uint64_t*>(A + J.o_widx), nw,
-                      reinterpret_cast<uint32_t*>(A + J.o_wout), reinterpret_cast<const uint64_t*>(A + J.o_widx) + nw, nh, A + J.o_wout + wbytes);
+                      reinterpret_cast<uint32_t*>(A + J.o_wout), reinterpret_cast<const uint64_t*>(A + J.o_widx) + nw, nh, A + J.o_wout + wbytes,
+                      J.enc ? J.enc->eval() : nullptr, first_tree_alt);
             FR_HIP(ctx, hipMemcpyAsync(hp, A + J.o_wout, out_bytes, hipMemcpyDeviceToHost, s));
         }
         FR_HIP(ctx, hipStreamSynchronize(s));
@@ -1029,6 +1102,121 @@ int prove(Ctx* ctx, const uint8_t* data, size_t len, bool data_on_device, const 
     int rc = prove_begin(ctx, data, len, data_on_device, seed, cfg);
     if (rc) return rc;
     return prove_finish(ctx, out_commitment, out);
+}
+
+// -------------------------------------------------------------------------------------------------
+// one blob under many seeds: the encoded blob (host.h)
+// -------------------------------------------------------------------------------------------------
+size_t encoded_bytes(uint32_t n, size_t* o_tree, size_t* o_root) {
+    ArenaPlan plan;
+    plan.take(sizeof(uint32_t) * 4 << n);
+    const size_t ot = plan.take(k::merkle_layer_offset(n, 0) + 32);
+    const size_t orr = plan.take(32);
+    if (o_tree) *o_tree = ot;
+    if (o_root) *o_root = orr;
+    return plan.off;
+}
+
+void encoded_release(Encoded& e) {
+    if (!e.d) return;
+    int cur = 0;
+    const bool sw = hipGetDevice(&cur) == hipSuccess && cur != e.device;
+    if (sw) (void)hipSetDevice(e.device);
+    (void)hipFree(e.d);
+    if (sw) (void)hipSetDevice(cur);
+    e.d = nullptr;
+}
+void encoded_free(Encoded* e) {
+    if (!e) return;
+    encoded_release(*e);
+    delete e;
+}
+
+int encode_blob(Ctx* ctx, const uint8_t* data, size_t len, bool data_on_device, uint32_t log_blowup, Encoded** out) {
+    FR_NO_JOB(ctx);
+    Shape sh;
+    int rc = make_shape(ctx, len, log_blowup, sh);
+    if (rc) return rc;
+    FR_HIP(ctx, hipSetDevice(ctx->device));
+    // the arena holds what encoding needs and the handle does not keep: the blob (a host blob) and the coefficients
+    ArenaPlan plan;
+    const size_t o_data = plan.take(data_on_device ? 0 : len);
+    const size_t o_coef = plan.take(sizeof(uint32_t) * sh.cs.n_padded);
+    rc = ctx->ensure_arena(plan.off);
+    if (rc) return rc;
+    rc = ensure_pinned(ctx, 4096);
+    if (rc) return rc;
+    TwiddleSet tw;
+    rc = ctx->get_twiddles(sh.n, tw);
+    if (rc) return rc;
+    std::unique_ptr<Encoded, void (*)(Encoded*)> e(new Encoded(), encoded_free);
+    e->device = ctx->device;
+    e->len = len;
+    e->log_blowup = log_blowup;
+    e->n = sh.n;
+    e->L = sh.L;
+    // a lone launch builds the tree: the threshold of a call of one blob (what k::build_tree applies to a Launch of batch 1)
+    e->skip_log = k::tree_skip_threshold(ctx->tuning, 1);
+    e->bytes = encoded_bytes(sh.n, &e->o_tree, &e->o_root);
+    if (hipMalloc((void**)&e->d, e->bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        e->d = nullptr;
+        return ctx->fail(FRIEDA_ERR_NOMEM, "hipMalloc(encoded blob " + std::to_string(e->bytes) + " B) failed");
+    }
+    hipStream_t s = ctx->stream;
+    uint8_t* A = ctx->arena;
+    const uint8_t* d_data = data;
+    if (!data_on_device) {
+        if (len) FR_HIP(ctx, hipMemcpyAsync(A + o_data, data, len, hipMemcpyHostToDevice, s));
+        d_data = A + o_data;
+    }
+    const k::Launch LN = ctx->launch();
+    uint32_t* eval = reinterpret_cast<uint32_t*>(e->d);
+    if (k::small_domain_shape(ctx->tuning, sh.L, sh.n)) {
+        k::small_encode_and_first_tree(LN, d_data, len, 0, sh.L, sh.n, tw.d_tw, tw.ds, eval, sh.N, e->d + e->o_tree, nullptr, e->d + e->o_root, nullptr,
+                                       nullptr, 0);
+    } else {
+        uint32_t* coef = reinterpret_cast<uint32_t*>(A + o_coef);
+        k::unpack30(LN, d_data, len, coef, sh.cs.n_padded);
+        k::encode_and_first_tree(LN, coef, (size_t)1 << sh.L, sh.L, sh.n, tw.d_tw, tw.ds, eval, sh.N, e->d + e->o_tree, nullptr, e->d + e->o_root, nullptr);
+    }
+    FR_HIP(ctx, hipMemcpyAsync(ctx->pinned, e->d + e->o_root, 32, hipMemcpyDeviceToHost, s));
+    FR_HIP(ctx, hipStreamSynchronize(s));
+    FR_HIP(ctx, hipGetLastError());
+    memcpy(e->root, ctx->pinned, 32);
+    *out = e.release();
+    return FRIEDA_OK;
+}
+
+// what prove_begin_impl plans for a prove_seeds job: the per-seed part times n_seeds, then the transcripts, the grind counters and the
+// opening lists of the host-planner fallback
+size_t seeds_workspace_bytes(size_t len, frieda_pcs_config cfg, uint32_t n_seeds) {
+    const uint32_t B = cfg.log_blowup_factor, last = cfg.log_last_layer_degree_bound;
+    if (n_seeds == 0 || n_seeds > 65535 || last > 10 || B > FRIEDA_MAX_LOG_DOMAIN || len > ((size_t)1 << 40)) return 0;
+    if (cfg.n_queries == 0 || cfg.n_queries > 4096) return 0;
+    Shape sh;
+    sh.cs = codec_shape(len);
+    sh.L = sh.cs.log_size;
+    sh.B = B;
+    if ((uint64_t)sh.L + B < 1 || (uint64_t)sh.L + B > FRIEDA_MAX_LOG_DOMAIN) return 0;
+    sh.n = sh.L + B;
+    sh.N = (size_t)1 << sh.n;
+    if (sh.n < 2 || sh.L < 1 + last) return 0;
+    const uint32_t n_inner = (sh.n - 1) - (last + B);
+    ArenaPlan plan;
+    size_t a, b, c, d;
+    FriLayerDev first;
+    std::vector<FriLayerDev> inner;
+    plan_prove_blob(plan, sh, last + B, 0, a, b, first, inner, c, d, true);
+    plan.off *= n_seeds;
+    plan.take(sizeof(DevTranscript) * n_seeds);
+    plan.take(sizeof(uint32_t) * k::GRIND_NEXT_STRIDE * n_seeds);
+    const size_t mw = opening_max_words(cfg.n_queries, n_inner) * n_seeds, mh = opening_max_hashes(cfg.n_queries, sh.n, n_inner, true) * n_seeds;
+    plan.take(8 * mw);
+    plan.take(8 * mh);
+    plan.take(4 * mw);
+    plan.take(32 * mh);
+    return plan.off;
 }
 
 }  // namespace frieda

@@ -107,12 +107,13 @@ struct TreeArgs {
                               // levels above the leaves either — 3/4 of a tree's bytes, read back only along ~20 opened paths, which
                               // decommit.hip re-hashes from the layer's values instead (2.7 % of a 2^24 proof, profiles/r05_skip_levels.txt)
     size_t bstride;           // batch: bytes between consecutive blobs' workspaces (blob = blockIdx.y); tr is an array
+    int shared_src;           // FOLD, prove_seeds: `cols` is the one encoded blob every blob (= seed) of the launch folds — no batch stride
 };
 
 // the arguments of the blob this workgroup works on
 __device__ __forceinline__ void tree_args_of_blob(TreeArgs& a) {
     const size_t off = (size_t)blockIdx.y * a.bstride;
-    a.cols = reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(a.cols) + off);
+    a.cols = reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(a.cols) + (a.shared_src ? 0 : off));
     a.children = a.children + off;
     a.out_vals = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(a.out_vals) + off);
     a.layers = a.layers + off;
@@ -326,6 +327,113 @@ __global__ __launch_bounds__(T5_THREADS) void tree5r_kernel(TreeArgs a) {
         b2_merkle_block<TP ? FRIEDA_B2_IDLE_NODE : B2_LAT>(m, h);
         store_hash(out_e, (wg_base >> 4) + t, h);
         FR_CLOCK_END(g_clock_tree5r, h[0])
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// tree5rs: the circle fold + five levels of tree5r for a GROUP OF SEEDS over one shared evaluation (prove_seeds, route B)
+// ------------------------------------------------------------------------------------------------
+// Proofs of one encoded blob under S seeds fold the SAME circle evaluation with S different alphas.  Through tree5r every seed's
+// workgroup re-reads the source pairs and the inverse twiddles and redoes the alpha-independent half of the fold (route A).  Here a
+// workgroup serves `group` consecutive seeds (blockIdx.y = group index): a thread loads its four source pairs and twiddles once and
+// keeps, per pair, f0 = x + y (unreduced, < 2P) and e = (x - y) * itw — the two operands qm_fold_pair combines with the alpha matrix,
+// 32 registers — then, seed after seed, forms f0 + alpha_s * e (the same multiply-adds and the same single reduction as
+// qm_fold_pair: identical words), writes that seed's folded layer and hashes its seven register-level nodes and the two LDS levels
+// exactly as tree5r does.  The alpha matrix of the seed in turn is uniform (scalar registers).  Every seed's outputs sit at
+// seed * bstride; stores are ordinary vector stores.
+template <bool TP>
+__global__ __launch_bounds__(T5_THREADS) void tree5rs_fold_circle_kernel(TreeArgs a, uint32_t n_seeds, uint32_t group) {
+    __shared__ __attribute__((aligned(16))) uint32_t RC[8 * (256 + 4)];
+    __shared__ __attribute__((aligned(16))) uint32_t RD[8 * (128 + 4)];
+    const uint32_t t = threadIdx.x;
+    const size_t wg_base = (size_t)blockIdx.x * 1024;  // the launcher guarantees 2^level_a >= 1024
+    const size_t g0 = wg_base + 4 * t;
+    const uint32_t seed0 = blockIdx.y * group;
+    const uint32_t seed1 = seed0 + group < n_seeds ? seed0 + group : n_seeds;
+    if (TP) tree_prologue_priority();
+    uint32_t f0[4][4], e[4][4];  // [pair][coordinate]
+    {
+        const uint2 xy = *reinterpret_cast<const uint2*>(a.itw + 2 * (g0 >> 2));
+        const uint32_t it[4] = {xy.y, m31_neg(xy.y), m31_neg(xy.x), xy.x};
+#pragma unroll
+        for (int c = 0; c < 4; c++) {
+            const uint4 lo = *reinterpret_cast<const uint4*>(a.cols + c * a.col_stride + 2 * g0);
+            const uint4 hi = *reinterpret_cast<const uint4*>(a.cols + c * a.col_stride + 2 * g0 + 4);
+            const uint32_t x[4] = {lo.x, lo.z, hi.x, hi.z}, y[4] = {lo.y, lo.w, hi.y, hi.w};
+#pragma unroll
+            for (int p = 0; p < 4; p++) {
+                f0[p][c] = x[p] + y[p];
+                e[p][c] = m31_reduce64((uint64_t)(x[p] + (P31 - y[p])) * it[p]);
+            }
+        }
+    }
+    for (uint32_t seed = seed0; seed < seed1; seed++) {
+        const size_t off = (size_t)seed * a.bstride;
+        const DevTranscript* tr = a.tr + seed;
+        uint32_t* out_vals = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(a.out_vals) + off);
+        uint8_t* layers = a.layers + off;
+        uint8_t* out_b = !a.skip_bc ? layers + layer_off(a.tree_log, a.level_a - 1) : nullptr;
+        uint8_t* out_c = !a.skip_bc ? layers + layer_off(a.tree_log, a.level_a - 2) : nullptr;
+        uint8_t* out_d = layers + layer_off(a.tree_log, a.level_a - 3);
+        uint8_t* out_e = layers + layer_off(a.tree_log, a.level_a - 4);
+        const QM31Mat am = qm_matrix({tr->alpha[0], tr->alpha[1], tr->alpha[2], tr->alpha[3]});
+        uint32_t r[4][4];  // [pair][coordinate]
+#pragma unroll
+        for (int p = 0; p < 4; p++) {
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                uint64_t acc = f0[p][k];
+#pragma unroll
+                for (int j = 0; j < 4; j++) acc += (uint64_t)am.m[k][j] * e[p][j];
+                r[p][k] = m31_reduce64(acc);
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < 4; k++)
+            *reinterpret_cast<uint4*>(out_vals + k * a.out_stride + g0) = make_uint4(r[0][k], r[1][k], r[2][k], r[3][k]);
+        uint32_t hb[2][8];
+        auto half_ab = [&](auto half_c) {
+            constexpr int half = decltype(half_c)::value;
+            uint32_t ha[2][8];
+            leaf_hash<TP ? FRIEDA_B2_IDLE_LEAF : B2_LAT>(r[2 * half][0], r[2 * half][1], r[2 * half][2], r[2 * half][3], ha[0]);
+            leaf_hash<TP ? FRIEDA_B2_IDLE_LEAF : B2_LAT>(r[2 * half + 1][0], r[2 * half + 1][1], r[2 * half + 1][2], r[2 * half + 1][3], ha[1]);
+            uint32_t m[16];
+#pragma unroll
+            for (int w = 0; w < 8; w++) m[w] = ha[0][w], m[8 + w] = ha[1][w];
+            b2_merkle_block<TP ? FRIEDA_B2_IDLE_NODE : B2_LAT>(m, hb[half]);
+        };
+        half_ab(std::integral_constant<int, 0>{});
+        half_ab(std::integral_constant<int, 1>{});
+        if (out_b) {
+            store_hash(out_b, (g0 >> 1), hb[0]);
+            store_hash(out_b, (g0 >> 1) + 1, hb[1]);
+        }
+        uint32_t hc[8];
+        {
+            uint32_t m[16];
+#pragma unroll
+            for (int w = 0; w < 8; w++) m[w] = hb[0][w], m[8 + w] = hb[1][w];
+            b2_merkle_block<TP ? FRIEDA_B2_IDLE_NODE : B2_LAT>(m, hc);
+        }
+        if (out_c) store_hash(out_c, g0 >> 2, hc);
+        // (RC is next written after the second barrier of this iteration, RD after the first barrier of the next: no extra barrier)
+        lds_put(RC, 256 + 4, t, hc);
+        __syncthreads();
+        if (t < 128) {
+            uint32_t m[16], h[8];
+            lds_children(RC, 256 + 4, t, m);
+            b2_merkle_block<TP ? FRIEDA_B2_IDLE_NODE : B2_LAT>(m, h);
+            store_hash(out_d, (wg_base >> 3) + t, h);
+            lds_put(RD, 128 + 4, t, h);
+        }
+        __syncthreads();
+        if (t < 64) {
+            uint32_t m[16], h[8];
+            lds_children(RD, 128 + 4, t, m);
+            b2_merkle_block<TP ? FRIEDA_B2_IDLE_NODE : B2_LAT>(m, h);
+            store_hash(out_e, (wg_base >> 4) + t, h);
+        }
+        if (TP) tree_prologue_priority();  // the next seed's fold arithmetic and stores ahead of the other waves' compressions
     }
 }
 
@@ -936,6 +1044,7 @@ struct TailArgs {
     DevTranscript* tr;
     size_t bstride;   // batch: bytes between blobs' workspaces (blob = blockIdx.y); tr is an array
     uint32_t* gnext;  // non-null: the grind's per-blob window counters, zeroed here for the grind launch that follows
+    int shared_src;   // prove_seeds: `src` is the encoded blob every blob (= seed) of the launch starts from — no batch stride
 };
 
 __global__ __launch_bounds__(WG1_THREADS) void tail_kernel(TailArgs a) {
@@ -957,7 +1066,7 @@ __global__ __launch_bounds__(WG1_THREADS) void tail_kernel(TailArgs a) {
     }
     if (t == 4 && a.gnext) a.gnext[blockIdx.y * GRIND_NEXT_STRIDE] = 0;
 
-    const uint32_t* src = reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(a.src) + boff);
+    const uint32_t* src = reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(a.src) + (a.shared_src ? 0 : boff));
     size_t src_stride = a.src_stride;
     uint32_t src_log = a.src_log;
     bool circle = a.src_is_circle != 0;
@@ -1315,7 +1424,7 @@ void finish_tree(const Launch& L, const TreeArgs& a, uint32_t m, uint32_t cur, c
 // Builds the tree of a layer whose level A is produced by `mode`; finishes with the root (and the channel step when tr).
 // `layers` non-null = keep every level (leaves-first); else only the root survives and `scratch` (>= 2 * 32 * 2^(m-4) B) is used.
 void build_tree(const Launch& L, int mode, TreeArgs a, uint32_t m, uint8_t* layers, uint8_t* scratch, uint8_t* root_out,
-                DevTranscript* tr, const DevTranscript* tr_init = nullptr, size_t tr_init_pitch = 0) {
+                DevTranscript* tr, const DevTranscript* tr_init = nullptr, size_t tr_init_pitch = 0, uint32_t seeds_group = 0) {
     a.level_a = m;
     a.tree_log = m;
     a.layers = layers;
@@ -1331,7 +1440,22 @@ void build_tree(const Launch& L, int mode, TreeArgs a, uint32_t m, uint8_t* laye
         return (md == T_LEAF4 ? 48.0 : 80.0) * (double)((size_t)1 << la) + node_levels_bytes(la > 0 ? la - 1 : 0, levels - 1);
     };
     const char* nm = mode == T_LEAF4 ? "tree5_leaf" : (mode == T_FOLD_CIRCLE ? "tree5_fold_circle" : "tree5_fold_line");
-    const uint32_t lv = launch_tree_a(L, mode, a, nm, bytes_of);
+    uint32_t lv;
+    // prove_seeds route B: the seed-looped kernel where route A's launch would be the (five-level) register-subtree kernel — every
+    // level kept, leaf hashes unwritten, 16-byte accesses; any other shape takes route A's kernel, which gives the same words
+    if (seeds_group && mode == T_FOLD_CIRCLE && a.shared_src && a.store_all && a.skip_a &&
+        tree_kernel_for(*L.tune, a.level_a, L.batch, tree_args_aligned16(a), true) == T_WIDE) {
+        const uint32_t groups = (L.batch + seeds_group - 1) / seeds_group;
+        const dim3 grid((unsigned)(((size_t)1 << a.level_a) / T5_UNITS), groups);
+        lv = T5_LEVELS;
+        Scope scope(L, "tree5s_fold_circle", (32.0 * groups / L.batch + 48.0) * (double)((size_t)1 << a.level_a) + node_levels_bytes(a.level_a - 1, lv - 1));
+        if (tp_launch(*L.tune, (size_t)grid.x * L.batch))
+            tree5rs_fold_circle_kernel<true><<<grid, T5_THREADS, 0, L.stream>>>(a, L.batch, seeds_group);
+        else
+            tree5rs_fold_circle_kernel<false><<<grid, T5_THREADS, 0, L.stream>>>(a, L.batch, seeds_group);
+    } else {
+        lv = launch_tree_a(L, mode, a, nm, bytes_of);
+    }
     const uint32_t cur = m - (lv - 1);  // lowest-index (smallest) level produced so far
     finish_tree(L, a, m, cur, layers ? layers + merkle_layer_offset(m, cur) : s0, s0, s1, root_out, tr, tr_init, tr_init_pitch);
 }
@@ -1464,7 +1588,8 @@ void tree_first_layer(const Launch& L, const uint32_t* cols, size_t stride, uint
 }
 
 void fold_and_tree(const Launch& L, bool circle, const uint32_t* src, size_t src_stride, uint32_t src_log, uint32_t n,
-                   const uint32_t* d_itw, DomainScalars ds, uint32_t* dst_vals, uint8_t* layers, DevTranscript* tr) {
+                   const uint32_t* d_itw, DomainScalars ds, uint32_t* dst_vals, uint8_t* layers, DevTranscript* tr, bool shared_src,
+                   uint32_t seeds_group) {
     const uint32_t m = src_log - 1;
     TreeArgs a{};
     a.cols = src;
@@ -1476,14 +1601,26 @@ void fold_and_tree(const Launch& L, bool circle, const uint32_t* src, size_t src
     a.inv_init_y = ds.inv_init_y;
     a.tr = tr;
     a.skip_a = m >= 1;
-    build_tree(L, circle ? T_FOLD_CIRCLE : T_FOLD_LINE, a, m, layers, nullptr, nullptr, tr);
+    a.shared_src = shared_src ? 1 : 0;
+    build_tree(L, circle ? T_FOLD_CIRCLE : T_FOLD_LINE, a, m, layers, nullptr, nullptr, tr, nullptr, 0, seeds_group);
+}
+
+void channel_after_shared_root(const Launch& L, const uint8_t* d_root, DevTranscript* tr, const DevTranscript* tr_init, size_t tr_init_pitch) {
+    TopArgs tp{};
+    tp.in = d_root;  // l_in = 0: the 8 words at `in` are the root; bstride 0: the same root for every blob of the launch
+    tp.tr = tr;
+    tp.tr_init = tr_init;
+    tp.tr_init_pitch = tr_init_pitch;
+    Scope scope(L, "seeds_first_alpha", 0.0);
+    top_kernel<<<dim3(1, L.batch), WG1_THREADS, 0, L.stream>>>(tp);
 }
 
 void fri_tail(const Launch& L, const uint32_t* src, size_t src_stride, uint32_t src_log, bool src_is_circle, uint32_t n,
               const uint32_t* d_itw, DomainScalars ds, uint32_t last_log, uint32_t last, uint32_t n_layers, uint32_t* const* vals,
-              uint8_t* const* trees, DevTranscript* tr, uint32_t* d_gnext) {
+              uint8_t* const* trees, DevTranscript* tr, uint32_t* d_gnext, bool shared_src) {
     TailArgs a{};
     a.gnext = d_gnext;
+    a.shared_src = shared_src ? 1 : 0;
     a.src = src;
     a.src_stride = src_stride;
     a.src_log = src_log;

@@ -111,6 +111,32 @@ class Proof {
     frieda_proof* h_ = nullptr;
 };
 
+// An encoded blob on the device (frieda_encoded): evaluations + first-layer tree + root in an allocation of its own — the half of a proof
+// that does not depend on the seed.  Made by Context::encode, only read by Context::prove_seeds (several contexts may share one).
+class Encoded {
+  public:
+    Encoded() = default;
+    explicit Encoded(frieda_encoded* h) : h_(h) {}
+    Encoded(const Encoded&) = delete;
+    Encoded& operator=(const Encoded&) = delete;
+    Encoded(Encoded&& o) noexcept : h_(o.h_) { o.h_ = nullptr; }
+    Encoded& operator=(Encoded&& o) noexcept {
+        std::swap(h_, o.h_);
+        return *this;
+    }
+    ~Encoded() { frieda_encoded_free(h_); }
+    Commitment commitment() const {
+        Commitment c;
+        check(frieda_encoded_commitment(h_, c.data()));
+        return c;
+    }
+    size_t bytes() const { return frieda_encoded_bytes(h_); }
+    const frieda_encoded* handle() const { return h_; }
+
+  private:
+    frieda_encoded* h_ = nullptr;
+};
+
 class Context {
   public:
     explicit Context(int device = 0, void* stream = nullptr) { check(frieda_ctx_create(device, stream, &h_)); }
@@ -149,6 +175,28 @@ class Context {
         check(frieda_commit_and_generate_proof_batch(h_, data, stride, len, count, seeds_or_null, cfg.c(), roots.data()->data(), ps.data()), h_);
         out.reserve(count);
         for (uint32_t i = 0; i < count; i++) out.emplace_back(roots[i], Proof(ps[i]));
+        return out;
+    }
+    // One blob under many seeds (a provider serving sampling clients): encode once — encode_device for a blob already on the device
+    // (frieda_encode_device) —, then proof i == commit_and_generate_proof(data, seeds[i], cfg).second byte for byte.  The split form
+    // (frieda_prove_seeds_begin / frieda_prove_seeds_finish) overlaps two contexts; frieda_commit_and_generate_proofs_for_seeds is the
+    // one-call convenience; frieda_seeds_workspace_bytes sizes a call.
+    Encoded encode(const uint8_t* data, size_t len, uint32_t log_blowup_factor) {
+        frieda_encoded* e = nullptr;
+        check(frieda_encode(h_, data, len, log_blowup_factor, &e), h_);
+        return Encoded(e);
+    }
+    Encoded encode_device(const void* d_data, size_t len, uint32_t log_blowup_factor) {
+        frieda_encoded* e = nullptr;
+        check(frieda_encode_device(h_, d_data, len, log_blowup_factor, &e), h_);
+        return Encoded(e);
+    }
+    std::vector<Proof> prove_seeds(const Encoded& enc, const std::vector<uint64_t>& seeds, const PcsConfig& cfg) {
+        std::vector<frieda_proof*> ps(seeds.size(), nullptr);
+        check(frieda_prove_seeds(h_, enc.handle(), seeds.data(), (uint32_t)seeds.size(), cfg.c(), ps.data()), h_);
+        std::vector<Proof> out;
+        out.reserve(ps.size());
+        for (frieda_proof* p : ps) out.emplace_back(p);
         return out;
     }
     // The reconstructor's half of the README's sampling flow (/root/reference/README.md:56-69): any >= 2^log_coef + 2 distinct

@@ -165,6 +165,39 @@ int frieda_prove_batch_begin_device(frieda_ctx* ctx, const void* d_data, size_t 
 int frieda_prove_batch_finish(frieda_ctx* ctx, uint32_t count, uint8_t* out_commitments, frieda_proof** out_proofs);
 int frieda_commit_batch(frieda_ctx* ctx, const uint8_t* data, size_t stride, size_t len, uint32_t count, uint32_t log_blowup_factor,
                         uint8_t* out_roots);
+/* One blob proved under many seeds.  In data-availability sampling a sample IS a proof: every client sends a seed and the provider
+ * answers with commit_and_generate_proof(data, seed, cfg) of the SAME blob.  The seed enters the transcript before the first root is
+ * mixed, so unpacking, the Reed-Solomon encode and the first-layer Merkle tree do not depend on it (about half of a large proof); every
+ * alpha, inner layer, nonce, query and opening does.  frieda_encode does the shared half once and keeps it on the device:
+ * a frieda_encoded owns ONE device allocation of its own — the 4 evaluation columns, the first-layer tree and the root,
+ * frieda_encoded_bytes() bytes — outside the context's workspace: it survives every other call on the context,
+ * frieda_ctx_release_workspace and the context itself, until frieda_encoded_free.  Proving only READS it, so several contexts on the
+ * same device may prove from one frieda_encoded at the same time (it must not be freed while a job that uses it is in flight).
+ * frieda_encode* synchronise (the commitment comes back); frieda_encoded_commitment == frieda_commit(data, log_blowup_factor). */
+typedef struct frieda_encoded frieda_encoded;
+int frieda_encode(frieda_ctx* ctx, const uint8_t* data, size_t len, uint32_t log_blowup_factor, frieda_encoded** out);
+int frieda_encode_device(frieda_ctx* ctx, const void* d_data, size_t len, uint32_t log_blowup_factor, frieda_encoded** out);
+int frieda_encoded_commitment(const frieda_encoded* enc, uint8_t out_root[32]);
+size_t frieda_encoded_bytes(const frieda_encoded* enc); /* device memory it holds */
+void frieda_encoded_free(frieda_encoded* enc);
+/* n_seeds proofs of the encoded blob: out_proofs[i] serialises to exactly the bytes of frieda_commit_and_generate_proof(data,
+ * &seeds[i], cfg); repeated seeds are allowed (identical proofs), the order is the caller's.  seeds != NULL, 1 <= n_seeds <= 65535,
+ * cfg.log_blowup_factor == the one the blob was encoded with, the ctx on the blob's device, and every argument rule of the batch
+ * entry points — else FRIEDA_ERR_ARG / FRIEDA_ERR_INVARIANT as there.  n_seeds > 1 is a batch: device transcript only (last FRI
+ * layer <= 2^11 points, host-channel policy off), else FRIEDA_ERR_ARG; n_seeds == 1 works under both policies.  _begin enqueues and
+ * returns without synchronising, _finish waits once and builds the n_seeds proofs of the job in flight (one job per ctx, as above).
+ * Memory: a call's workspace grows with n_seeds and is NOT cut into passes: frieda_seeds_workspace_bytes(len, cfg, n_seeds) is what
+ * the call asks of the ctx (the encoded blob excluded; 0 = a shape the prover refuses) — per seed the inner layers only, about half
+ * of frieda_workspace_bytes(.., prove).  A call the device cannot hold returns FRIEDA_ERR_NOMEM and leaves the ctx usable: size
+ * n_seeds per call with that function.  The seed-looped first fold is selected by the option FRIEDA_SEEDS_FOLD_GROUP. */
+int frieda_prove_seeds_begin(frieda_ctx* ctx, const frieda_encoded* enc, const uint64_t* seeds, uint32_t n_seeds, frieda_pcs_config cfg);
+int frieda_prove_seeds_finish(frieda_ctx* ctx, frieda_proof** out_proofs);
+int frieda_prove_seeds(frieda_ctx* ctx, const frieda_encoded* enc, const uint64_t* seeds, uint32_t n_seeds, frieda_pcs_config cfg,
+                       frieda_proof** out_proofs);
+/* convenience for a caller that has all seeds at once: encode, prove, free */
+int frieda_commit_and_generate_proofs_for_seeds(frieda_ctx* ctx, const uint8_t* data, size_t len, const uint64_t* seeds, uint32_t n_seeds,
+                                                frieda_pcs_config cfg, uint8_t out_commitment[32], frieda_proof** out_proofs);
+size_t frieda_seeds_workspace_bytes(size_t len, frieda_pcs_config cfg, uint32_t n_seeds);
 int frieda_commit_batch_device(frieda_ctx* ctx, const void* d_data, size_t stride, size_t len, uint32_t count,
                                uint32_t log_blowup_factor, uint8_t* out_roots);
 /* api::generate_proof (src/lib.rs:36) */
