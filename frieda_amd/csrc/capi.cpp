@@ -725,6 +725,7 @@ int frieda_dev_gather_device(frieda_ctx* ctx, const uint32_t* d_cols, size_t str
     if (!ctx) return FRIEDA_ERR_ARG;
     if (n == 0) return FRIEDA_OK;
     if (!d_cols || !d_idx || !d_out || ncols == 0 || ncols > 65535) return FRIEDA_ERR_ARG;
+    if (reinterpret_cast<uintptr_t>(d_idx) & 7) return ctx->c.fail(FRIEDA_ERR_ARG, "index list not 8-byte aligned");
     FR_HIP(&ctx->c, hipSetDevice(ctx->c.device));
     k::gather_rows(ctx->c.launch(), d_cols, stride, ncols, d_idx, n, d_out);
     FR_HIP(&ctx->c, hipGetLastError());
@@ -972,6 +973,8 @@ int frieda_reconstruct_device(frieda_ctx* ctx, const uint32_t* d_block, uint32_t
 int frieda_merkle_commit_layer(frieda_ctx* ctx, uint32_t log_size, const void* d_prev, const uint32_t* const* d_cols, uint32_t ncols,
                                void* d_out) {
     if (!ctx || !d_out || log_size > FRIEDA_MAX_LOG_DOMAIN || (ncols && !d_cols) || ncols > 1024) return FRIEDA_ERR_ARG;
+    // the kernels move hashes with 16-byte accesses
+    if ((reinterpret_cast<uintptr_t>(d_prev) | reinterpret_cast<uintptr_t>(d_out)) & 15) return ctx->c.fail(FRIEDA_ERR_ARG, "hash layer not 16-byte aligned");
     FR_NO_JOB(&ctx->c);
     FR_GUARD_BEGIN
     FR_HIP(&ctx->c, hipSetDevice(ctx->c.device));
@@ -1000,6 +1003,7 @@ size_t frieda_merkle_layer_offset(uint32_t log_size, uint32_t layer_log) { retur
 
 int frieda_merkle_commit(frieda_ctx* ctx, const uint32_t* d_cols, uint32_t log_size, void* d_layers) {
     if (!ctx || !d_cols || !d_layers || log_size > FRIEDA_MAX_LOG_DOMAIN) return FRIEDA_ERR_ARG;
+    if (reinterpret_cast<uintptr_t>(d_layers) & 15) return ctx->c.fail(FRIEDA_ERR_ARG, "tree layers not 16-byte aligned");
     FR_HIP(&ctx->c, hipSetDevice(ctx->c.device));
     const size_t n = (size_t)1 << log_size;
     k::merkle_tree4(ctx->c.launch(), d_cols, d_cols + n, d_cols + 2 * n, d_cols + 3 * n, log_size, static_cast<uint8_t*>(d_layers));
@@ -1090,6 +1094,11 @@ int frieda_fold_line(frieda_ctx* ctx, const uint32_t* d_src, uint32_t line_log, 
 int frieda_circle_extend(frieda_ctx* ctx, const uint32_t* d_coef, uint32_t ncols, uint32_t log_coef, uint32_t log_size, uint32_t* d_out) {
     if (!ctx || !d_coef || !d_out || ncols == 0 || ncols > 65535 || log_size > FRIEDA_MAX_LOG_DOMAIN) return FRIEDA_ERR_ARG;
     if (log_size < log_coef) return ctx->c.fail(FRIEDA_ERR_INVARIANT, "extend: log_size smaller than the polynomial's (stwo asserts log_size >= poly.log_size())");
+    {  // a workgroup would read coefficients another has already overwritten
+        const uintptr_t in = reinterpret_cast<uintptr_t>(d_coef), out = reinterpret_cast<uintptr_t>(d_out);
+        const size_t in_len = ((size_t)4 * ncols) << log_coef, out_len = ((size_t)4 * ncols) << log_size;
+        if (in < out + out_len && out < in + in_len) return ctx->c.fail(FRIEDA_ERR_ARG, "extend: coefficient and output buffers must not overlap");
+    }
     FR_GUARD_BEGIN
     FR_HIP(&ctx->c, hipSetDevice(ctx->c.device));
     k::circle_extend(ctx->c.launch(), d_coef, ncols, log_coef, log_size, d_out);

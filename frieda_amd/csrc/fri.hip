@@ -33,7 +33,15 @@ __device__ __forceinline__ uint32_t inv_circle_twiddle(const uint32_t* __restric
     return (r == 1 || r == 2) ? m31_neg(v) : v;
 }
 
+// A8: every column base is 8-byte aligned (one 8-byte load per coordinate); otherwise word loads — a Level B caller may pass any
+// 4-byte aligned column (a sub-column, a SecureColumn of fewer than two words per coordinate)
+template <bool A8>
 __device__ __forceinline__ void load_pair(const uint32_t* __restrict__ src, size_t stride, size_t i, QM31& f0, QM31& f1) {
+    if constexpr (!A8) {
+        f0 = {src[2 * i], src[stride + 2 * i], src[2 * stride + 2 * i], src[3 * stride + 2 * i]};
+        f1 = {src[2 * i + 1], src[stride + 2 * i + 1], src[2 * stride + 2 * i + 1], src[3 * stride + 2 * i + 1]};
+        return;
+    }
     uint2 a = reinterpret_cast<const uint2*>(src)[i];
     uint2 b = reinterpret_cast<const uint2*>(src + stride)[i];
     uint2 c = reinterpret_cast<const uint2*>(src + 2 * stride)[i];
@@ -42,6 +50,7 @@ __device__ __forceinline__ void load_pair(const uint32_t* __restrict__ src, size
     f1 = {a.y, b.y, c.y, d.y};
 }
 
+template <bool A8>
 __global__ __launch_bounds__(FR_THREADS) void fold_circle_kernel(uint32_t* __restrict__ dst, size_t dst_stride,
                                                                  const uint32_t* __restrict__ src, size_t src_stride,
                                                                  uint32_t n, const uint32_t* __restrict__ itw,
@@ -50,7 +59,7 @@ __global__ __launch_bounds__(FR_THREADS) void fold_circle_kernel(uint32_t* __res
     size_t half = (size_t)1 << (n - 1);
     if (i >= half) return;
     QM31 a, b;
-    load_pair(src, src_stride, i, a, b);
+    load_pair<A8>(src, src_stride, i, a, b);
     uint32_t it = inv_circle_twiddle(itw, n, i, inv_init_y);
     QM31 f0 = qm_add(a, b), f1 = qm_scale(qm_sub(a, b), it);
     QM31 fp = qm_add(qm_mul(alpha, f1), f0);
@@ -62,6 +71,7 @@ __global__ __launch_bounds__(FR_THREADS) void fold_circle_kernel(uint32_t* __res
     dst[3 * dst_stride + i] = r.d;
 }
 
+template <bool A8>
 __global__ __launch_bounds__(FR_THREADS) void fold_line_kernel(const uint32_t* __restrict__ src, size_t src_stride,
                                                                uint32_t m, const uint32_t* __restrict__ itw_level,
                                                                QM31 alpha, uint32_t* __restrict__ dst, size_t dst_stride) {
@@ -69,7 +79,7 @@ __global__ __launch_bounds__(FR_THREADS) void fold_line_kernel(const uint32_t* _
     size_t half = (size_t)1 << (m - 1);
     if (i >= half) return;
     QM31 a, b;
-    load_pair(src, src_stride, i, a, b);
+    load_pair<A8>(src, src_stride, i, a, b);
     uint32_t it = itw_level[i];
     QM31 f0 = qm_add(a, b), f1 = qm_scale(qm_sub(a, b), it);
     QM31 r = qm_add(f0, qm_mul(alpha, f1));
@@ -99,6 +109,9 @@ __global__ __launch_bounds__(FR_THREADS) void gather_kernel(const uint32_t* __re
         reinterpret_cast<uint4*>(out_hashes)[2 * hsh + part] = srcp[part];
     }
 }
+
+// the 8-byte pair loads of load_pair<true> need every coordinate column 8-byte aligned
+bool pairs_aligned8(const uint32_t* src, size_t stride) { return ((reinterpret_cast<uintptr_t>(src) | (stride * 4)) & 7) == 0; }
 
 struct Digest8 {
     uint32_t w[8];
@@ -138,8 +151,11 @@ void fold_circle_into_line(const Launch& L, uint32_t* d_dst, size_t dst_stride, 
     size_t half = (size_t)1 << (n - 1);
     hipStream_t s = L.stream;
     Scope scope(L, "fold_circle", 48.0 * (double)half);  // 16N in + 8N out (24N)
-    fold_circle_kernel<<<(unsigned)((half + FR_THREADS - 1) / FR_THREADS), FR_THREADS, 0, s>>>(d_dst, dst_stride, d_src, src_stride,
-                                                                                             n, d_itw, ds.inv_init_y, a, a2);
+    const unsigned grid = (unsigned)((half + FR_THREADS - 1) / FR_THREADS);
+    if (pairs_aligned8(d_src, src_stride))
+        fold_circle_kernel<true><<<grid, FR_THREADS, 0, s>>>(d_dst, dst_stride, d_src, src_stride, n, d_itw, ds.inv_init_y, a, a2);
+    else
+        fold_circle_kernel<false><<<grid, FR_THREADS, 0, s>>>(d_dst, dst_stride, d_src, src_stride, n, d_itw, ds.inv_init_y, a, a2);
 }
 
 void fold_line(const Launch& L, const uint32_t* d_src, size_t src_stride, uint32_t m, uint32_t n, const uint32_t* d_itw,
@@ -151,8 +167,11 @@ void fold_line(const Launch& L, const uint32_t* d_src, size_t src_stride, uint32
     const uint32_t* lvl = d_itw + tw_level_offset(n, n - 1 - m);
     hipStream_t s = L.stream;
     Scope scope(L, "fold_line", 48.0 * (double)half);  // 16M in + 8M out
-    fold_line_kernel<<<(unsigned)((half + FR_THREADS - 1) / FR_THREADS), FR_THREADS, 0, s>>>(d_src, src_stride, m, lvl, a, d_dst,
-                                                                                           dst_stride);
+    const unsigned grid = (unsigned)((half + FR_THREADS - 1) / FR_THREADS);
+    if (pairs_aligned8(d_src, src_stride))
+        fold_line_kernel<true><<<grid, FR_THREADS, 0, s>>>(d_src, src_stride, m, lvl, a, d_dst, dst_stride);
+    else
+        fold_line_kernel<false><<<grid, FR_THREADS, 0, s>>>(d_src, src_stride, m, lvl, a, d_dst, dst_stride);
 }
 
 void gather(const Launch& L, const uint32_t* d_base, const uint64_t* d_word_idx, size_t n_words, uint32_t* d_out_words,

@@ -133,8 +133,9 @@ __global__ __launch_bounds__(PO_THREADS) void decompose_lambda_kernel(const uint
         __syncthreads();
     }
 }
-__global__ __launch_bounds__(PO_THREADS) void decompose_apply_kernel(const uint32_t* __restrict__ ev, size_t n, const uint32_t* __restrict__ lambda,
-                                                                     uint32_t* __restrict__ g) {
+// ev and g may be the same buffer (frieda_fri_decompose in place): every thread reads its word before it writes it, and neither
+// pointer is __restrict__
+__global__ __launch_bounds__(PO_THREADS) void decompose_apply_kernel(const uint32_t* ev, size_t n, const uint32_t* __restrict__ lambda, uint32_t* g) {
     const size_t i = (size_t)blockIdx.x * PO_THREADS + threadIdx.x;
     const size_t coord = blockIdx.y;
     if (i >= n) return;

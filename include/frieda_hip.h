@@ -120,7 +120,8 @@ int frieda_ctx_last_transcript(const frieda_ctx* ctx, uint32_t* n_layers, uint32
 /* api::commit(data, log_blowup_factor) -> [u8; 32]   (src/lib.rs:31, src/commit.rs:11-22) */
 int frieda_commit(frieda_ctx* ctx, const uint8_t* data, size_t len, uint32_t log_blowup_factor, uint8_t out_root[32]);
 /* same with the blob already resident in device memory; the root is written to device memory
- * (d_out_root, 32 B) asynchronously on the ctx stream — no host synchronisation */
+ * (d_out_root, 32 B, 4-byte aligned) asynchronously on the ctx stream — no host synchronisation.  d_data (here and in every
+ * _device form below) is a byte pointer: any address, and any stride >= len between the blobs of a batch. */
 int frieda_commit_device(frieda_ctx* ctx, const void* d_data, size_t len, uint32_t log_blowup_factor, void* d_out_root);
 
 /* proof::commit_and_generate_proof(data, seed, cfg) -> (Commitment, Proof)   (src/proof.rs:32-77);
@@ -295,6 +296,12 @@ size_t frieda_proof_serialize(const frieda_proof* p, uint8_t* buf, size_t cap);
 int frieda_proof_deserialize(const uint8_t* buf, size_t len, frieda_proof** out);
 
 /* ---- Level B: backend-trait granular operations on device buffers ------------------------------- */
+/* The buffer contract of every device pointer of this header (Level A's d_data / d_out_root included):
+ * A device pointer to words needs 4-byte alignment, a pointer to bytes none, and a pointer to hashes 16 bytes, unless the function says otherwise. No call writes outside the extents it documents. No call modifies a `const` argument.
+ * Anything beyond those alignments only selects a faster kernel for the same result (16-byte aligned columns whose stride is a multiple
+ * of 4 words take the vector routes).  A hash pointer that is not 16-byte aligned is refused with FRIEDA_ERR_ARG before anything is
+ * launched.  The exceptions: frieda_merkle_root's d_root and frieda_commit_device's d_out_root (one hash, stored by words: 4-byte
+ * alignment is enough) and frieda_dev_gather_device's d_idx (64-bit indices: 8-byte alignment, else FRIEDA_ERR_ARG). */
 /* Column<T> storage */
 int frieda_dev_alloc(frieda_ctx* ctx, size_t bytes, void** d_out);
 int frieda_dev_free(frieda_ctx* ctx, void* d);
@@ -317,8 +324,9 @@ int frieda_dev_at_secure(frieda_ctx* ctx, const uint32_t* d_cols, size_t stride,
 int frieda_dev_gather(frieda_ctx* ctx, const uint32_t* d_cols, size_t stride, uint32_t ncols, const uint64_t* idx, size_t n, uint32_t* out);
 /* the same for a column of 32-byte hashes (one layer of a stored tree: layer_len hashes, 16-byte aligned); out: n x 32 bytes (host) */
 int frieda_dev_gather_hashes(frieda_ctx* ctx, const void* d_layer, size_t layer_len, const uint64_t* idx, size_t n, uint8_t* out);
-/* asynchronous form on the ctx stream: d_idx[n] and d_out[n][ncols] in device memory.  Nothing is checked on the host: the row of an
- * index >= stride is filled with 0xFFFFFFFF (not a canonical M31).  Available while a proof is in flight. */
+/* asynchronous form on the ctx stream: d_idx[n] (8-byte aligned, else FRIEDA_ERR_ARG) and d_out[n][ncols] in device memory.  The
+ * indices are not checked on the host: the row of an index >= stride is filled with 0xFFFFFFFF (not a canonical M31).  Available while
+ * a proof is in flight. */
 int frieda_dev_gather_device(frieda_ctx* ctx, const uint32_t* d_cols, size_t stride, uint32_t ncols, const uint64_t* d_idx, size_t n,
                              uint32_t* d_out);
 
@@ -426,8 +434,9 @@ int frieda_reconstruct_points_device(frieda_ctx* ctx, const uint32_t* d_cells, c
                                      uint32_t log_coef, uint32_t log_domain, size_t len, void* d_out_bytes);
 
 /* MerkleOps::commit_on_layer(log_size, prev_layer, columns): d_prev is NULL or 2^(log_size+1) hashes;
- * d_cols is a host array of ncols device column pointers (2^log_size words each); d_out gets 2^log_size
- * 32-byte hashes */
+ * d_cols is a host array of ncols device column pointers (2^log_size words each, any 4-byte aligned addresses: sub-slices of
+ * one SecureColumn are fine); d_out gets 2^log_size 32-byte hashes.  d_prev and d_out are hash pointers (16-byte aligned, else
+ * FRIEDA_ERR_ARG). */
 int frieda_merkle_commit_layer(frieda_ctx* ctx, uint32_t log_size, const void* d_prev, const uint32_t* const* d_cols,
                                uint32_t ncols, void* d_out);
 /* MerkleProver::commit over 4 equal-length columns d_cols[4][2^log_size]: all layers, leaves first
@@ -435,7 +444,7 @@ int frieda_merkle_commit_layer(frieda_ctx* ctx, uint32_t log_size, const void* d
  * bytes */
 int frieda_merkle_commit(frieda_ctx* ctx, const uint32_t* d_cols, uint32_t log_size, void* d_layers);
 size_t frieda_merkle_layer_offset(uint32_t log_size, uint32_t layer_log);
-/* root only (no layer is stored): the commit() shape */
+/* root only (no layer is stored): the commit() shape.  d_root: 32 bytes, 4-byte aligned. */
 int frieda_merkle_root(frieda_ctx* ctx, const uint32_t* d_cols, uint32_t log_size, void* d_root);
 
 /* FriOps::fold_circle_into_line: d_dst[4][N/2] (accumulated: dst*alpha^2 + f') from d_src[4][N] */
@@ -461,7 +470,7 @@ int frieda_circle_evaluate_fold2(frieda_ctx* ctx, const uint32_t* d_coeffs, uint
 /* ---- the trait methods frieda's three functions never call (SURVEY.md §8b lists them on the plug-in surface behind `CpuBackend`,
  * src/commit.rs:15-17, src/proof.rs:47-58): an `impl PolyOps / FriOps for HipBackend` needs them ----
  * PolyOps::extend(poly, log_size): d_coef[ncols][2^log_coef] -> d_out[ncols][2^log_size], zero-extended (FRIEDA_ERR_INVARIANT for
- * log_size < log_coef, stwo's assert).  Asynchronous on the ctx stream; the buffers must not overlap. */
+ * log_size < log_coef, stwo's assert).  Asynchronous on the ctx stream; the buffers must not overlap (FRIEDA_ERR_ARG). */
 int frieda_circle_extend(frieda_ctx* ctx, const uint32_t* d_coef, uint32_t ncols, uint32_t log_coef, uint32_t log_size, uint32_t* d_out);
 /* PolyOps::eval_at_point(poly, point): each of the ncols polynomials d_coef[ncols][2^log_coef] at the circle point (x, y) over
  * the secure field (QM31 coordinates as 4 canonical words each); out[ncols][4] on the host.  Synchronises the ctx stream. */

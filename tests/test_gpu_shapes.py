@@ -164,19 +164,23 @@ def test_circle_evaluate_mb_scale_shapes(gpu_ctx, oracle, L, n, ncols):
 
 @pytest.mark.parametrize("knob", ["FRIEDA_NO_ENCODE_TREE_FUSION", "FRIEDA_ENCODE_TREE_FUSION_PROVE", "FRIEDA_NTT_NO_PAD8", "FRIEDA_NTT_TREE_REG_ONLY", "FRIEDA_T5_REG3_LOG=18", "FRIEDA_NTT_CPW=2",
                                   "FRIEDA_HOST_DECOMMIT", "FRIEDA_NO_SMALL_FUSED", "FRIEDA_NTT_CPW_SMALL=4", "FRIEDA_NTT_REP", "FRIEDA_NTT_REP=0", "FRIEDA_TAIL_RUN_LOG=6",
-                                  "FRIEDA_T9_MAX_LOG=12", "FRIEDA_UNPACK_TILES=1", "FRIEDA_T5_WIDE_LOG=16", "FRIEDA_TP_MIN_WGS=0", "FRIEDA_TP_MIN_WGS=1073741824", "FRIEDA_TREE_SKIP_LOG=10", "FRIEDA_TREE_SKIP_LONE_LOG=10", "FRIEDA_TREE_SKIP_LOG=40"])
+                                  "FRIEDA_T9_MAX_LOG=12", "FRIEDA_UNPACK_TILES=1", "FRIEDA_T5_WIDE_LOG=16", "FRIEDA_TP_MIN_WGS=0", "FRIEDA_TP_MIN_WGS=1073741824", "FRIEDA_TREE_SKIP_LOG=10", "FRIEDA_TREE_SKIP_LONE_LOG=10", "FRIEDA_TREE_SKIP_LOG=40",
+                                  "FRIEDA_INTT_GENERIC", "FRIEDA_NTT_NO_CP", "FRIEDA_TOP_MAX_LOG=11", "FRIEDA_GATHER_COPY"])
 def test_knob_variants_on_their_own_context(oracle, knob):
     """The A/B options of DESIGN.md §10 select other kernels / templates for the same result (unfused encode + leaf launch, generic
     strided pass instead of the padded 8-layer one, the register-only tree variants, the compressions' throughput form — runs with
     switched wave priority — in EVERY tree launch or in none, ...).  They are PER CONTEXT
     (frieda_ctx_set_option; the environment only sets a new context's defaults), so each variant runs on its own context in this
-    process: commit root and whole proof against the oracle on five shapes."""
+    process: commit root and whole proof against the oracle on five shapes.  (FRIEDA_NTT_NO_CP selects a kernel of
+    frieda_circle_evaluate_fold2 only: tests/test_gpu_buffer_contract.py runs that call under both values.)"""
     import frieda_amd
 
     name, _, val = knob.partition("=")
     ctx = frieda_amd.Context(0)
     try:
         ctx.set_option(name, int(val or "1"))
+        if name == "FRIEDA_GATHER_COPY":
+            ctx.set_option("FRIEDA_HOST_DECOMMIT", 1)  # the copy form belongs to the host-planned gather: only that route reads the option
         for L, B in ((16, 4), (18, 2), (13, 7), (12, 4), (7, 4)):
             length = (4 << L) * 30 // 8 - 4321 if L > 8 else (4 << L) * 30 // 8 - 7
             data = splitmix64_bytes(3000 + L, length).tobytes()
