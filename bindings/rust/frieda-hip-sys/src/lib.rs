@@ -38,6 +38,11 @@ pub const FRIEDA_ERR_HIP: c_int = 2;
 pub const FRIEDA_ERR_INVARIANT: c_int = 3;
 pub const FRIEDA_ERR_NOMEM: c_int = 4;
 pub const FRIEDA_ERR_FORMAT: c_int = 5;
+/// per-proof status bytes of frieda_verify_many / frieda_verify_samples_many / frieda_reconstruct_from_proofs
+pub const FRIEDA_VERIFY_REJECTED: u8 = 0;
+pub const FRIEDA_VERIFY_ACCEPTED: u8 = 1;
+pub const FRIEDA_VERIFY_INVARIANT: u8 = 2;
+pub const FRIEDA_VERIFY_WRONG_COMMITMENT: u8 = 3;
 
 extern "C" {
     pub fn frieda_abi_version() -> u32;
@@ -114,6 +119,12 @@ extern "C" {
     pub fn frieda_verify(proof: *const frieda_proof, seed: *const u64, ok: *mut c_int) -> c_int;
     /// verify + the positions the accepted proof sampled (evaluations[i] sits at out_positions[i] of the bit-reversed codeword)
     pub fn frieda_verify_samples(proof: *const frieda_proof, seed: *const u64, ok: *mut c_int, out_positions: *mut u32, cap: usize, n_positions: *mut usize) -> c_int;
+    /// many proofs verified in one call on the GPU: one status byte per proof (FRIEDA_VERIFY_*), each the result of frieda_verify
+    pub fn frieda_verify_many(ctx: *mut frieda_ctx, proofs: *const *const frieda_proof, seeds: *const u64, count: u32, expected_commitment: *const u8, out_status: *mut u8) -> c_int;
+    /// the same + the positions of every accepted proof (row i of out_positions: out_n_positions[i] entries, pitch apart)
+    pub fn frieda_verify_samples_many(ctx: *mut frieda_ctx, proofs: *const *const frieda_proof, seeds: *const u64, count: u32, expected_commitment: *const u8, out_status: *mut u8, out_positions: *mut u32, pitch: usize, out_n_positions: *mut u32) -> c_int;
+    /// verify, pool the verified samples, rebuild the blob and check it against the commitment
+    pub fn frieda_reconstruct_from_proofs(ctx: *mut frieda_ctx, proofs: *const *const frieda_proof, seeds: *const u64, count: u32, expected_commitment: *const u8, len: usize, out_bytes: *mut u8, out_status: *mut u8, n_points: *mut usize) -> c_int;
 
     // struct Proof
     pub fn frieda_proof_free(p: *mut frieda_proof);

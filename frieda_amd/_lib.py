@@ -15,6 +15,7 @@ HEADER_PATH = os.path.join(_ROOT, "include", "frieda_hip.h")
 TESTING_HEADER_PATH = os.path.join(_ROOT, "include", "frieda_hip_testing.h")  # test hooks: not part of the drop-in boundary
 
 OK, ERR_ARG, ERR_HIP, ERR_INVARIANT, ERR_NOMEM, ERR_FORMAT = 0, 1, 2, 3, 4, 5
+VERIFY_REJECTED, VERIFY_ACCEPTED, VERIFY_INVARIANT, VERIFY_WRONG_COMMITMENT = 0, 1, 2, 3  # status bytes of frieda_verify_many
 
 
 class PcsConfigC(C.Structure):
@@ -132,6 +133,9 @@ def lib():
         "frieda_prove_many": (C.c_int, [vp, pp, C.POINTER(sz), u32, u64p, PcsConfigC, vp, pp]),
         "frieda_verify": (C.c_int, [vp, u64p, C.POINTER(C.c_int)]),
         "frieda_verify_samples": (C.c_int, [vp, u64p, C.POINTER(C.c_int), vp, sz, C.POINTER(sz)]),
+        "frieda_verify_many": (C.c_int, [vp, pp, u64p, u32, vp, vp]),
+        "frieda_verify_samples_many": (C.c_int, [vp, pp, u64p, u32, vp, vp, vp, sz, vp]),
+        "frieda_reconstruct_from_proofs": (C.c_int, [vp, pp, u64p, u32, vp, sz, vp, vp, C.POINTER(sz)]),
         "frieda_proof_free": (None, [vp]),
         "frieda_proof_clone": (C.c_int, [vp, pp]),
         "frieda_proof_proof_of_work": (u64, [vp]),

@@ -413,6 +413,69 @@ class Context:
         self._keep = None
         return bytes(root), Proof(out)
 
+    # ---- many proofs verified in one call on the device (frieda_verify_many*, verify.hip) ----
+    def _proof_array(self, proofs):
+        return (C.c_void_p * len(proofs))(*[p._h.value if isinstance(p._h, C.c_void_p) else p._h for p in proofs])
+
+    def verify_many(self, proofs, seeds=None, expected_commitment=None):
+        """One status byte per proof (numpy uint8: VERIFY_REJECTED / _ACCEPTED / _INVARIANT / _WRONG_COMMITMENT), each the result
+        verify() gives for that proof.  seeds: None or one int per proof; expected_commitment: 32 bytes or None."""
+        import numpy as np
+
+        count = len(proofs)
+        status = np.zeros(count, dtype=np.uint8)
+        if count == 0:
+            return status
+        com = (C.c_uint8 * 32)(*expected_commitment) if expected_commitment is not None else None
+        _check(self._L.frieda_verify_many(self._h, self._proof_array(proofs), self._seeds_array(seeds, count), count, com, status.ctypes.data), self._h)
+        return status
+
+    def verify_samples_many(self, proofs, seeds=None, expected_commitment=None, pitch=None):
+        """(status, positions): positions[i] is the numpy uint32 array verify_samples() returns for proof i, None unless it is accepted."""
+        import numpy as np
+
+        count = len(proofs)
+        status = np.zeros(count, dtype=np.uint8)
+        if count == 0:
+            return status, []
+        if pitch is None:
+            pitch = max(1, max(int(p.pcs_config.fri_config.n_queries) for p in proofs))
+        pos = np.zeros((count, max(1, pitch)), dtype=np.uint32)
+        npos = np.zeros(count, dtype=np.uint32)
+        com = (C.c_uint8 * 32)(*expected_commitment) if expected_commitment is not None else None
+        _check(
+            self._L.frieda_verify_samples_many(
+                self._h, self._proof_array(proofs), self._seeds_array(seeds, count), count, com, status.ctypes.data, pos.ctypes.data, pitch, npos.ctypes.data
+            ),
+            self._h,
+        )
+        return status, [pos[i, : npos[i]].copy() if status[i] == _lib.VERIFY_ACCEPTED else None for i in range(count)]
+
+    def reconstruct_from_proofs(self, proofs, seeds, expected_commitment, n_bytes):
+        """Verify the proofs against the commitment, pool the verified samples and rebuild the blob: (bytes, status, n_points).  Raises
+        FriedaError (with .n_points and .proof_status set) when the verified points do not suffice or the result does not commit to
+        expected_commitment."""
+        import numpy as np
+
+        count = len(proofs)
+        status = np.zeros(max(count, 1), dtype=np.uint8)
+        out = np.zeros(max(n_bytes, 1), dtype=np.uint8)
+        n = C.c_size_t(0)
+        com = (C.c_uint8 * 32)(*expected_commitment)
+        try:
+            _check(
+                self._L.frieda_reconstruct_from_proofs(
+                    self._h, self._proof_array(proofs) if count else None, self._seeds_array(seeds, count), count, com, n_bytes, out.ctypes.data,
+                    status.ctypes.data, C.byref(n)
+                ),
+                self._h,
+            )
+        except FriedaError as e:
+            e.n_points = n.value
+            e.proof_status = status[:count]
+            raise
+        return out[:n_bytes].tobytes(), status[:count], n.value
+
 
 class Encoded:
     """An encoded blob on the device (frieda_encoded): evaluations + first-layer tree + root, in an allocation of its own that outlives
@@ -809,3 +872,18 @@ def verify_samples(proof, seed):
     if not ok.value:
         return False, None
     return True, buf[: n.value].copy()
+
+
+def verify_many(proofs, seeds=None, expected_commitment=None):
+    """frieda_verify_many on the default context: one status byte per proof, verified in one call on the device."""
+    return default_context().verify_many(proofs, seeds, expected_commitment)
+
+
+def verify_samples_many(proofs, seeds=None, expected_commitment=None):
+    """frieda_verify_samples_many on the default context: (status, [positions or None])."""
+    return default_context().verify_samples_many(proofs, seeds, expected_commitment)
+
+
+def reconstruct_from_proofs(proofs, seeds, expected_commitment, n_bytes):
+    """frieda_reconstruct_from_proofs on the default context: (bytes, status, n_points)."""
+    return default_context().reconstruct_from_proofs(proofs, seeds, expected_commitment, n_bytes)

@@ -220,6 +220,13 @@ void batch_cut(uint32_t count, uint32_t per_call, uint32_t in_flight, std::vecto
 // the value of the 4 columns at position out_queries[i] of the bit-reversed codeword (src/proof.rs:62-66)
 int verify(const ProofData& proof, const uint64_t* seed, int* ok, std::vector<uint32_t>* out_queries = nullptr);
 
+// Many proofs in one call (verify_many.cpp, verify.hip): out_status[i] = a k::VerifyStatus, per proof the result of verify() whatever the
+// route (device passes for the shapes the kernel takes, from Tuning::verify_device_min eligible proofs on; verify() for the rest).
+// samples: an accepted proof must also hold one evaluation per distinct query (frieda_verify_samples), else VERIFY_INVARIANT;
+// positions (optional): the sampled positions of every accepted proof.  Uses the arena and the pinned block (callers: FR_NO_JOB).
+int verify_many(Ctx* ctx, const ProofData* const* proofs, const uint64_t* seeds, uint32_t count, const uint8_t* expected_commitment, bool samples,
+                uint8_t* out_status, std::vector<std::vector<uint32_t>>* positions);
+
 // transcript pieces shared by prover and verifier (transcript.cpp)
 void channel_mix_felts(Channel& ch, const std::vector<QM31>& felts);
 std::vector<uint32_t> generate_queries(Channel& ch, uint32_t log_domain_size, uint32_t n_queries);

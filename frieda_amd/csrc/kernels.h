@@ -48,6 +48,8 @@ struct Tuning {
     uint32_t tail_run_log = 9;           // FRIEDA_TAIL_RUN_LOG: layers of more than 2^v points use the multi-workgroup kernels
     bool host_decommit = false;          // FRIEDA_HOST_DECOMMIT: openings by the host planner + gather launch
     bool gather_copy = false;            // FRIEDA_GATHER_COPY: fallback path stages lists and results through device memory + copies
+    uint32_t verify_device_min = 1;      // FRIEDA_VERIFY_DEVICE_MIN: frieda_verify_many* use the device from this many device-eligible proofs per call
+                                         // (0: always; 1 is the starting value, the device route is not measured yet: profiles/r09_verify_many.txt)
     uint32_t open_small_max = 512;       // FRIEDA_OPEN_SMALL_MAX: largest position list frieda_merkle_decommit* opens in one workgroup (0: every list multi-block)
     uint32_t test_grind_first_log = 0;   // test hook (frieda_ctx_test_set_grind_first_log): a short first nonce range (0 = off)
     // batch policy (host.h, "batch policy"): workspace bytes a batched call may keep in flight, and the fewest calls a context gets
@@ -342,6 +344,30 @@ struct DecommitArgs {
     uint32_t first_shared, skip_log0;
 };
 void decommit(const Launch& L, const DecommitArgs& a, uint32_t wgs_per_blob);
+
+// ---- verify.hip: many proofs verified in one launch (frieda_verify_many) ----
+// The packed image of a pass: n_proofs VerifyHeaders, then every proof's words at img + off_words: a table of 4 words per layer (first
+// layer, then the inner ones: QM31s of fri_witness, hashes of hash_witness, words of column_witness, word offset of the layer's data =
+// commitment (8 words) | fri_witness | hash_witness), then the layers, the last-layer polynomial and the evaluations.  All offsets
+// are relative to the proof's first word and describe exactly what the image holds.
+constexpr uint32_t VERIFY_MAX_QUERIES = DECOMMIT_MAX_QUERIES;
+enum VerifyStatus : uint32_t { VERIFY_REJECTED = 0, VERIFY_ACCEPTED = 1, VERIFY_INVARIANT = 2, VERIFY_WRONG_COMMITMENT = 3 };
+struct VerifyHeader {
+    uint32_t off_words;  // of the proof's words, from the start of the image
+    uint32_t n, n_inner, n_queries, pow_bits;
+    uint32_t has_seed, seed_lo, seed_hi, nonce_lo, nonce_hi;
+    uint32_t n_last, n_evals;  // QM31 counts
+    uint32_t off_last, off_evals;
+    uint32_t pad_[2];
+};
+struct VerifyArgs {
+    const uint32_t* img;
+    uint32_t* out;   // per proof 2 + q_cap words: status, number of distinct queries, the queries (ascending)
+    uint32_t q_cap;  // >= 64, a power of two, >= every proof's n_queries
+};
+size_t verify_many_lds_bytes(uint32_t q_cap);
+hipError_t verify_many_init(const CPoint (&gen_pow2)[31]);  // uploads the generator's doublings (once per device)
+void verify_many(const Launch& L, const VerifyArgs& a, uint32_t n_proofs);
 
 // ---- opening.hip: Level B openings (frieda_dev_gather*, frieda_merkle_decommit*) ----
 constexpr uint32_t OPEN_BAD_WORD = 0xFFFFFFFFu;   // gathered word of an out-of-range index (device forms only; not a canonical M31)

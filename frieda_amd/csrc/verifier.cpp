@@ -4,8 +4,9 @@
 // FriFirstLayerVerifier / FriInnerLayerVerifier::verify_and_fold, SparseEvaluation::{fold_circle, fold_line}),
 // core/vcs/verifier.rs (MerkleVerifier::verify), core/queries.rs and core/poly/line.rs
 // (LinePoly::eval_at_point).  PARITY UNPINNED beyond the reference's own accept / reject tests
-// (src/proof.rs:136-193).  The reference verifier is O(n_queries * log N) hashes — microseconds — so it stays on the
-// host by design; there is no device code on this path.
+// (src/proof.rs:136-193).  The reference verifier is O(n_queries * log N) hashes: 0.24 - 0.66 ms per proof on one core
+// (profiles/r09_verify_many.txt).  This file is the one-proof host path and the reference of the batched device verifier
+// (verify.hip, verify_many.cpp), which must give this function's result for every proof.
 #include <algorithm>
 #include <string.h>
 

@@ -1,0 +1,386 @@
+// verify.hip — many proofs verified in one launch (gfx950): the device restatement of verifier.cpp::verify.
+//
+// One wave (a 64-thread workgroup) per proof.  The proof arrives as a packed image of 32-bit words (VerifyHeader + layer table +
+// data, built by verify_many.cpp); the wave
+//   1. replays the transcript (init, optional mix_u64(seed), per layer mix_root + draw_felt, mix_felts(last_layer_poly),
+//      mix_u64(nonce), the trailing-zeros test),
+//   2. draws the queries (independent draws, one per lane), sorts and de-duplicates them (as decommit.hip),
+//   3. walks the layers: with U_li = unique(queries >> li) the positions of layer li, every pair {2v, 2v + 1}, v in U_{li+1}, takes its
+//      members from the running values or — the index is a prefix count of "not queried" (ballot + popcount) — from fri_witness,
+//      folds it with the layer's alpha, and
+//   4. hashes the pair's two leaves and their parent, then walks the tree level by level: the nodes of a level are unique(positions
+//      >> s), a child that was not computed below comes from hash_witness at the prefix count of the missing children (the E_s tables
+//      of decommit.hip, read from the verifier's side), and the root is compared with the layer's commitment.
+// Every list lives in LDS and is compacted in place: entry k of a level is written after the entries >= k of the level below were
+// read (a wave executes its LDS accesses in program order), the neighbour below a 64-entry chunk is carried in a register.
+//
+// Every count of the image is checked arithmetically before a word is read through it (witness too short / too long, too few
+// evaluations, a non-empty column witness), so a malformed proof never reads outside its own image.
+#include <hip/hip_runtime.h>
+
+#include "dev_transcript.h"
+#include "kernels.h"
+#include "tree_dev.h"
+
+namespace frieda {
+namespace k {
+
+namespace {
+
+constexpr uint32_t LAST_LOG_MAX = 11;  // log2 of DT_MAX_LAST_POLY
+static_assert((1u << LAST_LOG_MAX) == DT_MAX_LAST_POLY, "the last-layer fold keeps one stack entry per bit of a coefficient index");
+
+__constant__ CPoint c_gen_pow2[31];  // 2^b * G of the circle group's generator (host: point_from_index)
+
+__device__ __forceinline__ CPoint dev_point_from_index(uint32_t index) {
+    CPoint res{1, 0};
+    index &= 0x7fffffffu;
+    for (uint32_t b = 0; index; b++, index >>= 1)
+        if (index & 1u) res = cp_add(res, c_gen_pow2[b]);
+    return res;
+}
+
+// point index of entry `i` of line_coset(n, n - li) (li = 0: Coset::half_odds(n - 1) itself)
+__device__ __forceinline__ uint32_t coset_index(uint32_t n, uint32_t doublings, uint32_t i) {
+    const unsigned long long init = (1ull << (30 - n)) << doublings, step = (1ull << (32 - n)) << doublings;
+    return (uint32_t)((init + step * i) & 0x7fffffffull);
+}
+
+struct Group {
+    bool first, miss, has_l, has_r;
+    uint32_t x, k, w;
+};
+
+// One 64-entry chunk of a level: lane `lane` looks at entry i = i0 + lane of the ascending list p[0 .. c).  The first entry of every
+// parent group (x >> 1) owns the group: k = its index in the next level, w = the index of its missing child among the missing children
+// of the level (a group misses at most one).  `carry`: the entry below the chunk (valid for i0 > 0).
+__device__ __forceinline__ Group group_of(const uint32_t* p, uint32_t c, uint32_t i0, uint32_t lane, uint32_t carry, uint32_t& kbase, uint32_t& wbase) {
+    const unsigned long long lt_mask = (1ull << lane) - 1;
+    const uint32_t i = i0 + lane;
+    Group g;
+    g.x = i < c ? p[i] : 0u;
+    const uint32_t prev = lane == 0 ? carry : p[i < c ? i - 1 : 0];
+    const uint32_t next = i + 1 < c ? p[i + 1] : 0xFFFFFFFFu;
+    g.first = i < c && (i == 0 || (prev >> 1) != (g.x >> 1));
+    g.has_l = !(g.x & 1u);
+    g.has_r = (g.x & 1u) || next == g.x + 1;
+    g.miss = g.first && !(g.has_l && g.has_r);
+    const unsigned long long mf = __ballot(g.first), mm = __ballot(g.miss);
+    g.k = kbase + (uint32_t)__popcll(mf & lt_mask);
+    g.w = wbase + (uint32_t)__popcll(mm & lt_mask);
+    kbase += (uint32_t)__popcll(mf);
+    wbase += (uint32_t)__popcll(mm);
+    return g;
+}
+
+__device__ __forceinline__ QM31 load_qm(const uint32_t* p) { return QM31{p[0], p[1], p[2], p[3]}; }
+
+__global__ __launch_bounds__(64) void verify_many_kernel(VerifyArgs a) {
+    extern __shared__ uint32_t lds[];
+    const uint32_t Q = a.q_cap;
+    uint32_t* s_pos = lds;           // positions of the current layer: U_li
+    uint32_t* s_hp = lds + Q;        // sort scratch, then the node positions of the Merkle walk
+    uint32_t* s_ev = lds + 2 * Q;    // the current layer's values at s_pos, 4 words each
+    uint32_t* s_h = lds + 6 * Q;     // node hashes of the Merkle walk, 8 words each
+    __shared__ uint32_t s_alpha[4 * DT_MAX_LAYERS];
+    __shared__ uint32_t s_digest[8];
+    __shared__ uint32_t s_misc[2];
+
+    const uint32_t lane = threadIdx.x, slot = blockIdx.x;
+    const unsigned long long lt_mask = (1ull << lane) - 1;
+    const VerifyHeader hd = reinterpret_cast<const VerifyHeader*>(a.img)[slot];
+    const uint32_t* img = a.img + hd.off_words;
+    uint32_t* out = a.out + (size_t)slot * (2 + a.q_cap);
+    const uint32_t n = hd.n, nl = hd.n_inner, nq = hd.n_queries;
+    const uint32_t* tab = img;  // per layer: n_fri_witness, n_hash_witness, n_column_witness, offset of the layer's words
+    const uint32_t* last_poly = img + hd.off_last;
+    const uint32_t* evals = img + hd.off_evals;
+    const uint32_t np = hd.n_last;
+
+#define VK_FINISH(st)                  \
+    do {                               \
+        if (lane == 0) out[0] = (st);  \
+        return;                        \
+    } while (0)
+
+    // ---- 1. the transcript: every lane computes the same chain; lane 0 keeps the alphas ----
+    {
+        Channel ch;
+        ch.init();
+        if (hd.has_seed) ch.mix_u64((uint64_t)hd.seed_lo | ((uint64_t)hd.seed_hi << 32));
+        for (uint32_t li = 0; li <= nl; li++) {
+            const uint32_t* c = img + tab[4 * li + 3];
+            uint32_t w[8];
+#pragma unroll
+            for (int i = 0; i < 8; i++) w[i] = c[i];
+            ch.mix_root(w);
+            const QM31 al = ch.draw_felt();
+            if (lane == 0) s_alpha[4 * li] = al.a, s_alpha[4 * li + 1] = al.b, s_alpha[4 * li + 2] = al.c, s_alpha[4 * li + 3] = al.d;
+        }
+        // Blake2sChannel::mix_felts: blake2s256(digest || the words of every coefficient), streamed from the image
+        {
+            const uint32_t n_words = 8 + 4 * np, len = 4 * n_words;
+            uint32_t h[8], nx[8], m[16];
+#pragma unroll
+            for (int i = 0; i < 8; i++) h[i] = b2detail::IV[i];
+            h[0] ^= 0x01010020u;
+            uint32_t off = 0;  // words
+            while (len - 4 * off > 64) {
+#pragma unroll
+                for (int i = 0; i < 16; i++) m[i] = (off == 0 && i < 8) ? ch.digest[i & 7] : last_poly[off + i - 8];
+                b2_compress(h, m, 4 * off + 64, 0, 0, 0, nx);
+#pragma unroll
+                for (int i = 0; i < 8; i++) h[i] = nx[i];
+                off += 16;
+            }
+#pragma unroll
+            for (int i = 0; i < 16; i++) m[i] = (off == 0 && i < 8) ? ch.digest[i & 7] : (off + i < n_words ? last_poly[off + i - 8] : 0u);
+            b2_compress(h, m, len, 0, 0xFFFFFFFFu, 0, nx);
+            ch.update_digest(nx);
+        }
+        ch.mix_u64((uint64_t)hd.nonce_lo | ((uint64_t)hd.nonce_hi << 32));
+        if (ch.trailing_zeros() < hd.pow_bits) VK_FINISH(VERIFY_REJECTED);
+        if (lane == 0) {
+#pragma unroll
+            for (int i = 0; i < 8; i++) s_digest[i] = ch.digest[i];
+        }
+    }
+    __syncthreads();
+
+    // ---- 2. Queries::generate, sorted and de-duplicated into s_pos (decommit.hip) ----
+    uint32_t nu;
+    {
+        const uint32_t mask = (1u << n) - 1;
+        uint32_t P = 2;
+        while (P < nq) P <<= 1;
+        for (uint32_t d = lane; d < (nq + 7) / 8; d += 64) {
+            uint32_t w[16], r[8], h0[8];
+#pragma unroll
+            for (int i = 0; i < 8; i++) w[i] = s_digest[i], w[8 + i] = 0, h0[i] = b2detail::IV[i];
+            w[8] = d;
+            h0[0] ^= 0x01010020u;
+            b2_compress(h0, w, 64, 0, 0xFFFFFFFFu, 0, r);
+#pragma unroll
+            for (int j = 0; j < 8; j++)
+                if (8 * d + j < nq) s_hp[8 * d + j] = r[j] & mask;
+        }
+        for (uint32_t i = nq + lane; i < P; i += 64) s_hp[i] = 0xFFFFFFFFu;
+        __syncthreads();
+        if (P <= 64) {
+            const uint32_t v = s_hp[lane < P ? lane : 0];
+            uint32_t rank = 0;
+#pragma unroll
+            for (int j = 0; j < 64; j++) {
+                const uint32_t o = (uint32_t)__builtin_amdgcn_readlane((int)v, j);
+                rank += ((uint32_t)j < P && (o < v || (o == v && (uint32_t)j < lane))) ? 1u : 0u;
+            }
+            __syncthreads();
+            if (lane < P) s_hp[rank] = v;
+            __syncthreads();
+            const uint32_t x = s_hp[lane < P ? lane : 0], prev = s_hp[lane > 0 && lane < P ? lane - 1 : 0];
+            const bool first = lane < nq && (lane == 0 || x != prev);
+            const unsigned long long m = __ballot(first);
+            if (first) s_pos[__popcll(m & lt_mask)] = x;
+            nu = (uint32_t)__popcll(m);
+        } else {
+            for (uint32_t k2 = 2; k2 <= P; k2 <<= 1) {
+                for (uint32_t j = k2 >> 1; j > 0; j >>= 1) {
+                    for (uint32_t i = lane; i < P; i += 64) {
+                        const uint32_t ixj = i ^ j;
+                        if (ixj > i) {
+                            const uint32_t x = s_hp[i], y = s_hp[ixj];
+                            const bool asc = (i & k2) == 0;
+                            if ((x > y) == asc) {
+                                s_hp[i] = y;
+                                s_hp[ixj] = x;
+                            }
+                        }
+                    }
+                    __syncthreads();
+                }
+            }
+            nu = 0;
+            for (uint32_t i0 = 0; i0 < nq; i0 += 64) {
+                const uint32_t i = i0 + lane;
+                const bool first = i < nq && (i == 0 || s_hp[i] != s_hp[i - 1]);
+                const unsigned long long m = __ballot(first);
+                if (first) s_pos[nu + (uint32_t)__popcll(m & lt_mask)] = s_hp[i];
+                nu += (uint32_t)__popcll(m);
+            }
+        }
+        __syncthreads();
+        for (uint32_t i = lane; i < nu; i += 64) out[2 + i] = s_pos[i];
+        if (lane == 0) out[1] = nu;
+    }
+
+    // ---- 3 + 4. the layers ----
+    const uint32_t ne = hd.n_evals;
+    for (uint32_t i = lane; i < 4 * nu; i += 64) s_ev[i] = i < 4 * ne ? evals[i] : 0u;  // (too few evaluations: decided below, nothing is read past them)
+    if (lane == 0) s_misc[0] = 0xFFFFFFFFu;
+    __syncthreads();
+    const uint32_t eval_fail_pos = ne < nu ? s_pos[ne] : 0u;  // the query at which the reference runs out of evaluations
+    uint32_t c = nu;  // |U_li|
+    for (uint32_t li = 0; li <= nl; li++) {
+        const uint32_t m = n - li;  // log size of the layer
+        const uint32_t nw = tab[4 * li], nh = tab[4 * li + 1], ncw = tab[4 * li + 2];
+        const uint32_t* lay = img + tab[4 * li + 3];
+        const uint32_t* wit = lay + 8;
+        const uint32_t* hw = wit + 4 * (size_t)nw;
+        const QM31 alpha = load_qm(s_alpha + 4 * li);
+        bool bad = false;
+        uint32_t kbase = 0, wbase = 0, carry = 0;
+        for (uint32_t i0 = 0; i0 < c; i0 += 64) {
+            const Group g = group_of(s_pos, c, i0, lane, carry, kbase, wbase);
+            const uint32_t i = i0 + lane;
+            QM31 l{0, 0, 0, 0}, r{0, 0, 0, 0};
+            if (g.first) {
+                QM31 wv{0, 0, 0, 0};
+                if (g.miss) {
+                    if (g.w < nw)
+                        wv = load_qm(wit + 4 * (size_t)g.w);
+                    else
+                        bad = true;  // InsufficientWitness
+                    if (li == 0 && g.w == nw) s_misc[0] = g.x ^ 1u;  // the position at which the reference runs out of witness
+                }
+                const QM31 own = load_qm(s_ev + 4 * i);
+                l = g.has_l ? own : wv;
+                r = (g.x & 1u) ? own : (g.has_r ? load_qm(s_ev + 4 * (i + 1)) : wv);
+            }
+            carry = (uint32_t)__shfl((int)g.x, 63);
+            __syncthreads();
+            if (g.first) {
+                const uint32_t v = g.x >> 1;
+                // the pair's two leaves and their parent: node v of level m - 1
+                uint32_t hl[8], hr[8], mm[16], hp[8];
+                treedev::leaf_hash<B2_LAT>(l.a, l.b, l.c, l.d, hl);
+                treedev::leaf_hash<B2_LAT>(r.a, r.b, r.c, r.d, hr);
+#pragma unroll
+                for (int w = 0; w < 8; w++) mm[w] = hl[w], mm[8 + w] = hr[w];
+                b2_merkle_block<B2_LAT>(mm, hp);
+#pragma unroll
+                for (int w = 0; w < 8; w++) s_h[8 * g.k + w] = hp[w];
+                s_hp[g.k] = v;
+                // fold: the twiddle is the inverse of the domain point's y (circle layer) or x (line layers) at bit_reverse(2 v)
+                const CPoint pt = dev_point_from_index(coset_index(n, li ? li - 1 : 0, bit_reverse(2 * v, m)));
+                const uint32_t it = m31_inv(li ? pt.x : pt.y);
+                const QM31 f0 = qm_add(l, r), f1 = qm_scale(qm_sub(l, r), it);
+                const QM31 f = qm_add(f0, qm_mul(alpha, f1));
+                s_pos[g.k] = v;
+                s_ev[4 * g.k] = f.a, s_ev[4 * g.k + 1] = f.b, s_ev[4 * g.k + 2] = f.c, s_ev[4 * g.k + 3] = f.d;
+            }
+            __syncthreads();
+        }
+        if (li == 0 && ne < nu) {
+            // QueryEvalsExhausted (the reference panics) unless the witness ran out at a smaller position first
+            const uint32_t wit_fail_pos = s_misc[0];
+            if (!(wbase > nw && wit_fail_pos < eval_fail_pos)) VK_FINISH(VERIFY_INVARIANT);
+        }
+        if (__any(bad) || wbase != nw || ncw != 0) VK_FINISH(VERIFY_REJECTED);
+        c = kbase;  // |U_{li+1}|: the nodes of level m - 1
+        // ---- the Merkle walk of this layer: levels m - 2 .. 0 ----
+        uint32_t cn = c, hbase = 0;
+        for (uint32_t lv = m - 1; lv > 0; lv--) {
+            uint32_t kb = 0, cr = 0;
+            for (uint32_t i0 = 0; i0 < cn; i0 += 64) {
+                const Group g = group_of(s_hp, cn, i0, lane, cr, kb, hbase);
+                const uint32_t i = i0 + lane;
+                uint32_t mm[16];
+                if (g.first) {
+                    const bool wok = !g.miss || g.w < nh;
+                    if (!wok) bad = true;  // WitnessTooShort
+                    const uint32_t* wsrc = hw + 8 * (size_t)(wok && g.miss ? g.w : 0);
+                    const uint32_t* own = s_h + 8 * i;
+                    const uint32_t* nxt = s_h + 8 * (g.has_l && g.has_r ? i + 1 : i);
+#pragma unroll
+                    for (int w = 0; w < 8; w++) {
+                        const uint32_t wv = (g.miss && wok) ? wsrc[w] : 0u;
+                        mm[w] = g.has_l ? own[w] : wv;
+                        mm[8 + w] = (g.x & 1u) ? own[w] : (g.has_r ? nxt[w] : wv);
+                    }
+                }
+                cr = (uint32_t)__shfl((int)g.x, 63);
+                __syncthreads();
+                if (g.first) {
+                    uint32_t hp[8];
+                    b2_merkle_block<B2_LAT>(mm, hp);
+#pragma unroll
+                    for (int w = 0; w < 8; w++) s_h[8 * g.k + w] = hp[w];
+                    s_hp[g.k] = g.x >> 1;
+                }
+                __syncthreads();
+            }
+            cn = kb;
+            if (__any(bad)) VK_FINISH(VERIFY_REJECTED);
+        }
+        if (hbase != nh || cn != 1) VK_FINISH(VERIFY_REJECTED);  // WitnessTooLong
+        {
+            const bool diff = lane < 8 && s_h[lane] != lay[lane];
+            if (__any(diff)) VK_FINISH(VERIFY_REJECTED);
+        }
+        if (nl == 0) VK_FINISH(VERIFY_INVARIANT);  // assert!(first_layer_columns.is_empty()) upstream
+        __syncthreads();
+    }
+
+    // ---- decommit_last_layer: LinePoly::eval_at_point at every remaining position ----
+    if (np == 0 || (np & (np - 1))) VK_FINISH(VERIFY_REJECTED);
+    {
+        const uint32_t plog = 31 - (uint32_t)__clz((int)np);
+        const uint32_t ml = n - nl - 1;
+        bool bad = false;
+        for (uint32_t i = lane; i < c; i += 64) {
+            const uint32_t x = dev_point_from_index(coset_index(n, nl, bit_reverse(s_pos[i], ml))).x;
+            // fold(coeffs, doublings) of LinePoly::eval_at_point, bottom up in one pass over the coefficients: bit b of a coefficient's
+            // index carries x doubled (plog - 1 - b) times; stk[b] holds the folded left half of an open 2^(b+1) block.  j is uniform
+            // over the wave, so the branches are scalar and the arrays stay in registers: np - 1 QM31 scalings per position.
+            uint32_t fb[LAST_LOG_MAX];
+            {
+                uint32_t xx = x;
+#pragma unroll
+                for (uint32_t b = 0; b < LAST_LOG_MAX; b++) fb[b] = 0;
+#pragma unroll
+                for (uint32_t d = 0; d < LAST_LOG_MAX; d++) {
+#pragma unroll
+                    for (uint32_t b = 0; b < LAST_LOG_MAX; b++)
+                        if (b + d + 1 == plog) fb[b] = xx;
+                    xx = double_x(xx);
+                }
+            }
+            QM31 stk[LAST_LOG_MAX], acc{0, 0, 0, 0};
+#pragma unroll
+            for (uint32_t b = 0; b < LAST_LOG_MAX; b++) stk[b] = QM31{0, 0, 0, 0};
+            for (uint32_t j = 0; j < np; j++) {
+                acc = load_qm(last_poly + 4 * (size_t)j);
+                bool open = true;
+#pragma unroll
+                for (uint32_t b = 0; b < LAST_LOG_MAX; b++) {
+                    if (open) {
+                        if ((j >> b) & 1u) {
+                            acc = qm_add(stk[b], qm_scale(acc, fb[b]));
+                        } else {
+                            stk[b] = acc;
+                            open = false;
+                        }
+                    }
+                }
+            }
+            if (!qm_eq(acc, load_qm(s_ev + 4 * i))) bad = true;  // LastLayerEvaluationsInvalid
+        }
+        if (__any(bad)) VK_FINISH(VERIFY_REJECTED);
+    }
+    VK_FINISH(VERIFY_ACCEPTED);
+#undef VK_FINISH
+}
+
+}  // namespace
+
+size_t verify_many_lds_bytes(uint32_t q_cap) { return sizeof(uint32_t) * 14 * (size_t)q_cap; }
+
+hipError_t verify_many_init(const CPoint (&gen_pow2)[31]) { return hipMemcpyToSymbol(HIP_SYMBOL(c_gen_pow2), gen_pow2, sizeof(gen_pow2)); }
+
+void verify_many(const Launch& L, const VerifyArgs& a, uint32_t n_proofs) {
+    Scope scope(L, "verify_many", 0.0);
+    verify_many_kernel<<<dim3(n_proofs), 64, verify_many_lds_bytes(a.q_cap), L.stream>>>(a);
+}
+
+}  // namespace k
+}  // namespace frieda

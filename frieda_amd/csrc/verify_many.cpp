@@ -1,0 +1,310 @@
+// verify_many.cpp — frieda_verify_many / frieda_verify_samples_many / frieda_reconstruct_from_proofs: the host side of verify.hip.
+//
+// Per proof the result is that of verifier.cpp::verify, whatever the route.  The checks that hash nothing and that the reference makes
+// before anything else run here (the L, L + B range, InvalidNumFriLayers, LastLayerDegreeInvalid): such a proof has its status without
+// being sent.  (The power-of-two rule of the last layer and the empty inner_layers assertion come AFTER the first layer's checks in the
+// reference — a proof that is also short of evaluations panics first — so the kernel applies them, in the reference's order.)  Proofs of
+// a shape the kernel does not take (more than VERIFY_MAX_QUERIES queries, a last layer above DT_MAX_LAST_POLY, more than DT_MAX_LAYERS
+// layers, no queries at all) go through verify() inside the same call.  The rest is flattened into the context's pinned staging block
+// in passes bounded by PASS_BYTES — header, layer table, words — uploaded, verified by one launch per pass, and one status word and
+// the sampled positions per proof come back.
+#include <string.h>
+
+#include <algorithm>
+#include <unordered_map>
+
+#include "dev_transcript.h"
+#include "host.h"
+
+namespace frieda {
+
+namespace {
+
+constexpr size_t PASS_BYTES = (size_t)32 << 20;  // staging budget of one upload (a lone larger proof is a pass of its own)
+
+size_t image_words(const ProofData& p) {
+    size_t w = 4 * (p.inner_layers.size() + 1);
+    auto layer = [](const LayerProof& l) { return 8 + 4 * l.fri_witness.size() + 8 * l.hash_witness.size(); };
+    w += layer(p.first_layer);
+    for (const LayerProof& l : p.inner_layers) w += layer(l);
+    return w + 4 * p.last_layer_poly.size() + 4 * p.evaluations.size();
+}
+
+void pack_layer(const LayerProof& l, uint32_t* base, uint32_t* tab, size_t& off) {
+    tab[0] = (uint32_t)l.fri_witness.size();
+    tab[1] = (uint32_t)l.hash_witness.size();
+    tab[2] = (uint32_t)l.column_witness.size();
+    tab[3] = (uint32_t)off;
+    memcpy(base + off, l.commitment.data(), 32);
+    off += 8;
+    if (!l.fri_witness.empty()) memcpy(base + off, l.fri_witness.data(), 16 * l.fri_witness.size());
+    off += 4 * l.fri_witness.size();
+    if (!l.hash_witness.empty()) memcpy(base + off, l.hash_witness.data(), 32 * l.hash_witness.size());
+    off += 8 * l.hash_witness.size();
+}
+
+void pack_proof(const ProofData& p, const uint64_t* seed, uint32_t* base, k::VerifyHeader& h, size_t off_words) {
+    memset(&h, 0, sizeof h);
+    h.off_words = (uint32_t)off_words;
+    h.n = p.log_size_bound + p.pcs_config.log_blowup_factor;
+    h.n_inner = (uint32_t)p.inner_layers.size();
+    h.n_queries = p.pcs_config.n_queries;
+    h.pow_bits = p.pcs_config.pow_bits;
+    h.has_seed = seed ? 1u : 0u;
+    h.seed_lo = seed ? (uint32_t)*seed : 0u;
+    h.seed_hi = seed ? (uint32_t)(*seed >> 32) : 0u;
+    h.nonce_lo = (uint32_t)p.proof_of_work;
+    h.nonce_hi = (uint32_t)(p.proof_of_work >> 32);
+    h.n_last = (uint32_t)p.last_layer_poly.size();
+    h.n_evals = (uint32_t)p.evaluations.size();
+    size_t off = 4 * (p.inner_layers.size() + 1);
+    pack_layer(p.first_layer, base, base, off);
+    for (size_t i = 0; i < p.inner_layers.size(); i++) pack_layer(p.inner_layers[i], base, base + 4 * (i + 1), off);
+    h.off_last = (uint32_t)off;
+    if (h.n_last) memcpy(base + off, p.last_layer_poly.data(), 16 * (size_t)h.n_last);
+    off += 4 * (size_t)h.n_last;
+    h.off_evals = (uint32_t)off;
+    if (h.n_evals) memcpy(base + off, p.evaluations.data(), 16 * (size_t)h.n_evals);
+}
+
+// the checks of verify() that precede every hash; true: `status` is final
+bool structural_status(const ProofData& p, uint8_t& status) {
+    const uint32_t B = p.pcs_config.log_blowup_factor, last = p.pcs_config.log_last_layer_degree_bound, L = p.log_size_bound;
+    if (L < 1 || (uint64_t)L + B < 2 || (uint64_t)L + B > 30) {
+        status = k::VERIFY_INVARIANT;
+        return true;
+    }
+    status = k::VERIFY_REJECTED;
+    uint32_t bound = L - 1;
+    for (size_t i = 0; i < p.inner_layers.size(); i++) {
+        if (bound < 1) return true;  // InvalidNumFriLayers
+        bound -= 1;
+    }
+    if (bound != last) return true;
+    if (p.last_layer_poly.size() > ((size_t)1 << last)) return true;  // LastLayerDegreeInvalid
+    return false;
+}
+
+bool device_shape(const ProofData& p) {
+    const uint32_t nq = p.pcs_config.n_queries;
+    return nq >= 1 && nq <= k::VERIFY_MAX_QUERIES && p.last_layer_poly.size() <= DT_MAX_LAST_POLY && p.inner_layers.size() + 1 <= DT_MAX_LAYERS &&
+           image_words(p) < ((size_t)1 << 30);
+}
+
+void host_route(const ProofData& p, const uint64_t* seed, bool samples, uint8_t& status, std::vector<uint32_t>* pos) {
+    int ok = 0;
+    std::vector<uint32_t> q;
+    const int rc = verify(p, seed, &ok, &q);
+    if (rc != FRIEDA_OK)
+        status = k::VERIFY_INVARIANT;
+    else if (!ok)
+        status = k::VERIFY_REJECTED;
+    else if (samples && q.size() != p.evaluations.size())
+        status = k::VERIFY_INVARIANT;  // frieda_verify_samples: an accepted proof has one evaluation per distinct query
+    else
+        status = k::VERIFY_ACCEPTED;
+    if (pos && status == k::VERIFY_ACCEPTED) *pos = std::move(q);
+}
+
+int init_device_tables(Ctx* ctx) {
+    static std::mutex mu;
+    static std::vector<int> done;
+    std::lock_guard<std::mutex> g(mu);
+    if (std::find(done.begin(), done.end(), ctx->device) != done.end()) return FRIEDA_OK;
+    CPoint t[31];
+    for (uint32_t b = 0; b < 31; b++) t[b] = point_from_index(1u << b);
+    FR_HIP(ctx, k::verify_many_init(t));
+    done.push_back(ctx->device);
+    return FRIEDA_OK;
+}
+
+}  // namespace
+
+int verify_many(Ctx* ctx, const ProofData* const* proofs, const uint64_t* seeds, uint32_t count, const uint8_t* expected_commitment, bool samples,
+                uint8_t* out_status, std::vector<std::vector<uint32_t>>* positions) {
+    if (positions) positions->assign(count, {});
+    std::vector<uint32_t> dev;  // indices of the proofs the kernel takes
+    std::vector<uint32_t> host;
+    for (uint32_t i = 0; i < count; i++) {
+        const ProofData& p = *proofs[i];
+        if (expected_commitment && memcmp(p.first_layer.commitment.data(), expected_commitment, 32) != 0) {
+            out_status[i] = k::VERIFY_WRONG_COMMITMENT;
+            continue;
+        }
+        if (structural_status(p, out_status[i])) continue;
+        (device_shape(p) ? dev : host).push_back(i);
+    }
+    if (dev.size() < ctx->tuning.verify_device_min || dev.empty()) {
+        host.insert(host.end(), dev.begin(), dev.end());
+        dev.clear();
+    }
+    for (uint32_t i : host) host_route(*proofs[i], seeds ? seeds + i : nullptr, samples, out_status[i], positions ? &(*positions)[i] : nullptr);
+    if (dev.empty()) return FRIEDA_OK;
+
+    FR_HIP(ctx, hipSetDevice(ctx->device));
+    int rc = init_device_tables(ctx);
+    if (rc) return rc;
+    hipStream_t s = ctx->stream;
+    const size_t hdr_words = sizeof(k::VerifyHeader) / 4;
+    for (size_t first = 0; first < dev.size();) {
+        // the proofs of this pass
+        size_t end = first, words = 0;
+        uint32_t q_cap = 64;
+        while (end < dev.size()) {
+            const size_t w = hdr_words + image_words(*proofs[dev[end]]);
+            if (end > first && 4 * (words + w) > PASS_BYTES) break;
+            words += w;
+            while (q_cap < proofs[dev[end]]->pcs_config.n_queries) q_cap <<= 1;
+            end++;
+        }
+        const size_t np = end - first, in_bytes = (4 * words + 255) & ~(size_t)255, out_bytes = 4 * np * (2 + (size_t)q_cap);
+        if (words >= ((size_t)1 << 32)) return ctx->fail(FRIEDA_ERR_ARG, "verify_many: one proof beyond 2^32 words");
+        ArenaPlan ap;
+        const size_t a_in = ap.take(in_bytes), a_out = ap.take(out_bytes);
+        rc = ctx->ensure_arena(ap.off);
+        if (rc) return rc;
+        rc = ensure_pinned(ctx, in_bytes + out_bytes);
+        if (rc) return rc;
+        uint32_t* pin = static_cast<uint32_t*>(ctx->pinned);
+        k::VerifyHeader* hdr = reinterpret_cast<k::VerifyHeader*>(pin);
+        size_t off = hdr_words * np;
+        for (size_t j = 0; j < np; j++) {
+            const uint32_t i = dev[first + j];
+            pack_proof(*proofs[i], seeds ? seeds + i : nullptr, pin + off, hdr[j], off);
+            off += image_words(*proofs[i]);
+        }
+        FR_HIP(ctx, hipMemcpyAsync(ctx->arena + a_in, pin, 4 * words, hipMemcpyHostToDevice, s));
+        k::VerifyArgs va;
+        va.img = reinterpret_cast<const uint32_t*>(ctx->arena + a_in);
+        va.out = reinterpret_cast<uint32_t*>(ctx->arena + a_out);
+        va.q_cap = q_cap;
+        k::verify_many(ctx->launch(), va, (uint32_t)np);
+        FR_HIP(ctx, hipGetLastError());
+        uint32_t* res = pin + in_bytes / 4;
+        FR_HIP(ctx, hipMemcpyAsync(res, ctx->arena + a_out, out_bytes, hipMemcpyDeviceToHost, s));
+        FR_HIP(ctx, hipStreamSynchronize(s));
+        for (size_t j = 0; j < np; j++) {
+            const uint32_t i = dev[first + j];
+            const uint32_t* r = res + j * (2 + (size_t)q_cap);
+            uint8_t st = (uint8_t)r[0];
+            if (r[0] > k::VERIFY_INVARIANT) return ctx->fail(FRIEDA_ERR_INVARIANT, "verify_many: the kernel left no status");
+            if (st == k::VERIFY_ACCEPTED && samples && r[1] != proofs[i]->evaluations.size()) st = k::VERIFY_INVARIANT;
+            out_status[i] = st;
+            if (positions && st == k::VERIFY_ACCEPTED) (*positions)[i].assign(r + 2, r + 2 + r[1]);
+        }
+        first = end;
+    }
+    return FRIEDA_OK;
+}
+
+}  // namespace frieda
+
+using namespace frieda;
+
+extern "C" {
+
+static int verify_many_common(frieda_ctx* ctx, const frieda_proof* const* proofs, const uint64_t* seeds, uint32_t count,
+                              const uint8_t* expected_commitment, bool samples, uint8_t* out_status, std::vector<std::vector<uint32_t>>* positions) {
+    if (!ctx) return FRIEDA_ERR_ARG;
+    if (count == 0) return FRIEDA_OK;
+    if (!proofs || !out_status) return FRIEDA_ERR_ARG;
+    for (uint32_t i = 0; i < count; i++)
+        if (!proofs[i]) return ctx->c.fail(FRIEDA_ERR_ARG, "null proof " + std::to_string(i));
+    FR_NO_JOB(&ctx->c);
+    FR_GUARD_BEGIN
+    std::vector<const ProofData*> ps(count);
+    for (uint32_t i = 0; i < count; i++) ps[i] = &proofs[i]->p;
+    return verify_many(&ctx->c, ps.data(), seeds, count, expected_commitment, samples, out_status, positions);
+    FR_GUARD_END(ctx)
+}
+
+int frieda_verify_many(frieda_ctx* ctx, const frieda_proof* const* proofs, const uint64_t* seeds, uint32_t count,
+                       const uint8_t* expected_commitment, uint8_t* out_status) {
+    return verify_many_common(ctx, proofs, seeds, count, expected_commitment, false, out_status, nullptr);
+}
+
+int frieda_verify_samples_many(frieda_ctx* ctx, const frieda_proof* const* proofs, const uint64_t* seeds, uint32_t count,
+                               const uint8_t* expected_commitment, uint8_t* out_status, uint32_t* out_positions, size_t pitch,
+                               uint32_t* out_n_positions) {
+    if (!ctx) return FRIEDA_ERR_ARG;
+    if (count == 0) return FRIEDA_OK;
+    if (!proofs || !out_status || !out_positions || !out_n_positions) return FRIEDA_ERR_ARG;
+    for (uint32_t i = 0; i < count; i++) {
+        if (!proofs[i]) return ctx->c.fail(FRIEDA_ERR_ARG, "null proof " + std::to_string(i));
+        if (pitch < proofs[i]->p.pcs_config.n_queries) return ctx->c.fail(FRIEDA_ERR_ARG, "pitch smaller than n_queries of proof " + std::to_string(i));
+    }
+    FR_GUARD_BEGIN
+    std::vector<std::vector<uint32_t>> pos;
+    const int rc = verify_many_common(ctx, proofs, seeds, count, expected_commitment, true, out_status, &pos);
+    if (rc != FRIEDA_OK) return rc;
+    for (uint32_t i = 0; i < count; i++) {
+        out_n_positions[i] = (uint32_t)pos[i].size();
+        if (!pos[i].empty()) memcpy(out_positions + (size_t)i * pitch, pos[i].data(), 4 * pos[i].size());
+    }
+    return FRIEDA_OK;
+    FR_GUARD_END(ctx)
+}
+
+int frieda_reconstruct_from_proofs(frieda_ctx* ctx, const frieda_proof* const* proofs, const uint64_t* seeds, uint32_t count,
+                                   const uint8_t expected_commitment[32], size_t len, uint8_t* out_bytes, uint8_t* out_status, size_t* n_points) {
+    if (!ctx || !proofs || !expected_commitment || !out_status || !n_points || count == 0 || (len && !out_bytes)) return FRIEDA_ERR_ARG;
+    *n_points = 0;
+    FR_GUARD_BEGIN
+    std::vector<std::vector<uint32_t>> pos;
+    int rc = verify_many_common(ctx, proofs, seeds, count, expected_commitment, true, out_status, &pos);
+    if (rc != FRIEDA_OK) return rc;
+    // pool the verified (position, evaluation) pairs: first occurrence of a position kept
+    bool have_shape = false;
+    uint32_t L = 0, B = 0;
+    std::vector<uint32_t> index, cells;
+    std::unordered_map<uint32_t, uint32_t> seen;
+    for (uint32_t i = 0; i < count; i++) {
+        if (out_status[i] != k::VERIFY_ACCEPTED) continue;
+        const ProofData& p = proofs[i]->p;
+        if (!have_shape) {
+            L = p.log_size_bound, B = p.pcs_config.log_blowup_factor;
+            have_shape = true;
+        } else if (p.log_size_bound != L || p.pcs_config.log_blowup_factor != B) {
+            *n_points = index.size();  // the points pooled before the proof that disagrees
+            return ctx->c.fail(FRIEDA_ERR_ARG, "accepted proofs disagree on the shape of the codeword");
+        }
+        for (size_t j = 0; j < pos[i].size(); j++) {
+            if (!seen.emplace(pos[i][j], (uint32_t)index.size()).second) continue;
+            index.push_back(pos[i][j]);
+            const QM31& e = p.evaluations[j];
+            cells.insert(cells.end(), {e.a, e.b, e.c, e.d});
+        }
+    }
+    *n_points = index.size();
+    if (!have_shape) return ctx->c.fail(FRIEDA_ERR_ARG, "no proof was accepted");
+    if (index.size() < ((size_t)1 << L) + 2)
+        return ctx->c.fail(FRIEDA_ERR_ARG, std::to_string(index.size()) + " distinct verified points, " + std::to_string(((size_t)1 << L) + 2) + " needed");
+    if ((8 * len + 29) / 30 > ((size_t)4 << L)) return ctx->c.fail(FRIEDA_ERR_ARG, "len does not fit the polynomial");
+    FR_HIP(&ctx->c, hipSetDevice(ctx->c.device));
+    void *d_cells = nullptr, *d_out = nullptr;
+    hipError_t e = hipMalloc(&d_cells, 4 * cells.size());
+    if (e == hipSuccess) e = hipMalloc(&d_out, len ? len : 1);
+    if (e != hipSuccess) {
+        if (d_cells) (void)hipFree(d_cells);
+        ctx->c.err = std::string("hipMalloc: ") + hipGetErrorString(e);
+        return FRIEDA_ERR_NOMEM;
+    }
+    std::vector<uint8_t> bytes(len);
+    rc = frieda_dev_upload(ctx, d_cells, cells.data(), 4 * cells.size());
+    if (rc == FRIEDA_OK)
+        rc = frieda_reconstruct_points_device(ctx, static_cast<const uint32_t*>(d_cells), index.data(), (uint32_t)index.size(), 0, L, L + B, len, d_out);
+    if (rc == FRIEDA_OK) rc = frieda_dev_download(ctx, bytes.data(), d_out, len);
+    (void)hipStreamSynchronize(ctx->c.stream);
+    (void)hipFree(d_cells);
+    (void)hipFree(d_out);
+    if (rc != FRIEDA_OK) return rc;
+    uint8_t root[32];
+    rc = commit_host(&ctx->c, bytes.data(), len, B, root);
+    if (rc != FRIEDA_OK) return rc;
+    if (memcmp(root, expected_commitment, 32) != 0) return ctx->c.fail(FRIEDA_ERR_ARG, "the rebuilt blob does not commit to expected_commitment (wrong len?)");
+    if (len) memcpy(out_bytes, bytes.data(), len);
+    return FRIEDA_OK;
+    FR_GUARD_END(ctx)
+}
+
+}  // extern "C"

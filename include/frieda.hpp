@@ -9,6 +9,7 @@
 // rejections return false.  Option<u64> is std::optional<uint64_t>.  A thread-local default context (device 0) backs the
 // free functions; construct frieda::Context for other devices / streams.
 #pragma once
+#include <algorithm>
 #include <array>
 #include <cstdint>
 #include <optional>
@@ -216,6 +217,61 @@ class Context {
               h_);
         std::vector<uint8_t> out(len);
         if (len) check(frieda_dev_download(h_, out.data(), d_out.ptr, len), h_);
+        return out;
+    }
+    // Many proofs verified in one call on the GPU (frieda_verify_many): one status byte per proof — FRIEDA_VERIFY_REJECTED, FRIEDA_VERIFY_ACCEPTED,
+    // FRIEDA_VERIFY_INVARIANT (api::verify would throw Panic), FRIEDA_VERIFY_WRONG_COMMITMENT — each what api::verify gives for that proof.
+    // seeds: empty (None for all) or one per proof; expected_commitment: optional.
+    std::vector<uint8_t> verify_many(const std::vector<const Proof*>& proofs, const std::vector<uint64_t>& seeds = {},
+                                     const Commitment* expected_commitment = nullptr) {
+        std::vector<uint8_t> status(proofs.size());
+        if (proofs.empty()) return status;
+        if (!seeds.empty() && seeds.size() != proofs.size()) throw Error(FRIEDA_ERR_ARG, "verify_many: one seed per proof");
+        std::vector<const frieda_proof*> hs;
+        for (const Proof* p : proofs) hs.push_back(p->handle());
+        check(frieda_verify_many(h_, hs.data(), seeds.empty() ? nullptr : seeds.data(), (uint32_t)hs.size(),
+                                 expected_commitment ? expected_commitment->data() : nullptr, status.data()),
+              h_);
+        return status;
+    }
+    // the same + the positions every accepted proof sampled (frieda_verify_samples_many; empty for a proof that is not accepted)
+    std::pair<std::vector<uint8_t>, std::vector<std::vector<uint32_t>>> verify_samples_many(const std::vector<const Proof*>& proofs,
+                                                                                            const std::vector<uint64_t>& seeds = {},
+                                                                                            const Commitment* expected_commitment = nullptr) {
+        std::vector<uint8_t> status(proofs.size());
+        std::vector<std::vector<uint32_t>> out(proofs.size());
+        if (proofs.empty()) return {status, out};
+        if (!seeds.empty() && seeds.size() != proofs.size()) throw Error(FRIEDA_ERR_ARG, "verify_samples_many: one seed per proof");
+        std::vector<const frieda_proof*> hs;
+        size_t pitch = 1;
+        for (const Proof* p : proofs) {
+            hs.push_back(p->handle());
+            pitch = std::max<size_t>(pitch, frieda_proof_pcs_config(p->handle()).n_queries);
+        }
+        std::vector<uint32_t> pos(pitch * hs.size()), n(hs.size());
+        check(frieda_verify_samples_many(h_, hs.data(), seeds.empty() ? nullptr : seeds.data(), (uint32_t)hs.size(),
+                                         expected_commitment ? expected_commitment->data() : nullptr, status.data(), pos.data(), pitch, n.data()),
+              h_);
+        for (size_t i = 0; i < hs.size(); i++) out[i].assign(pos.begin() + i * pitch, pos.begin() + i * pitch + n[i]);
+        return {status, out};
+    }
+    // the sampling client's whole flow (frieda_reconstruct_from_proofs): verify against the commitment, pool the verified samples, rebuild
+    // the blob's `len` bytes and check that they commit to expected_commitment; throws Error when the verified points do not suffice
+    std::vector<uint8_t> reconstruct_from_proofs(const std::vector<const Proof*>& proofs, const std::vector<uint64_t>& seeds,
+                                                 const Commitment& expected_commitment, size_t len, std::vector<uint8_t>* out_status = nullptr,
+                                                 size_t* n_points = nullptr) {
+        if (!seeds.empty() && seeds.size() != proofs.size()) throw Error(FRIEDA_ERR_ARG, "reconstruct_from_proofs: one seed per proof");
+        std::vector<const frieda_proof*> hs;
+        for (const Proof* p : proofs) hs.push_back(p->handle());
+        std::vector<uint8_t> status(hs.size() + 1), out(len + 1);
+        size_t np = 0;
+        const int rc = frieda_reconstruct_from_proofs(h_, hs.data(), seeds.empty() ? nullptr : seeds.data(), (uint32_t)hs.size(), expected_commitment.data(),
+                                                      len, out.data(), status.data(), &np);
+        status.resize(hs.size());
+        if (out_status) *out_status = status;
+        if (n_points) *n_points = np;
+        check(rc, h_);
+        out.resize(len);
         return out;
     }
     // Level B openings over caller device buffers (frieda_dev_gather, frieda_dev_gather_hashes, frieda_merkle_decommit)

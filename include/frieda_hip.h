@@ -138,7 +138,7 @@ int frieda_commit_and_generate_proof_device(frieda_ctx* ctx, const void* d_data,
  * context") and leaves the proof untouched: frieda_commit*, frieda_commit_batch*, a second _begin, frieda_merkle_root,
  * frieda_merkle_commit_layer, frieda_grind, frieda_reconstruct*_device, frieda_circle_interpolate_cells,
  * frieda_ctx_release_workspace, frieda_dev_gather, frieda_dev_gather_hashes, frieda_merkle_decommit (and
- * frieda_merkle_decommit_device beyond 512 positions).  Level B calls that only read the twiddle cache and caller buffers stay available.
+ * frieda_merkle_decommit_device beyond 512 positions), frieda_verify_many, frieda_verify_samples_many, frieda_reconstruct_from_proofs.  Level B calls that only read the twiddle cache and caller buffers stay available.
  * A blob passed to _begin_device must stay valid until _finish returns. */
 int frieda_prove_begin(frieda_ctx* ctx, const uint8_t* data, size_t len, const uint64_t* seed, frieda_pcs_config cfg);
 int frieda_prove_begin_device(frieda_ctx* ctx, const void* d_data, size_t len, const uint64_t* seed, frieda_pcs_config cfg);
@@ -204,8 +204,8 @@ int frieda_commit_batch_device(frieda_ctx* ctx, const void* d_data, size_t strid
 /* api::generate_proof (src/lib.rs:36) */
 int frieda_generate_proof(frieda_ctx* ctx, const uint8_t* data, size_t len, const uint64_t* seed, frieda_pcs_config cfg,
                           frieda_proof** out);
-/* api::verify(proof, seed) -> bool  (src/lib.rs:41, src/proof.rs:79-101).  Host-only (the reference's
- * verifier is O(n_queries * log N) hashes).  *ok receives the bool; FRIEDA_ERR_INVARIANT where the
+/* api::verify(proof, seed) -> bool  (src/lib.rs:41, src/proof.rs:79-101).  Host-only, one proof, one core (the reference's
+ * verifier is O(n_queries * log N) hashes; many proofs: frieda_verify_many below).  *ok receives the bool; FRIEDA_ERR_INVARIANT where the
  * reference panics (src/proof.rs:166-173). */
 int frieda_verify(const frieda_proof* proof, const uint64_t* seed, int* ok);
 /* The sampling client's half of the README's flow (/root/reference/README.md:56-69; in src/ a sample IS a proof: the seed of
@@ -216,6 +216,43 @@ int frieda_verify(const frieda_proof* proof, const uint64_t* seed, int* ok);
  * frieda_circle_interpolate_points / frieda_reconstruct_points_device (log_cell 0, cell r = evaluations[r]).  *n_positions receives
  * the count (0 when the proof is rejected); FRIEDA_ERR_ARG when cap is smaller than that. */
 int frieda_verify_samples(const frieda_proof* proof, const uint64_t* seed, int* ok, uint32_t* out_positions, size_t cap, size_t* n_positions);
+/* Many proofs in one call, verified on the GPU (verify.hip: one wave per proof replays the transcript, draws the queries, folds the
+ * value chain and walks every layer's Merkle tree).  A sampling client checks thousands of proofs before it can rebuild a blob, and the
+ * host verifier above costs 0.24 - 0.66 ms per proof on one core (profiles/r09_verify_many.txt).  proofs[count]: host array of
+ * handles, which may differ in config, size and seed; seeds: NULL (None for all) or seeds[i] = Some for proof i.  Every proof gets one
+ * status byte, always the result frieda_verify gives for it — proofs of a shape the kernel does not take (more than 1024 queries, a
+ * last layer above 2^11 coefficients, more than 40 layers) run through the host verifier inside the same call:
+ *   FRIEDA_VERIFY_REJECTED          frieda_verify: *ok = 0
+ *   FRIEDA_VERIFY_ACCEPTED          frieda_verify: *ok = 1
+ *   FRIEDA_VERIFY_INVARIANT         frieda_verify returns FRIEDA_ERR_INVARIANT (the reference panics)
+ *   FRIEDA_VERIFY_WRONG_COMMITMENT  expected_commitment (32 bytes; NULL: not compared) differs from the proof's first-layer
+ *                                   commitment: not verified at all (api::verify never sees the commitment, a sampling client has it)
+ * The option FRIEDA_VERIFY_DEVICE_MIN is the number of kernel-eligible proofs from which a call uses the GPU
+ * (0: always, 2^31: never).  The calls stage through the context's workspace in passes of bounded size: FRIEDA_ERR_ARG while a
+ * proof is in flight on the context. */
+#define FRIEDA_VERIFY_REJECTED 0
+#define FRIEDA_VERIFY_ACCEPTED 1
+#define FRIEDA_VERIFY_INVARIANT 2
+#define FRIEDA_VERIFY_WRONG_COMMITMENT 3
+int frieda_verify_many(frieda_ctx* ctx, const frieda_proof* const* proofs, const uint64_t* seeds, uint32_t count,
+                       const uint8_t* expected_commitment, uint8_t* out_status);
+/* The same, and WHERE every accepted proof sampled, exactly as frieda_verify_samples reports it: row i of out_positions (pitch
+ * entries per row) holds out_n_positions[i] ascending positions, 0 for a proof that is not accepted.  A proof frieda_verify_samples
+ * answers with FRIEDA_ERR_INVARIANT (accepted, but not one evaluation per distinct query) has status FRIEDA_VERIFY_INVARIANT here.
+ * pitch < n_queries of any proof: FRIEDA_ERR_ARG before anything runs. */
+int frieda_verify_samples_many(frieda_ctx* ctx, const frieda_proof* const* proofs, const uint64_t* seeds, uint32_t count,
+                               const uint8_t* expected_commitment, uint8_t* out_status, uint32_t* out_positions, size_t pitch,
+                               uint32_t* out_n_positions);
+/* The sampling client's whole flow: verify all proofs against expected_commitment, pool the (position, evaluation) pairs of the
+ * accepted ones (de-duplicated by position, first occurrence kept), rebuild the blob from them (frieda_reconstruct_points_device with
+ * log_cell 0, log_coef = the proofs' log_size_bound, log_domain = log_size_bound + log_blowup_factor) and require frieda_commit of
+ * the len rebuilt bytes to equal expected_commitment.  *n_points receives the number of distinct verified points (where accepted
+ * proofs disagree on the shape: those pooled before the proof that disagrees); fewer than
+ * 2^log_size_bound + 2 of them, accepted proofs that disagree on the shape, or a result that does not commit to expected_commitment
+ * (a wrong len): FRIEDA_ERR_ARG with out_bytes untouched.  out_status[count] as frieda_verify_samples_many. */
+int frieda_reconstruct_from_proofs(frieda_ctx* ctx, const frieda_proof* const* proofs, const uint64_t* seeds, uint32_t count,
+                                   const uint8_t expected_commitment[32], size_t len, uint8_t* out_bytes, uint8_t* out_status,
+                                   size_t* n_points);
 
 /* ---- batch policy: how a stream of equal-length blobs is cut into batched calls ("bytes in flight") -------------------------
  * Every kernel of a batched call covers all its blobs, so the launch / Fiat-Shamir latency chain is paid once per call: small
