@@ -356,12 +356,16 @@ FR_HD uint32_t b2_grind_word0(const uint32_t (&h)[8], const uint32_t (&pre)[14],
 #endif
 }
 
+// Initial state of standard unkeyed Blake2s-256: the IV with the parameter block (digest length 32, fanout 1, depth 1) folded in.
+FR_HD void b2s256_init(uint32_t (&h)[8]) {
+    for (int i = 0; i < 8; i++) h[i] = b2detail::IV[i];
+    h[0] ^= 0x01010020u;
+}
 // Standard unkeyed Blake2s-256 of a message given as little-endian words, at most one... any number of
 // 64-byte blocks; `len` in bytes, `words` must be zero padded to a multiple of 16 words.
 FR_HD void b2s256_words(const uint32_t* words, uint32_t len, uint32_t (&out)[8]) {
     uint32_t h[8];
-    for (int i = 0; i < 8; i++) h[i] = b2detail::IV[i];
-    h[0] ^= 0x01010020u;
+    b2s256_init(h);
     uint32_t off = 0;
     while (len - off > 64) {
         uint32_t m[16], nx[8];

@@ -49,16 +49,37 @@ struct Channel {
         b2s256_words(w, 64, r);
         update_digest(r);
     }
-    // blake2s256(digest || LE(n_sent) padded to 32 bytes); n_sent += 1
-    FR_HD void draw_random_words(uint32_t (&out)[8]) {
+    // blake2s256(digest || the LE words of every felt), streamed 64 bytes at a time: no staging buffer
+    FR_HD void mix_felts(const uint32_t* words, uint32_t n_felts) {
+        const uint32_t n_words = 8 + 4 * n_felts, len = 4 * n_words;
+        uint32_t h[8], nx[8], m[16];
+        b2s256_init(h);
+        uint32_t off = 0;  // message words consumed
+        while (len - 4 * off > 64) {
+            for (int i = 0; i < 16; i++) m[i] = (off == 0 && i < 8) ? digest[i & 7] : words[off + i - 8];
+            b2_compress(h, m, 4 * off + 64, 0, 0, 0, nx);
+            for (int i = 0; i < 8; i++) h[i] = nx[i];
+            off += 16;
+        }
+        for (int i = 0; i < 16; i++) m[i] = (off == 0 && i < 8) ? digest[i & 7] : (off + i < n_words ? words[off + i - 8] : 0u);
+        b2_compress(h, m, len, 0, 0xFFFFFFFFu, 0, nx);
+        update_digest(nx);
+    }
+    // draw `counter` of the current digest: blake2s256(digest || LE(counter) padded to 32 bytes).  The draws of one digest are
+    // independent of each other; n_sent is not touched.
+    FR_HD void draw_block(uint32_t counter, uint32_t (&out)[8]) const {
         uint32_t w[16];
         for (int i = 0; i < 8; i++) {
             w[i] = digest[i];
             w[8 + i] = 0;
         }
-        w[8] = n_sent;
-        n_sent += 1;
+        w[8] = counter;
         b2s256_words(w, 64, out);
+    }
+    // Blake2sChannel::draw_random_bytes: the next draw; n_sent += 1
+    FR_HD void draw_random_words(uint32_t (&out)[8]) {
+        draw_block(n_sent, out);
+        n_sent += 1;
     }
     // draw_base_felts retry rule: all eight words < 2P, then reduce; first four form the QM31
     // `bound`: acceptance bound, 2P in stwo; only the retry-branch test passes anything else (<= 2P)

@@ -2,12 +2,8 @@
 // (stwo core/vcs/prover.rs) of a tree whose columns all sit on the leaf layer (frieda_merkle_decommit*), for arbitrary trees and
 // arbitrary position lists.  decommit.hip does the same work inside a proof, for that proof's own trees and at most 1024 queries.
 //
-// Decommitment.  With p the strictly ascending positions (leaf indices of a tree of 2^L leaves), U_s = unique(p >> s) and E_s = the
-// children of the nodes of U_s that are missing from U_{s-1} (each node contributes at most one; E_s is ascending), stwo's hash
-// witness — the bottom-up merge walk that pushes, per layer and per node in ascending order, the hash of every child it does not
-// already know — is E_1, E_2, ..., E_L, with E_s read at tree layer L - s + 1.  Position i emits at level s iff it is the first of
-// its parent group and lies in the right child (the left is missing), or the last and lies in the left child (emit_of).  Every level
-// needs only p, so all levels are computed independently:
+// Decommitment.  stwo's hash witness for the strictly ascending positions p is the E_s tables of queries_dev.h, E_1, E_2, ..., E_L, with
+// E_s read at tree layer L - s + 1; every level needs only p, so all levels are computed independently:
 //   small lists (n <= OPEN_SMALL_MAX): one workgroup, E tables in LDS, one launch;
 //   otherwise: count (block of 1024 positions x level; ballot + popcount) -> one-workgroup exclusive scan in level-major order (stwo's
 //   output order) -> emit (the same ballots, hashes gathered straight into the output; level 0 gathers the column values).
@@ -16,6 +12,7 @@
 #include <hip/hip_runtime.h>
 
 #include "kernels.h"
+#include "queries_dev.h"
 
 namespace frieda {
 namespace k {
@@ -68,22 +65,6 @@ __global__ __launch_bounds__(OP_THREADS) void gather_hashes_kernel(const uint4* 
 }
 
 // ---- decommitment ----
-__device__ __forceinline__ bool emit_at(const uint32_t* p, uint32_t n, uint32_t i, uint32_t s, uint32_t& child) {
-    if (i >= n) return false;
-    const uint32_t x = p[i], v = x >> s, bit = (x >> (s - 1)) & 1u;
-    const bool first = i == 0 || (p[i - 1] >> s) != v;
-    const bool last = i + 1 == n || (p[i + 1] >> s) != v;
-    if (first && bit) {  // every position under v lies in the right child: the left one is missing
-        child = 2 * v;
-        return true;
-    }
-    if (last && !bit) {  // every position under v lies in the left child
-        child = 2 * v + 1;
-        return true;
-    }
-    return false;
-}
-
 __device__ __forceinline__ bool bad_at(const uint32_t* p, uint32_t i, uint32_t log_size) {
     return (p[i] >> log_size) != 0 || (i > 0 && p[i - 1] >= p[i]);
 }
@@ -117,7 +98,6 @@ __global__ __launch_bounds__(OP_THREADS) void decommit_small_kernel(DecommitOpen
     __shared__ const uint4* s_layer[OPEN_MAX_LOG + 1];
     const uint32_t t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const uint32_t n = a.n, L = a.log_size;
-    const unsigned long long lt_mask = (1ull << lane) - 1;
     bool bad = false;
     for (uint32_t i = t; i < n; i += OP_THREADS) {
         s_p[i] = a.pos[i];
@@ -139,16 +119,8 @@ __global__ __launch_bounds__(OP_THREADS) void decommit_small_kernel(DecommitOpen
         return;
     }
     for (uint32_t s = 1 + wave; s <= L; s += OP_THREADS / 64) {
-        uint32_t run = 0;
-        uint32_t* E = s_E + s_slot[s];
-        for (uint32_t i0 = 0; i0 < n; i0 += 64) {
-            uint32_t child = 0;
-            const bool e = emit_at(s_p, n, i0 + lane, s, child);
-            const unsigned long long m = __ballot(e);
-            if (e) E[run + (uint32_t)__popcll(m & lt_mask)] = child;
-            run += (uint32_t)__popcll(m);
-        }
-        if (lane == 0) s_cnt[s] = run;
+        const uint32_t c = qdev::build_level(s_p, n, s, s_E + s_slot[s]);
+        if (lane == 0) s_cnt[s] = c;
     }
     __syncthreads();
     if (t == 0) {
@@ -189,7 +161,7 @@ __global__ __launch_bounds__(OP_THREADS) void decommit_count_kernel(DecommitOpen
     for (uint32_t r = 0; r < OPEN_BLOCK / 4 / 64; r++) {
         const uint32_t i = i0 + r * 64 + lane;
         uint32_t child;
-        c += (uint32_t)__popcll(__ballot(emit_at(a.pos, a.n, i, s, child)));
+        c += (uint32_t)__popcll(__ballot(qdev::emit_of(a.pos, a.n, i, s, child)));
         if (s == 1 && i < a.n) b = b || bad_at(a.pos, i, a.log_size);
     }
     if (lane == 0) s_w[wave] = c;
@@ -277,7 +249,7 @@ __global__ __launch_bounds__(OP_THREADS) void decommit_emit_kernel(DecommitOpen 
 #pragma unroll
     for (uint32_t r = 0; r < OPEN_BLOCK / 4 / 64; r++) {
         ch[r] = 0;
-        m[r] = __ballot(emit_at(a.pos, n, i0 + r * 64 + lane, s, ch[r]));
+        m[r] = __ballot(qdev::emit_of(a.pos, n, i0 + r * 64 + lane, s, ch[r]));
         c += (uint32_t)__popcll(m[r]);
     }
     if (lane == 0) s_w[wave] = c;

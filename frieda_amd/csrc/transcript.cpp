@@ -1,26 +1,19 @@
 // transcript.cpp — the variable-length parts of the Fiat–Shamir transcript shared by prover and verifier:
 // Blake2sChannel::mix_felts and stwo core/queries.rs::Queries::{generate, fold}.  PARITY UNPINNED (see channel.h).
+#include <stddef.h>
+
 #include <algorithm>
 
 #include "host.h"
 
 namespace frieda {
 
-// Blake2sChannel::mix_felts: blake2s256(digest || LE words of every QM31)
+// Blake2sChannel::mix_felts (channel.h) over a vector of QM31
 void channel_mix_felts(Channel& ch, const std::vector<QM31>& felts) {
-    std::vector<uint32_t> w(8 + 4 * felts.size());
-    for (int i = 0; i < 8; i++) w[i] = ch.digest[i];
-    for (size_t i = 0; i < felts.size(); i++) {
-        w[8 + 4 * i] = felts[i].a;
-        w[9 + 4 * i] = felts[i].b;
-        w[10 + 4 * i] = felts[i].c;
-        w[11 + 4 * i] = felts[i].d;
-    }
-    uint32_t len = (uint32_t)(4 * w.size());
-    w.resize((w.size() + 15) / 16 * 16, 0u);
-    uint32_t r[8];
-    b2s256_words(w.data(), len, r);
-    ch.update_digest(r);
+    static_assert(sizeof(QM31) == 4 * sizeof(uint32_t) && offsetof(QM31, a) == 0 && offsetof(QM31, b) == 4 && offsetof(QM31, c) == 8 &&
+                      offsetof(QM31, d) == 12,
+                  "a QM31 is four consecutive uint32_t: a, b, c, d");
+    ch.mix_felts(reinterpret_cast<const uint32_t*>(felts.data()), (uint32_t)felts.size());
 }
 
 // Queries::generate

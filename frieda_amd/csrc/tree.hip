@@ -1171,7 +1171,7 @@ __global__ __launch_bounds__(WG1_THREADS) void tail_kernel(TailArgs a) {
     for (uint32_t i = msg_words + t; i < ((msg_words + 15) / 16) * 16; i += WG1_THREADS) MSG[i] = 0;
     __syncthreads();
     if (t == 0) {
-        // Blake2sChannel::mix_felts(last_layer_poly)
+        // Blake2sChannel::mix_felts(last_layer_poly): all 1024 threads assembled the message in LDS, so not the streamed Channel::mix_felts
         Channel ch = tr->ch;
 #pragma unroll
         for (int w = 0; w < 8; w++) MSG[w] = ch.digest[w];

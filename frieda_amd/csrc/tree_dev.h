@@ -41,6 +41,16 @@ template <int IDLE = FRIEDA_B2_IDLE_LEAF>
 __device__ __forceinline__ void leaf_hash(uint32_t v0, uint32_t v1, uint32_t v2, uint32_t v3, uint32_t (&h)[8]) {
     b2_merkle_leaf<IDLE>(v0, v1, v2, v3, h);
 }
+// the node above two neighbouring leaves of 4 column words each: two leaf hashes and their parent
+template <int IDLE>
+__device__ __forceinline__ void pair_node(const uint32_t (&l)[4], const uint32_t (&r)[4], uint32_t (&h)[8]) {
+    uint32_t hl[8], hr[8], m[16];
+    leaf_hash<IDLE>(l[0], l[1], l[2], l[3], hl);
+    leaf_hash<IDLE>(r[0], r[1], r[2], r[3], hr);
+#pragma unroll
+    for (int w = 0; w < 8; w++) m[w] = hl[w], m[8 + w] = hr[w];
+    b2_merkle_block<IDLE>(m, h);
+}
 __device__ __forceinline__ size_t layer_off(uint32_t tree_log, uint32_t layer) {
     return ((size_t)64 << tree_log) - ((size_t)64 << layer);
 }

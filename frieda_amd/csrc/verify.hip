@@ -4,13 +4,13 @@
 // data, built by verify_many.cpp); the wave
 //   1. replays the transcript (init, optional mix_u64(seed), per layer mix_root + draw_felt, mix_felts(last_layer_poly),
 //      mix_u64(nonce), the trailing-zeros test),
-//   2. draws the queries (independent draws, one per lane), sorts and de-duplicates them (as decommit.hip),
+//   2. draws the queries, sorted and de-duplicated (queries_dev.h, the code the prover's decommit.hip runs),
 //   3. walks the layers: with U_li = unique(queries >> li) the positions of layer li, every pair {2v, 2v + 1}, v in U_{li+1}, takes its
 //      members from the running values or — the index is a prefix count of "not queried" (ballot + popcount) — from fri_witness,
 //      folds it with the layer's alpha, and
 //   4. hashes the pair's two leaves and their parent, then walks the tree level by level: the nodes of a level are unique(positions
 //      >> s), a child that was not computed below comes from hash_witness at the prefix count of the missing children (the E_s tables
-//      of decommit.hip, read from the verifier's side), and the root is compared with the layer's commitment.
+//      of queries_dev.h, read from the verifier's side), and the root is compared with the layer's commitment.
 // Every list lives in LDS and is compacted in place: entry k of a level is written after the entries >= k of the level below were
 // read (a wave executes its LDS accesses in program order), the neighbour below a 64-entry chunk is carried in a register.
 //
@@ -20,6 +20,7 @@
 
 #include "dev_transcript.h"
 #include "kernels.h"
+#include "queries_dev.h"
 #include "tree_dev.h"
 
 namespace frieda {
@@ -83,11 +84,9 @@ __global__ __launch_bounds__(64) void verify_many_kernel(VerifyArgs a) {
     uint32_t* s_ev = lds + 2 * Q;    // the current layer's values at s_pos, 4 words each
     uint32_t* s_h = lds + 6 * Q;     // node hashes of the Merkle walk, 8 words each
     __shared__ uint32_t s_alpha[4 * DT_MAX_LAYERS];
-    __shared__ uint32_t s_digest[8];
     __shared__ uint32_t s_misc[2];
 
     const uint32_t lane = threadIdx.x, slot = blockIdx.x;
-    const unsigned long long lt_mask = (1ull << lane) - 1;
     const VerifyHeader hd = reinterpret_cast<const VerifyHeader*>(a.img)[slot];
     const uint32_t* img = a.img + hd.off_words;
     uint32_t* out = a.out + (size_t)slot * (2 + a.q_cap);
@@ -104,114 +103,26 @@ __global__ __launch_bounds__(64) void verify_many_kernel(VerifyArgs a) {
     } while (0)
 
     // ---- 1. the transcript: every lane computes the same chain; lane 0 keeps the alphas ----
-    {
-        Channel ch;
-        ch.init();
-        if (hd.has_seed) ch.mix_u64((uint64_t)hd.seed_lo | ((uint64_t)hd.seed_hi << 32));
-        for (uint32_t li = 0; li <= nl; li++) {
-            const uint32_t* c = img + tab[4 * li + 3];
-            uint32_t w[8];
+    Channel ch;
+    ch.init();
+    if (hd.has_seed) ch.mix_u64((uint64_t)hd.seed_lo | ((uint64_t)hd.seed_hi << 32));
+    for (uint32_t li = 0; li <= nl; li++) {
+        const uint32_t* c = img + tab[4 * li + 3];
+        uint32_t w[8];
 #pragma unroll
-            for (int i = 0; i < 8; i++) w[i] = c[i];
-            ch.mix_root(w);
-            const QM31 al = ch.draw_felt();
-            if (lane == 0) s_alpha[4 * li] = al.a, s_alpha[4 * li + 1] = al.b, s_alpha[4 * li + 2] = al.c, s_alpha[4 * li + 3] = al.d;
-        }
-        // Blake2sChannel::mix_felts: blake2s256(digest || the words of every coefficient), streamed from the image
-        {
-            const uint32_t n_words = 8 + 4 * np, len = 4 * n_words;
-            uint32_t h[8], nx[8], m[16];
-#pragma unroll
-            for (int i = 0; i < 8; i++) h[i] = b2detail::IV[i];
-            h[0] ^= 0x01010020u;
-            uint32_t off = 0;  // words
-            while (len - 4 * off > 64) {
-#pragma unroll
-                for (int i = 0; i < 16; i++) m[i] = (off == 0 && i < 8) ? ch.digest[i & 7] : last_poly[off + i - 8];
-                b2_compress(h, m, 4 * off + 64, 0, 0, 0, nx);
-#pragma unroll
-                for (int i = 0; i < 8; i++) h[i] = nx[i];
-                off += 16;
-            }
-#pragma unroll
-            for (int i = 0; i < 16; i++) m[i] = (off == 0 && i < 8) ? ch.digest[i & 7] : (off + i < n_words ? last_poly[off + i - 8] : 0u);
-            b2_compress(h, m, len, 0, 0xFFFFFFFFu, 0, nx);
-            ch.update_digest(nx);
-        }
-        ch.mix_u64((uint64_t)hd.nonce_lo | ((uint64_t)hd.nonce_hi << 32));
-        if (ch.trailing_zeros() < hd.pow_bits) VK_FINISH(VERIFY_REJECTED);
-        if (lane == 0) {
-#pragma unroll
-            for (int i = 0; i < 8; i++) s_digest[i] = ch.digest[i];
-        }
+        for (int i = 0; i < 8; i++) w[i] = c[i];
+        ch.mix_root(w);
+        const QM31 al = ch.draw_felt();
+        if (lane == 0) s_alpha[4 * li] = al.a, s_alpha[4 * li + 1] = al.b, s_alpha[4 * li + 2] = al.c, s_alpha[4 * li + 3] = al.d;
     }
-    __syncthreads();
+    ch.mix_felts(last_poly, np);
+    ch.mix_u64((uint64_t)hd.nonce_lo | ((uint64_t)hd.nonce_hi << 32));
+    if (ch.trailing_zeros() < hd.pow_bits) VK_FINISH(VERIFY_REJECTED);
 
-    // ---- 2. Queries::generate, sorted and de-duplicated into s_pos (decommit.hip) ----
-    uint32_t nu;
-    {
-        const uint32_t mask = (1u << n) - 1;
-        uint32_t P = 2;
-        while (P < nq) P <<= 1;
-        for (uint32_t d = lane; d < (nq + 7) / 8; d += 64) {
-            uint32_t w[16], r[8], h0[8];
-#pragma unroll
-            for (int i = 0; i < 8; i++) w[i] = s_digest[i], w[8 + i] = 0, h0[i] = b2detail::IV[i];
-            w[8] = d;
-            h0[0] ^= 0x01010020u;
-            b2_compress(h0, w, 64, 0, 0xFFFFFFFFu, 0, r);
-#pragma unroll
-            for (int j = 0; j < 8; j++)
-                if (8 * d + j < nq) s_hp[8 * d + j] = r[j] & mask;
-        }
-        for (uint32_t i = nq + lane; i < P; i += 64) s_hp[i] = 0xFFFFFFFFu;
-        __syncthreads();
-        if (P <= 64) {
-            const uint32_t v = s_hp[lane < P ? lane : 0];
-            uint32_t rank = 0;
-#pragma unroll
-            for (int j = 0; j < 64; j++) {
-                const uint32_t o = (uint32_t)__builtin_amdgcn_readlane((int)v, j);
-                rank += ((uint32_t)j < P && (o < v || (o == v && (uint32_t)j < lane))) ? 1u : 0u;
-            }
-            __syncthreads();
-            if (lane < P) s_hp[rank] = v;
-            __syncthreads();
-            const uint32_t x = s_hp[lane < P ? lane : 0], prev = s_hp[lane > 0 && lane < P ? lane - 1 : 0];
-            const bool first = lane < nq && (lane == 0 || x != prev);
-            const unsigned long long m = __ballot(first);
-            if (first) s_pos[__popcll(m & lt_mask)] = x;
-            nu = (uint32_t)__popcll(m);
-        } else {
-            for (uint32_t k2 = 2; k2 <= P; k2 <<= 1) {
-                for (uint32_t j = k2 >> 1; j > 0; j >>= 1) {
-                    for (uint32_t i = lane; i < P; i += 64) {
-                        const uint32_t ixj = i ^ j;
-                        if (ixj > i) {
-                            const uint32_t x = s_hp[i], y = s_hp[ixj];
-                            const bool asc = (i & k2) == 0;
-                            if ((x > y) == asc) {
-                                s_hp[i] = y;
-                                s_hp[ixj] = x;
-                            }
-                        }
-                    }
-                    __syncthreads();
-                }
-            }
-            nu = 0;
-            for (uint32_t i0 = 0; i0 < nq; i0 += 64) {
-                const uint32_t i = i0 + lane;
-                const bool first = i < nq && (i == 0 || s_hp[i] != s_hp[i - 1]);
-                const unsigned long long m = __ballot(first);
-                if (first) s_pos[nu + (uint32_t)__popcll(m & lt_mask)] = s_hp[i];
-                nu += (uint32_t)__popcll(m);
-            }
-        }
-        __syncthreads();
-        for (uint32_t i = lane; i < nu; i += 64) out[2 + i] = s_pos[i];
-        if (lane == 0) out[1] = nu;
-    }
+    // ---- 2. Queries::generate, sorted in s_hp and de-duplicated into s_pos ----
+    const uint32_t nu = qdev::generate_queries<64>(ch, n, nq, s_hp, s_pos);
+    for (uint32_t i = lane; i < nu; i += 64) out[2 + i] = s_pos[i];
+    if (lane == 0) out[1] = nu;
 
     // ---- 3 + 4. the layers ----
     const uint32_t ne = hd.n_evals;
@@ -251,12 +162,9 @@ __global__ __launch_bounds__(64) void verify_many_kernel(VerifyArgs a) {
             if (g.first) {
                 const uint32_t v = g.x >> 1;
                 // the pair's two leaves and their parent: node v of level m - 1
-                uint32_t hl[8], hr[8], mm[16], hp[8];
-                treedev::leaf_hash<B2_LAT>(l.a, l.b, l.c, l.d, hl);
-                treedev::leaf_hash<B2_LAT>(r.a, r.b, r.c, r.d, hr);
-#pragma unroll
-                for (int w = 0; w < 8; w++) mm[w] = hl[w], mm[8 + w] = hr[w];
-                b2_merkle_block<B2_LAT>(mm, hp);
+                const uint32_t lw[4] = {l.a, l.b, l.c, l.d}, rw[4] = {r.a, r.b, r.c, r.d};
+                uint32_t hp[8];
+                treedev::pair_node<B2_LAT>(lw, rw, hp);
 #pragma unroll
                 for (int w = 0; w < 8; w++) s_h[8 * g.k + w] = hp[w];
                 s_hp[g.k] = v;

@@ -429,6 +429,46 @@ def test_draw_felt_retry_branch(gpu_ctx, oracle, host_channel):
     assert d_root == g_root and d_proof.serialize() != g_proof.serialize()
 
 
+@pytest.mark.parametrize("nq", [1, 2, 63, 128, 129, 1024])
+def test_query_sort_and_compaction_seams(gpu_ctx, oracle, nq):
+    """The seams of the sort / de-duplication the prover's openings and verify_many share (queries_dev.h): 1 and 2 queries (the
+    smallest padded list), 63 (just under one wave), 128 (exactly two compaction chunks), 129 (a chunk plus one) and 1024 (the
+    kernels' limit).  Two domains under blow-up 2^3, last-layer bound 1: 200 bytes -> 2^7 (at 1024 queries every position is drawn
+    many times, at most 128 distinct) and 1500 bytes -> 2^10 (at 1024 queries ~650 distinct positions, several chunks, and the
+    opening tables still fit the kernel).  Each proof byte for byte against the oracle's, then through verify_many and the host
+    verifier, both accepting; at 1024 queries the openings must have come from the device kernel, not the host planner (whose
+    fallback shows as a `gather` launch); at 129 also one batch of three blobs."""
+    import frieda_amd
+
+    cfg, ocfg = _cfg(frieda_amd, 4, 3, 1, nq), oracle.make_config(4, 3, 1, nq)
+    datas = [splitmix64_bytes(600 + i, nbytes).tobytes() for i, nbytes in enumerate((200, 1500))]
+    seeds = [17, 18]
+    proofs = []
+    for data, seed, log_domain in zip(datas, seeds, (7, 10)):
+        o_root, o_proof = oracle.commit_and_generate_proof(data, seed, ocfg)
+        gpu_ctx.set_kernel_timing(nq == 1024)
+        try:
+            g_root, g_proof = gpu_ctx.commit_and_generate_proof(data, seed, cfg)
+            names = [k["name"] for k in gpu_ctx.kernel_timing_report()] if nq == 1024 else None
+        finally:
+            gpu_ctx.set_kernel_timing(False)
+        assert g_proof.log_size_bound + 3 == log_domain
+        assert g_root == o_root and g_proof.serialize() == o_proof.serialize()
+        if names is not None:
+            assert "decommit" in names and "gather" not in names, names
+        assert frieda_amd.verify(g_proof, seed)
+        proofs.append(g_proof)
+    assert list(gpu_ctx.verify_many(proofs, seeds)) == [1, 1]  # VERIFY_ACCEPTED
+    if nq == 129:
+        blobs = [splitmix64_bytes(610 + i, 200).tobytes() for i in range(3)]
+        got = gpu_ctx.commit_and_generate_proof_batch(blobs, [5, 6, 7], cfg)
+        for i, (root, proof) in enumerate(got):
+            o_root, o_proof = oracle.commit_and_generate_proof(blobs[i], 5 + i, ocfg)
+            assert root == o_root and proof.serialize() == o_proof.serialize(), i
+            assert frieda_amd.verify(proof, 5 + i)
+        assert list(gpu_ctx.verify_many([p for _, p in got], [5, 6, 7])) == [1, 1, 1]
+
+
 def test_reference_proof_tests_on_gpu(gpu_ctx, blob):
     """src/proof.rs:119-193 through the GPU prover and the C-ABI verifier."""
     import frieda_amd

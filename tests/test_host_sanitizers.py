@@ -57,13 +57,25 @@ def test_parser_and_verifier_under_asan(fuzz_binary, oracle, blob, tmp_path, cas
     assert "accepted_mutants 0" in r.stdout
 
 
-def test_lazy_field_arithmetic_matches_textbook(tmp_path):
-    """field.h's lazily reduced fold (one 64-bit accumulator per coordinate) equals the textbook QM31 sequence, under UBSan,
-    including the operands that attain the accumulator bound."""
-    exe = tmp_path / "test_field"
+def _run_host_program(tmp_path, name):
+    """tests/cpp/<name>.cpp: a stand-alone host program over the product's headers, built with UBSan; it prints OK"""
+    exe = tmp_path / name
     cmd = ["g++", "-std=c++17", "-O2", "-fsanitize=undefined", "-fno-sanitize-recover=undefined", "-I" + CSRC,
-           os.path.join(ROOT, "tests", "cpp", "test_field.cpp"), "-o", str(exe)]
+           os.path.join(ROOT, "tests", "cpp", name + ".cpp"), "-o", str(exe)]
     r = subprocess.run(cmd, capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-800:]
     r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0 and r.stdout.startswith("OK"), r.stdout + r.stderr
+
+
+def test_lazy_field_arithmetic_matches_textbook(tmp_path):
+    """field.h's lazily reduced fold (one 64-bit accumulator per coordinate) equals the textbook QM31 sequence, under UBSan,
+    including the operands that attain the accumulator bound."""
+    _run_host_program(tmp_path, "test_field")
+
+
+def test_channel_streamed_mix_and_draws(tmp_path):
+    """channel.h under UBSan: the streamed Channel::mix_felts equals blake2s256 over the zero-padded buffer digest || words for
+    0 .. 9, 14 .. 17 and 2048 felts (2 and 6 felts end exactly on a block boundary), draw_block(k) is the draw of a channel whose
+    n_sent is k, and mix_u64 / draw_felt on a fixed digest give the recorded words."""
+    _run_host_program(tmp_path, "test_channel")
