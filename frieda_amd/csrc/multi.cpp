@@ -27,6 +27,7 @@
 #include <thread>
 
 #include "host.h"
+#include "unit_pipeline.h"
 
 using namespace frieda;
 
@@ -188,15 +189,12 @@ static void drain_ctx(frieda_ctx* c) {
 }
 
 inline size_t ring_stride(size_t len) { return (len + 255) & ~(size_t)255; }
-constexpr uint32_t RING_SLOTS_C = 3;  // (= RING_SLOTS below)
+constexpr uint32_t RING_SLOTS = 3;  // staging slots of a device's upload ring (UploadRing below)
 
 // A device's share of the blobs (blob d, d + n, ...) cut into units = calls of the batched kernels.  A run of equal-length blobs is
 // cut by the library's batch policy (host.h: workspace bytes in flight, two calls in flight per device), anything else is a single
 // blob.  With host blobs travelling ahead of their kernels, the very first unit is a single blob when more follow: the chip starts
-// after one upload instead of a whole unit's.
-struct Unit {
-    uint32_t slot, cnt;
-};
+// after one upload instead of a whole unit's.  (struct Unit: unit_pipeline.h)
 //  The policy's budget is a figure for an otherwise empty MI355X.  `mem_cap` = the bytes this device can give the pass NOW
 // (what hipMemGetInfo reports free + what the device's two contexts and its ring already hold, less a margin; 0 = unknown): two calls'
 // workspaces and three ring slots must fit.  `shrink`: the per-call count halved that many times (the workers' retry after a
@@ -213,7 +211,7 @@ static void cut_device_units(const size_t* lens, uint32_t d, uint32_t n, uint32_
         while (batchable && slot + run < mine && lens[i0 + run * n] == lens[i0]) run++;
         const size_t ws = workspace_bytes_per_blob(lens[i0], log_blowup, log_last, prove, true);  // 0: the call itself reports the shape error
         uint32_t per = ws ? batch_per_call(tune, ws, run, 2) : 1u;
-        if (ws && mem_cap) per = (uint32_t)std::min<uint64_t>(per, std::max<uint64_t>(1, mem_cap / (2 * (uint64_t)ws + RING_SLOTS_C * ring_stride(lens[i0]))));
+        if (ws && mem_cap) per = (uint32_t)std::min<uint64_t>(per, std::max<uint64_t>(1, mem_cap / (2 * (uint64_t)ws + RING_SLOTS * ring_stride(lens[i0]))));
         per = std::max<uint32_t>(1, per >> std::min<uint32_t>(shrink, 31));
         if (first_single && slot == from_slot && mine - from_slot > 1 && run > 1) {
             // Host blobs: a unit starts when its last blob has arrived, and the upload of unit u + 1 runs under the kernels of unit u.  A
@@ -247,7 +245,6 @@ static void cut_device_units(const size_t* lens, uint32_t d, uint32_t n, uint32_
 // idle (measured: 1.15 ms per unit of four 15.7 MB blobs, 0.3 ms per blob — profiles/r03_multi_trace_before.txt).  Instead
 // each device has a copy stream and three staging slots in device memory: the blobs of unit u + 2 are uploaded while units u and
 // u + 1 compute, an event orders the unit's first kernel behind its upload, and the kernels read the blobs where they landed.
-constexpr uint32_t RING_SLOTS = RING_SLOTS_C;
 struct UploadRing {
     hipStream_t stream = nullptr;
     hipEvent_t ready[RING_SLOTS] = {};
@@ -416,6 +413,191 @@ int frieda_multi::gather_roots(const std::vector<std::vector<Hash32>>& local, ui
     return FRIEDA_OK;
 }
 
+// ---- frieda_commit_many / frieda_prove_many: one worker thread per device, one pass driver (unit_pipeline.h) ----
+// The blobs of one unit of device d's share: blob k of the unit is blob i0 + k * n of the call.
+struct UnitBlobs {
+    uint32_t i0, n, cnt;
+    std::vector<const uint8_t*> ptrs(const uint8_t* const* blobs) const {
+        std::vector<const uint8_t*> p(cnt);
+        for (uint32_t k = 0; k < cnt; k++) p[k] = blobs[i0 + k * n];
+        return p;
+    }
+};
+
+// Device d's worker.  Its blobs in order, cut into units (cut_device_units); two units in flight on the device's two contexts —
+// begin(u + 1) is enqueued on the other context before finish(u) waits —, the blobs of the unit after them uploaded meanwhile on the
+// copy stream (run_unit_pass); a pass that ran out of device memory is repeated from its first unfinished blob with the calls
+// halved (run_unit_passes).  What differs between committing and proving is in `ops`:
+//   prove, log_blowup, log_last: the shape cut_device_units plans for;  batchable(c0, c1): may equal-length runs share a call;
+//   begin(c, unit blobs, dev) -> status: enqueue the unit on c; dev = where its blobs were uploaded, null = read the host blobs;
+//   finish(c, unit blobs, roots) -> status;  abandon(c, unit blobs): finish a begun unit for nobody;
+//   recover(c): after an exception nothing may stay in flight on c, and nothing may throw.
+template <class Ops>
+static void device_worker(frieda_multi* m, uint32_t d, const uint8_t* const* blobs, const size_t* lens, const Ops& ops,
+                          std::vector<Hash32>& roots, std::atomic<bool>& abort, int& status, std::string& what) {
+    const uint32_t n = (uint32_t)m->devices.size();
+    pin_this_thread(m->near_cpus[d]);
+    frieda_ctx* cx[2] = {m->ctx[2 * d], m->ctx[2 * d + 1]};
+    cx[1]->c.tuning.test_arena_limit = cx[0]->c.tuning.test_arena_limit;  // (test hook set through frieda_multi_ctx: the slot's both contexts)
+    const bool pf = m->prefetch;
+    struct DrainUploads {  // no upload may still be reading the caller's blobs when the worker returns
+        frieda_multi* m;
+        size_t d;
+        bool on;
+        ~DrainUploads() {
+            if (on) (void)hipStreamSynchronize(m->ring[d].stream);
+        }
+    } drain_uploads{m, d, pf};
+    auto fail = [&](int rc, const std::string& msg) {
+        status = rc;
+        what = msg;
+        abort.store(true);
+    };
+    try {
+        const uint32_t mine = (uint32_t)roots.size();
+        if (mine == 0) return;
+        if (hipSetDevice(m->devices[d]) != hipSuccess) return fail(FRIEDA_ERR_HIP, "hipSetDevice");
+        const bool batchable = ops.batchable(cx[0]->c, cx[1]->c);
+        const UploadRing& ring = m->ring[d];
+        std::vector<Unit> units;
+        size_t ring_need = 0;
+        std::string err, msg;  // the text of the call that just failed; of the pass's first failure
+        auto blobs_of = [&](size_t u) { return UnitBlobs{d + units[u].slot * n, n, units[u].cnt}; };
+        auto said = [&](frieda_ctx* c, int rc) {
+            if (rc != FRIEDA_OK) err = c->c.err;
+            return rc;
+        };
+        auto cut = [&](uint32_t from_slot, uint32_t shrink) -> const std::vector<Unit>& {
+            cut_device_units(lens, d, n, mine, batchable, ops.prove, ops.log_blowup, ops.log_last, cx[0]->c.tuning, pf, units, ring_need, from_slot,
+                             m->mem_cap_now(d), shrink);
+            return units;
+        };
+        auto prepare = [&] { return pf ? m->ensure_ring(d, ring_need, msg) : FRIEDA_OK; };
+        auto drop = [&] { m->drop_device_workspace(d, pf); };  // (synchronises the contexts' streams and the copy stream first)
+        auto upload = [&](size_t u) {
+            const UnitBlobs ub = blobs_of(u);
+            return m->upload(d, (uint32_t)(u % RING_SLOTS), ub.ptrs(blobs).data(), lens[ub.i0], ub.cnt, err);
+        };
+        auto begin = [&](size_t u) {
+            frieda_ctx* c = cx[u & 1];
+            const uint8_t* dev = nullptr;
+            if (pf) {
+                if (hipStreamWaitEvent(c->c.stream, ring.ready[u % RING_SLOTS], 0) != hipSuccess)
+                    return said(c, c->c.fail(FRIEDA_ERR_HIP, "hipStreamWaitEvent(blob upload)"));
+                dev = ring.slot[u % RING_SLOTS];
+            }
+            return said(c, ops.begin(c, blobs_of(u), dev));
+        };
+        auto finish = [&](size_t u) { return said(cx[u & 1], ops.finish(cx[u & 1], blobs_of(u), roots[units[u].slot].data())); };
+        auto abandon = [&](size_t u) { ops.abandon(cx[u & 1], blobs_of(u)); };
+        auto pass = [&](const std::vector<Unit>& us, uint32_t& done) {
+            return run_unit_pass(us, pf, abort, upload, begin, finish, abandon, done, err, msg);
+        };
+        const int st = run_unit_passes(abort, cut, prepare, drop, pass);
+        if (st != FRIEDA_OK) fail(st, msg);
+    } catch (...) {  // nothing may unwind out of a worker thread
+        fail(FRIEDA_ERR_NOMEM, "host allocation failed");
+        for (frieda_ctx* c : cx) ops.recover(c);
+    }
+}
+
+// blob i -> device i mod n; local[d] receives the roots device d produced, in its order.  The first failing device is the call's error.
+template <class Ops>
+static int run_on_devices(frieda_multi* m, const uint8_t* const* blobs, const size_t* lens, uint32_t count, const Ops& ops,
+                          std::vector<std::vector<Hash32>>& local) {
+    const uint32_t n = (uint32_t)m->devices.size();
+    std::vector<int> status(n, FRIEDA_OK);
+    std::vector<std::string> what(n);
+    std::atomic<bool> abort{false};
+    local.assign(n, {});
+    for (uint32_t d = 0; d < n; d++) local[d].resize((count + n - 1 - d) / n);
+    {
+        std::vector<std::thread> workers;
+        JoinAll join_guard{workers};
+        for (uint32_t d = 0; d < n; d++)
+            workers.emplace_back([&, d] { device_worker(m, d, blobs, lens, ops, local[d], abort, status[d], what[d]); });
+    }
+    for (uint32_t d = 0; d < n; d++)
+        if (status[d] != FRIEDA_OK) return m->fail(status[d], "device " + std::to_string(m->devices[d]) + ": " + what[d]);
+    if (abort.load()) return m->fail(FRIEDA_ERR_INVARIANT, "internal: aborted without a status");
+    return FRIEDA_OK;
+}
+
+struct CommitOps {
+    static constexpr bool prove = false;
+    const uint8_t* const* blobs;
+    const size_t* lens;
+    uint32_t log_blowup, log_last;
+    bool batchable(const Ctx&, const Ctx&) const { return true; }
+    int begin(frieda_ctx* c, const UnitBlobs& ub, const uint8_t* dev) const {
+        const size_t len = lens[ub.i0];
+        if (dev) return commit_batch_begin(&c->c, dev, ring_stride(len), len, ub.cnt, true, log_blowup, nullptr);
+        const std::vector<const uint8_t*> ptrs = ub.ptrs(blobs);
+        return commit_batch_begin(&c->c, ptrs[0], len, len, ub.cnt, false, log_blowup, ptrs.data());
+    }
+    int finish(frieda_ctx* c, const UnitBlobs&, uint8_t* roots) const { return commit_batch_finish(&c->c, roots); }
+    void abandon(frieda_ctx* c, const UnitBlobs& ub) const {
+        std::vector<uint8_t> r(32 * (size_t)ub.cnt);
+        (void)commit_batch_finish(&c->c, r.data());
+    }
+    void recover(frieda_ctx* c) const {  // (without allocating: the exception may have been bad_alloc)
+        if (!c->c.commit_pending) return;
+        (void)hipStreamSynchronize(c->c.stream);
+        c->c.commit_pending = 0;
+    }
+};
+
+struct ProveOps {
+    static constexpr bool prove = true;
+    const uint8_t* const* blobs;
+    const size_t* lens;
+    const uint64_t* seeds;
+    frieda_pcs_config cfg;
+    uint32_t log_blowup, log_last;
+    frieda_proof** out_proofs;
+    // batches need the device transcript (prover.cpp): small last layers, and neither context switched to the host channel through
+    // frieda_multi_ctx (then equal-length runs go as single proofs instead of failing)
+    bool batchable(const Ctx& c0, const Ctx& c1) const {
+        return log_last <= 11 && log_blowup <= 11 && log_last + log_blowup <= 11 && !c0.host_channel && !c1.host_channel;
+    }
+    int begin(frieda_ctx* c, const UnitBlobs& ub, const uint8_t* dev) const {
+        const size_t len = lens[ub.i0];
+        if (ub.cnt == 1) return prove_begin(&c->c, dev ? dev : blobs[ub.i0], len, dev != nullptr, seeds ? &seeds[ub.i0] : nullptr, cfg);
+        std::vector<uint64_t> sd(seeds ? ub.cnt : 0);  // a batch wants its seeds side by side
+        for (uint32_t k = 0; k < sd.size(); k++) sd[k] = seeds[ub.i0 + k * ub.n];
+        const uint64_t* sp = seeds ? sd.data() : nullptr;
+        if (dev) return prove_begin_batch(&c->c, dev, ring_stride(len), len, ub.cnt, true, sp, cfg);
+        return prove_begin_batch_ptrs(&c->c, ub.ptrs(blobs).data(), len, ub.cnt, sp, cfg);
+    }
+    int finish(frieda_ctx* c, const UnitBlobs& ub, uint8_t* roots) const {  // fills the unit's roots and out_proofs
+        std::vector<frieda_proof*> objs(ub.cnt, nullptr);
+        std::vector<ProofData> outs(ub.cnt);
+        for (uint32_t k = 0; k < ub.cnt; k++) {
+            objs[k] = c->pool->get();
+            objs[k]->home = c->pool;
+            outs[k] = std::move(objs[k]->p);
+        }
+        const int rf = prove_finish_batch(&c->c, roots, outs);
+        for (uint32_t k = 0; k < ub.cnt; k++) {
+            if (k < outs.size()) objs[k]->p = std::move(outs[k]);
+            if (rf != FRIEDA_OK)
+                c->pool->put(objs[k]);
+            else
+                out_proofs[ub.i0 + k * ub.n] = objs[k];
+        }
+        return rf;
+    }
+    void abandon(frieda_ctx* c, const UnitBlobs&) const { drain_ctx(c); }
+    void recover(frieda_ctx* c) const { drain_ctx(c); }
+};
+
+static void free_out_proofs(frieda_proof** out_proofs, uint32_t count) {
+    for (uint32_t i = 0; i < count; i++) {
+        if (out_proofs[i]) frieda_proof_free(out_proofs[i]);
+        out_proofs[i] = nullptr;
+    }
+}
+
 extern "C" {
 
 int frieda_multi_create(const int* devices, uint32_t n_devices, frieda_multi** out) {
@@ -569,144 +751,9 @@ int frieda_commit_many(frieda_multi* m, const uint8_t* const* blobs, const size_
     for (uint32_t i = 0; i < count; i++)
         if (!blobs[i] && lens[i]) return m->fail(FRIEDA_ERR_ARG, "null blob");
     try {
-        const size_t n = m->devices.size();
-        std::vector<std::vector<Hash32>> local(n);
-        std::vector<int> status(n, FRIEDA_OK);
-        std::vector<std::string> what(n);
-        std::atomic<bool> abort{false};
-        std::vector<std::thread> workers;
-        JoinAll join_guard{workers};
-        for (size_t d = 0; d < n; d++) local[d].resize((count + n - 1 - d) / n);
-        for (size_t d = 0; d < n; d++) {
-            workers.emplace_back([&, d] {
-                pin_this_thread(m->near_cpus[d]);
-                frieda_ctx* cx[2] = {m->ctx[2 * d], m->ctx[2 * d + 1]};
-                cx[1]->c.tuning.test_arena_limit = cx[0]->c.tuning.test_arena_limit;  // (test hook set through frieda_multi_ctx: the slot's both contexts)
-                const bool pf = m->prefetch;
-                struct DrainUploads {  // no upload may still be reading the caller's blobs when the worker returns
-                    frieda_multi* m;
-                    size_t d;
-                    bool on;
-                    ~DrainUploads() {
-                        if (on) (void)hipStreamSynchronize(m->ring[d].stream);
-                    }
-                } drain_uploads{m, d, pf};
-                try {
-                    // This device's blobs in order, cut into units (cut_device_units: a run of blobs of one length = calls of the
-                    // batched kernels, sized by the batch policy); two units in flight on the two contexts, the blobs of the unit after them being uploaded
-                    // meanwhile on the copy stream.
-                    const uint32_t mine = (uint32_t)local[d].size();
-                    if (mine == 0) return;
-                    if (hipSetDevice(m->devices[d]) != hipSuccess) {
-                        status[d] = FRIEDA_ERR_HIP;
-                        what[d] = "hipSetDevice";
-                        abort.store(true);
-                        return;
-                    }
-                    // One PASS over what is left of this device's blobs; a pass that ran out of device memory is repeated from its first
-                    // unfinished blob with the calls halved (pass_st / pass_msg: the pass's own status, published when final).
-                    uint32_t done = 0, shrink = 0;
-                    for (;;) {
-                    int pass_st = FRIEDA_OK;
-                    std::string pass_msg;
-                    uint32_t largest = 1;
-                    auto pass = [&] {
-                    std::vector<Unit> units;
-                    size_t ring_need = 0;
-                    cut_device_units(lens, (uint32_t)d, (uint32_t)n, mine, true, false, log_blowup_factor, 0, cx[0]->c.tuning, pf, units, ring_need, done,
-                                     m->mem_cap_now(d), shrink);
-                    for (const Unit& un : units) largest = std::max(largest, un.cnt);
-                    auto bail_msg = [&](int rc, const std::string& msg) {
-                        if (pass_st == FRIEDA_OK) {
-                            pass_st = rc;
-                            pass_msg = msg;
-                        }
-                    };
-                    auto bail = [&](int rc, frieda_ctx* c) { bail_msg(rc, c->c.err); };
-                    if (units.empty()) return;
-                    std::string uw;
-                    if (pf) {
-                        const int rr = m->ensure_ring(d, ring_need, uw);
-                        if (rr != FRIEDA_OK) return bail_msg(rr, uw);
-                    }
-                    auto upload = [&](size_t u) {
-                        const uint32_t i0 = (uint32_t)d + units[u].slot * (uint32_t)n;
-                        std::vector<const uint8_t*> ptrs(units[u].cnt);
-                        for (uint32_t k = 0; k < units[u].cnt; k++) ptrs[k] = blobs[i0 + k * n];
-                        return m->upload(d, (uint32_t)(u % RING_SLOTS), ptrs.data(), lens[i0], units[u].cnt, uw);
-                    };
-                    auto begin = [&](size_t u) {
-                        const uint32_t i0 = (uint32_t)d + units[u].slot * (uint32_t)n;
-                        Ctx* c = &cx[u & 1]->c;
-                        if (pf) {
-                            if (hipStreamWaitEvent(c->stream, m->ring[d].ready[u % RING_SLOTS], 0) != hipSuccess)
-                                return c->fail(FRIEDA_ERR_HIP, "hipStreamWaitEvent(blob upload)");
-                            return commit_batch_begin(c, m->ring[d].slot[u % RING_SLOTS], ring_stride(lens[i0]), lens[i0], units[u].cnt, true,
-                                                      log_blowup_factor, nullptr);
-                        }
-                        std::vector<const uint8_t*> ptrs(units[u].cnt);
-                        for (uint32_t k = 0; k < units[u].cnt; k++) ptrs[k] = blobs[i0 + k * n];
-                        return commit_batch_begin(c, ptrs[0], lens[i0], lens[i0], units[u].cnt, false, log_blowup_factor, ptrs.data());
-                    };
-                    int rc = FRIEDA_OK;
-                    for (size_t u = 0; pf && u < 2 && u < units.size() && rc == FRIEDA_OK; u++) rc = upload(u);
-                    if (rc != FRIEDA_OK) return bail_msg(rc, uw);
-                    rc = begin(0);
-                    if (rc != FRIEDA_OK) return bail(rc, cx[0]);
-                    for (size_t u = 0; u < units.size(); u++) {
-                        bool next_begun = false;
-                        if (u + 1 < units.size() && !abort.load()) {
-                            rc = begin(u + 1);
-                            if (rc != FRIEDA_OK) bail(rc, cx[(u + 1) & 1]);
-                            next_begun = rc == FRIEDA_OK;
-                        }
-                        if (pf && u + 2 < units.size() && !abort.load()) {  // slot (u + 2) % 3 held unit u - 1, which has finished
-                            rc = upload(u + 2);
-                            if (rc != FRIEDA_OK) bail_msg(rc, uw);
-                        }
-                        const int rf = commit_batch_finish(&cx[u & 1]->c, local[d][units[u].slot].data());
-                        if (rf != FRIEDA_OK)
-                            bail(rf, cx[u & 1]);
-                        else
-                            done = units[u].slot + units[u].cnt;
-                        if (pass_st != FRIEDA_OK || abort.load()) {
-                            if (next_begun) {
-                                std::vector<uint8_t> r(32 * (size_t)units[u + 1].cnt);
-                                (void)commit_batch_finish(&cx[(u + 1) & 1]->c, r.data());
-                            }
-                            return;
-                        }
-                    }
-                    };  // pass
-                    pass();
-                    if (pass_st == FRIEDA_ERR_NOMEM && largest > 1 && !abort.load() && shrink < 16) {
-                        m->drop_device_workspace(d, pf);  // (synchronises the contexts' streams and the copy stream first)
-                        shrink++;
-                        continue;
-                    }
-                    if (pass_st != FRIEDA_OK) {
-                        status[d] = pass_st;
-                        what[d] = pass_msg;
-                        abort.store(true);
-                    }
-                    return;
-                    }  // passes
-                } catch (...) {  // nothing may unwind out of a worker thread
-                    what[d] = "host allocation failed";
-                    status[d] = FRIEDA_ERR_NOMEM;
-                    abort.store(true);
-                    for (frieda_ctx* c : cx)
-                        if (c->c.commit_pending) {
-                            (void)hipStreamSynchronize(c->c.stream);
-                            c->c.commit_pending = 0;
-                        }
-                }
-            });
-        }
-        for (auto& w : workers) w.join();
-        for (size_t d = 0; d < n; d++)
-            if (status[d] != FRIEDA_OK) return m->fail(status[d], "device " + std::to_string(m->devices[d]) + ": " + what[d]);
-        return m->gather_roots(local, count, out_roots);
+        std::vector<std::vector<Hash32>> local;
+        const int rc = run_on_devices(m, blobs, lens, count, CommitOps{blobs, lens, log_blowup_factor, 0}, local);
+        return rc != FRIEDA_OK ? rc : m->gather_roots(local, count, out_roots);
     } catch (const std::bad_alloc&) {
         return m->fail(FRIEDA_ERR_NOMEM, "host allocation failed");
     } catch (const std::exception& e) {
@@ -723,197 +770,19 @@ int frieda_prove_many(frieda_multi* m, const uint8_t* const* blobs, const size_t
         out_proofs[i] = nullptr;
         if (!blobs[i] && lens[i]) return m->fail(FRIEDA_ERR_ARG, "null blob");
     }
+    int rc;
     try {
-        const size_t n = m->devices.size();
-        std::vector<std::vector<Hash32>> local(n);
-        std::vector<int> status(n, FRIEDA_OK);
-        std::vector<std::string> what(n);
-        std::atomic<bool> abort{false};
-        std::vector<std::thread> workers;
-        JoinAll join_guard{workers};
-        for (size_t d = 0; d < n; d++) local[d].resize((count + n - 1 - d) / n);
-        for (size_t d = 0; d < n; d++) {
-            workers.emplace_back([&, d] {
-              pin_this_thread(m->near_cpus[d]);
-              const bool pf = m->prefetch;
-              struct DrainUploads {  // no upload may still be reading the caller's blobs when the worker returns
-                  frieda_multi* m;
-                  size_t d;
-                  bool on;
-                  ~DrainUploads() {
-                      if (on) (void)hipStreamSynchronize(m->ring[d].stream);
-                  }
-              } drain_uploads{m, d, pf};
-              try {
-                // This device's blobs in order, cut into units (cut_device_units: a run of blobs of one length goes through the
-                // batched kernels, as many per call as the batch policy's workspace budget allows — the Fiat-Shamir chain is paid
-                // once per unit —, anything else is a single proof).  Two units in
-                // flight: begin(u + 1) is enqueued on the other context before finish(u) waits; the blobs of unit u + 2 are
-                // uploaded on the copy stream meanwhile.
-                frieda_ctx* cx[2] = {m->ctx[2 * d], m->ctx[2 * d + 1]};
-                cx[1]->c.tuning.test_arena_limit = cx[0]->c.tuning.test_arena_limit;  // (test hook set through frieda_multi_ctx: the slot's both contexts)
-                const uint32_t mine = (uint32_t)local[d].size();
-                if (mine == 0) return;
-                // batches need the device transcript (prover.cpp): small last layers, and neither context switched to the host channel
-                // through frieda_multi_ctx (then equal-length runs go as single proofs instead of failing)
-                const bool batchable = cfg.log_last_layer_degree_bound <= 11 && cfg.log_blowup_factor <= 11 &&
-                                       cfg.log_last_layer_degree_bound + cfg.log_blowup_factor <= 11 && !cx[0]->c.host_channel &&
-                                       !cx[1]->c.host_channel;
-                if (hipSetDevice(m->devices[d]) != hipSuccess) {
-                    status[d] = FRIEDA_ERR_HIP;
-                    what[d] = "hipSetDevice";
-                    abort.store(true);
-                    return;
-                }
-                // passes over what is left of this device's blobs: see frieda_commit_many (a pass that ran out of device memory is
-                // repeated from its first unfinished blob with the calls halved)
-                uint32_t done = 0, shrink = 0;
-                for (;;) {
-                int pass_st = FRIEDA_OK;
-                std::string pass_msg;
-                uint32_t largest = 1;
-                auto pass = [&] {
-                std::vector<Unit> units;
-                size_t ring_need = 0;
-                cut_device_units(lens, (uint32_t)d, (uint32_t)n, mine, batchable, true, cfg.log_blowup_factor, cfg.log_last_layer_degree_bound,
-                                 cx[0]->c.tuning, pf, units, ring_need, done, m->mem_cap_now(d), shrink);
-                for (const Unit& un : units) largest = std::max(largest, un.cnt);
-                auto bail_msg = [&](int rc, const std::string& msg) {
-                    if (pass_st == FRIEDA_OK) {
-                        pass_st = rc;
-                        pass_msg = msg;
-                    }
-                };
-                auto bail = [&](int rc, frieda_ctx* c) { bail_msg(rc, c->c.err); };
-                if (units.empty()) return;
-                std::string uw;
-                if (pf) {
-                    const int rr = m->ensure_ring(d, ring_need, uw);
-                    if (rr != FRIEDA_OK) return bail_msg(rr, uw);
-                }
-                auto upload = [&](size_t u) {
-                    const uint32_t i0 = (uint32_t)d + units[u].slot * (uint32_t)n;
-                    std::vector<const uint8_t*> ptrs(units[u].cnt);
-                    for (uint32_t k = 0; k < units[u].cnt; k++) ptrs[k] = blobs[i0 + k * n];
-                    return m->upload(d, (uint32_t)(u % RING_SLOTS), ptrs.data(), lens[i0], units[u].cnt, uw);
-                };
-                auto begin = [&](size_t u) {
-                    const Unit& un = units[u];
-                    const uint32_t i0 = (uint32_t)d + un.slot * (uint32_t)n;
-                    Ctx* c = &cx[u & 1]->c;
-                    std::vector<const uint8_t*> ptrs_v(un.cnt);
-                    std::vector<uint64_t> sd_v(un.cnt);
-                    const uint8_t** ptrs = ptrs_v.data();
-                    uint64_t* sd = sd_v.data();
-                    for (uint32_t k = 0; k < un.cnt; k++) {
-                        ptrs[k] = blobs[i0 + k * n];
-                        sd[k] = seeds ? seeds[i0 + k * n] : 0;
-                    }
-                    if (pf) {
-                        if (hipStreamWaitEvent(c->stream, m->ring[d].ready[u % RING_SLOTS], 0) != hipSuccess)
-                            return c->fail(FRIEDA_ERR_HIP, "hipStreamWaitEvent(blob upload)");
-                        const uint8_t* dev = m->ring[d].slot[u % RING_SLOTS];
-                        if (un.cnt == 1) return prove_begin(c, dev, lens[i0], true, seeds ? &seeds[i0] : nullptr, cfg);
-                        return prove_begin_batch(c, dev, ring_stride(lens[i0]), lens[i0], un.cnt, true, seeds ? sd : nullptr, cfg);
-                    }
-                    if (un.cnt == 1) return prove_begin(c, blobs[i0], lens[i0], false, seeds ? &seeds[i0] : nullptr, cfg);
-                    return prove_begin_batch_ptrs(c, ptrs, lens[i0], un.cnt, seeds ? sd : nullptr, cfg);
-                };
-                auto finish = [&](size_t u) {  // -> status; fills local roots and out_proofs of the unit
-                    const Unit& un = units[u];
-                    frieda_ctx* c = cx[u & 1];
-                    std::vector<frieda_proof*> objs(un.cnt, nullptr);
-                    std::vector<ProofData> outs(un.cnt);
-                    for (uint32_t k = 0; k < un.cnt; k++) {
-                        objs[k] = c->pool->get();
-                        objs[k]->home = c->pool;
-                        outs[k] = std::move(objs[k]->p);
-                    }
-                    const int rf = prove_finish_batch(&c->c, local[d][un.slot].data(), outs);
-                    for (uint32_t k = 0; k < un.cnt; k++) {
-                        if (k < outs.size()) objs[k]->p = std::move(outs[k]);
-                        if (rf != FRIEDA_OK)
-                            c->pool->put(objs[k]);
-                        else
-                            out_proofs[(uint32_t)d + (un.slot + k) * (uint32_t)n] = objs[k];
-                    }
-                    return rf;
-                };
-                int rc = FRIEDA_OK;
-                for (size_t u = 0; pf && u < 2 && u < units.size() && rc == FRIEDA_OK; u++) rc = upload(u);
-                if (rc != FRIEDA_OK) return bail_msg(rc, uw);
-                rc = begin(0);
-                if (rc != FRIEDA_OK) return bail(rc, cx[0]);
-                for (size_t u = 0; u < units.size(); u++) {
-                    bool next_begun = false;
-                    if (u + 1 < units.size() && !abort.load()) {
-                        rc = begin(u + 1);
-                        if (rc != FRIEDA_OK) bail(rc, cx[(u + 1) & 1]);
-                        next_begun = rc == FRIEDA_OK;
-                    }
-                    if (pf && u + 2 < units.size() && !abort.load()) {  // slot (u + 2) % 3 held unit u - 1, which has finished
-                        rc = upload(u + 2);
-                        if (rc != FRIEDA_OK) bail_msg(rc, uw);
-                    }
-                    const int rf = finish(u);
-                    if (rf != FRIEDA_OK)
-                        bail(rf, cx[u & 1]);
-                    else
-                        done = units[u].slot + units[u].cnt;
-                    if (pass_st != FRIEDA_OK || abort.load()) {
-                        if (next_begun) drain_ctx(cx[(u + 1) & 1]);  // the unit already enqueued: the context must stay reusable
-                        return;
-                    }
-                }
-                };  // pass
-                pass();
-                if (pass_st == FRIEDA_ERR_NOMEM && largest > 1 && !abort.load() && shrink < 16) {
-                    m->drop_device_workspace(d, pf);  // (synchronises the contexts' streams and the copy stream first)
-                    shrink++;
-                    continue;
-                }
-                if (pass_st != FRIEDA_OK) {
-                    status[d] = pass_st;
-                    what[d] = pass_msg;
-                    abort.store(true);
-                }
-                return;
-                }  // passes
-              } catch (...) {  // nothing may unwind out of a worker thread
-                  status[d] = FRIEDA_ERR_NOMEM;
-                  what[d] = "host allocation failed";
-                  abort.store(true);
-                  drain_ctx(m->ctx[2 * d]);
-                  drain_ctx(m->ctx[2 * d + 1]);
-              }
-            });
-        }
-        for (auto& w : workers) w.join();
-        int rc = FRIEDA_OK;
-        for (size_t d = 0; d < n && rc == FRIEDA_OK; d++)
-            if (status[d] != FRIEDA_OK) rc = m->fail(status[d], "device " + std::to_string(m->devices[d]) + ": " + what[d]);
-        if (rc == FRIEDA_OK && abort.load()) rc = m->fail(FRIEDA_ERR_INVARIANT, "internal: aborted without a status");
+        std::vector<std::vector<Hash32>> local;
+        const ProveOps ops{blobs, lens, seeds, cfg, cfg.log_blowup_factor, cfg.log_last_layer_degree_bound, out_proofs};
+        rc = run_on_devices(m, blobs, lens, count, ops, local);
         if (rc == FRIEDA_OK) rc = m->gather_roots(local, count, out_commitments);
-        if (rc != FRIEDA_OK)
-            for (uint32_t i = 0; i < count; i++) {
-                if (out_proofs[i]) frieda_proof_free(out_proofs[i]);
-                out_proofs[i] = nullptr;
-            }
-        return rc;
     } catch (const std::bad_alloc&) {
-        // (the workers have been joined by JoinAll; whatever they published is handed back to nobody)
-        for (uint32_t i = 0; i < count; i++) {
-            if (out_proofs[i]) frieda_proof_free(out_proofs[i]);
-            out_proofs[i] = nullptr;
-        }
-        return m->fail(FRIEDA_ERR_NOMEM, "host allocation failed");
+        rc = m->fail(FRIEDA_ERR_NOMEM, "host allocation failed");
     } catch (const std::exception& e) {
-        for (uint32_t i = 0; i < count; i++) {
-            if (out_proofs[i]) frieda_proof_free(out_proofs[i]);
-            out_proofs[i] = nullptr;
-        }
-        return m->fail(FRIEDA_ERR_INVARIANT, e.what());
+        rc = m->fail(FRIEDA_ERR_INVARIANT, e.what());
     }
+    if (rc != FRIEDA_OK) free_out_proofs(out_proofs, count);  // (the workers have been joined: what they published is handed back to nobody)
+    return rc;
 }
 
 }  // extern "C"

@@ -764,6 +764,40 @@ def test_multi_context_python_and_rccl_failure_is_loud(gpu_ctx, oracle, monkeypa
         frieda_amd.MultiContext([99])
 
 
+def test_many_entry_points_without_the_upload_ring(gpu_ctx, oracle, monkeypatch):
+    """FRIEDA_MULTI_NO_PREFETCH=1: the units read the host blobs at begin (batches through the pointer table, the lone blob through
+    prove_begin / a batch of one) instead of the upload ring.  A run of four, a lone blob and a run of two on one device: roots and
+    proofs byte-identical to the oracle's and to those of a handle that uploads ahead; one device gathers nothing."""
+    import frieda_amd
+
+    lengths = [3000, 3000, 3000, 3000, 1024, 3000, 3000]
+    blobs = [splitmix64_bytes(700 + i, n).tobytes() for i, n in enumerate(lengths)]
+    seeds = list(range(7))
+    cfg = _cfg(frieda_amd, 8, 4, 0, 10)
+    ocfg = oracle.make_config(8, 4, 0, 10)
+    expected = [oracle.commit_and_generate_proof(b, s, ocfg) for b, s in zip(blobs, seeds)]
+    exp_roots = [r for r, _ in expected]
+    exp_proofs = [p.serialize() for _, p in expected]
+    assert exp_roots == [oracle.commit(b, 4) for b in blobs]
+
+    def run():
+        mc = frieda_amd.MultiContext([0])  # (the variable is read when the handle is created)
+        try:
+            roots = mc.commit_many(blobs, 4)
+            got = mc.prove_many(blobs, seeds, cfg)
+            assert mc.gather_count == 0
+            return roots, [r for r, _ in got], [p.serialize() for _, p in got]
+        finally:
+            mc.close()
+
+    monkeypatch.setenv("FRIEDA_MULTI_NO_PREFETCH", "1")
+    direct = run()
+    assert direct[0] == exp_roots
+    assert direct[1] == exp_roots and direct[2] == exp_proofs
+    monkeypatch.delenv("FRIEDA_MULTI_NO_PREFETCH")
+    assert run() == direct
+
+
 def test_panics_map_to_status(gpu_ctx):
     import frieda_amd
 

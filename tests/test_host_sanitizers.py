@@ -79,3 +79,11 @@ def test_channel_streamed_mix_and_draws(tmp_path):
     0 .. 9, 14 .. 17 and 2048 felts (2 and 6 felts end exactly on a block boundary), draw_block(k) is the draw of a channel whose
     n_sent is k, and mix_u64 / draw_felt on a fixed digest give the recorded words."""
     _run_host_program(tmp_path, "test_channel")
+
+
+def test_unit_pipeline_order_and_retry(tmp_path):
+    """unit_pipeline.h under UBSan, with recording fakes: the whole trace of uploads, begins, finishes and abandons of a pass (one
+    to four units, with and without the upload ring, each call failing in turn, abort set: the first error is the status, a begun
+    unit is abandoned, `done` ends behind the last finished unit), and the retry of a pass that ran out of device memory (17 cuts
+    at most, each from the first blob not done; none for single blobs, another error or an aborted call)."""
+    _run_host_program(tmp_path, "test_unit_pipeline")
