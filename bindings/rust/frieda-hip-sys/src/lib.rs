@@ -63,6 +63,7 @@ extern "C" {
     pub fn frieda_ctx_test_set_draw_bound(ctx: *mut frieda_ctx, bound: u32) -> c_int;
     pub fn frieda_ctx_test_set_grind_first_log(ctx: *mut frieda_ctx, log_first: u32) -> c_int;
     pub fn frieda_ctx_test_set_arena_limit(ctx: *mut frieda_ctx, bytes: u64) -> c_int;
+    pub fn frieda_ctx_test_set_verify_pass_bytes(ctx: *mut frieda_ctx, bytes: u64) -> c_int;
     pub fn frieda_test_near_cpus(sysfs_root: *const c_char, pci_bus_id: *const c_char, out_cpus: *mut c_int, cap: usize, n: *mut usize) -> c_int;
     pub fn frieda_test_parse_cpulist(text: *const c_char, out_cpus: *mut c_int, cap: usize, n: *mut usize) -> c_int;
     /// batch policy: device workspace one blob adds to a batched call; the cut of `count` equal-length blobs into calls
@@ -125,6 +126,12 @@ extern "C" {
     pub fn frieda_verify_samples_many(ctx: *mut frieda_ctx, proofs: *const *const frieda_proof, seeds: *const u64, count: u32, expected_commitment: *const u8, out_status: *mut u8, out_positions: *mut u32, pitch: usize, out_n_positions: *mut u32) -> c_int;
     /// verify, pool the verified samples, rebuild the blob and check it against the commitment
     pub fn frieda_reconstruct_from_proofs(ctx: *mut frieda_ctx, proofs: *const *const frieda_proof, seeds: *const u64, count: u32, expected_commitment: *const u8, len: usize, out_bytes: *mut u8, out_status: *mut u8, n_points: *mut usize) -> c_int;
+    /// verify + every point the accepted proof authenticates: both members of every opened first-layer pair (out_values: 4 words per point)
+    pub fn frieda_verify_pairs(proof: *const frieda_proof, seed: *const u64, ok: *mut c_int, out_positions: *mut u32, out_values: *mut u32, cap: usize, n_points: *mut usize) -> c_int;
+    /// the same for many proofs (row i: out_n_points[i] points, pitch apart; values 4 * pitch words apart)
+    pub fn frieda_verify_pairs_many(ctx: *mut frieda_ctx, proofs: *const *const frieda_proof, seeds: *const u64, count: u32, expected_commitment: *const u8, out_status: *mut u8, out_positions: *mut u32, out_values: *mut u32, pitch: usize, out_n_points: *mut u32) -> c_int;
+    /// frieda_reconstruct_from_proofs with the pair points as the pool: about half as many proofs needed
+    pub fn frieda_reconstruct_from_proof_pairs(ctx: *mut frieda_ctx, proofs: *const *const frieda_proof, seeds: *const u64, count: u32, expected_commitment: *const u8, len: usize, out_bytes: *mut u8, out_status: *mut u8, n_points: *mut usize) -> c_int;
 
     // struct Proof
     pub fn frieda_proof_free(p: *mut frieda_proof);

@@ -85,6 +85,7 @@ def lib():
         "frieda_ctx_test_set_draw_bound": (C.c_int, [vp, u32]),
         "frieda_ctx_test_set_grind_first_log": (C.c_int, [vp, u32]),
         "frieda_ctx_test_set_arena_limit": (C.c_int, [vp, u64]),
+        "frieda_ctx_test_set_verify_pass_bytes": (C.c_int, [vp, u64]),
         "frieda_workspace_bytes": (sz, [sz, u32, u32, C.c_int]),
         "frieda_batch_plan": (C.c_int, [vp, sz, u32, u32, C.c_int, u32, u32, C.POINTER(u32), sz, C.POINTER(u32)]),
         "frieda_ctx_set_kernel_timing": (C.c_int, [vp, C.c_int]),
@@ -136,6 +137,9 @@ def lib():
         "frieda_verify_many": (C.c_int, [vp, pp, u64p, u32, vp, vp]),
         "frieda_verify_samples_many": (C.c_int, [vp, pp, u64p, u32, vp, vp, vp, sz, vp]),
         "frieda_reconstruct_from_proofs": (C.c_int, [vp, pp, u64p, u32, vp, sz, vp, vp, C.POINTER(sz)]),
+        "frieda_verify_pairs": (C.c_int, [vp, u64p, C.POINTER(C.c_int), vp, vp, sz, C.POINTER(sz)]),
+        "frieda_verify_pairs_many": (C.c_int, [vp, pp, u64p, u32, vp, vp, vp, vp, sz, vp]),
+        "frieda_reconstruct_from_proof_pairs": (C.c_int, [vp, pp, u64p, u32, vp, sz, vp, vp, C.POINTER(sz)]),
         "frieda_proof_free": (None, [vp]),
         "frieda_proof_clone": (C.c_int, [vp, pp]),
         "frieda_proof_proof_of_work": (u64, [vp]),

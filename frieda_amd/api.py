@@ -476,6 +476,56 @@ class Context:
             raise
         return out[:n_bytes].tobytes(), status[:count], n.value
 
+    # ---- the pair forms: every point an accepted proof authenticates (frieda_verify_pairs_many, frieda_reconstruct_from_proof_pairs) ----
+    def verify_pairs_many(self, proofs, seeds=None, expected_commitment=None, pitch=None):
+        """(status, points): points[i] is the (positions uint32 [n], values uint32 [n, 4]) pair verify_pairs() returns for proof i, None
+        unless it is accepted."""
+        import numpy as np
+
+        count = len(proofs)
+        status = np.zeros(count, dtype=np.uint8)
+        if count == 0:
+            return status, []
+        if pitch is None:
+            pitch = max(1, 2 * max(int(p.pcs_config.fri_config.n_queries) for p in proofs))
+        pos = np.zeros((count, max(1, pitch)), dtype=np.uint32)
+        val = np.zeros((count, max(1, pitch), 4), dtype=np.uint32)
+        npts = np.zeros(count, dtype=np.uint32)
+        com = (C.c_uint8 * 32)(*expected_commitment) if expected_commitment is not None else None
+        _check(
+            self._L.frieda_verify_pairs_many(
+                self._h, self._proof_array(proofs), self._seeds_array(seeds, count), count, com, status.ctypes.data, pos.ctypes.data, val.ctypes.data,
+                pitch, npts.ctypes.data
+            ),
+            self._h,
+        )
+        return status, [(pos[i, : npts[i]].copy(), val[i, : npts[i]].copy()) if status[i] == _lib.VERIFY_ACCEPTED else None for i in range(count)]
+
+    def reconstruct_from_proof_pairs(self, proofs, seeds, expected_commitment, n_bytes):
+        """reconstruct_from_proofs with the pair points as the pool — both members of every first-layer pair an accepted proof opened, so
+        about half as many proofs suffice: (bytes, status, n_points).  Raises FriedaError (with .n_points and .proof_status set) as
+        reconstruct_from_proofs does."""
+        import numpy as np
+
+        count = len(proofs)
+        status = np.zeros(max(count, 1), dtype=np.uint8)
+        out = np.zeros(max(n_bytes, 1), dtype=np.uint8)
+        n = C.c_size_t(0)
+        com = (C.c_uint8 * 32)(*expected_commitment)
+        try:
+            _check(
+                self._L.frieda_reconstruct_from_proof_pairs(
+                    self._h, self._proof_array(proofs) if count else None, self._seeds_array(seeds, count), count, com, n_bytes, out.ctypes.data,
+                    status.ctypes.data, C.byref(n)
+                ),
+                self._h,
+            )
+        except FriedaError as e:
+            e.n_points = n.value
+            e.proof_status = status[:count]
+            raise
+        return out[:n_bytes].tobytes(), status[:count], n.value
+
 
 class Encoded:
     """An encoded blob on the device (frieda_encoded): evaluations + first-layer tree + root, in an allocation of its own that outlives
@@ -872,6 +922,34 @@ def verify_samples(proof, seed):
     if not ok.value:
         return False, None
     return True, buf[: n.value].copy()
+
+
+def verify_pairs(proof, seed):
+    """verify + every point the accepted proof authenticates (frieda_verify_pairs, host-only): (ok, positions, values) with positions the
+    ascending distinct positions of both members of every opened first-layer pair and values[i] the four column words at positions[i]
+    — from proof.evaluations where the position was queried, from the first layer's fri_witness otherwise; (False, None, None) when the
+    proof is rejected."""
+    import numpy as np
+
+    ok = C.c_int(0)
+    n = C.c_size_t(0)
+    cap = max(1, 2 * int(proof.pcs_config.fri_config.n_queries))
+    pos = np.zeros(cap, dtype=np.uint32)
+    val = np.zeros((cap, 4), dtype=np.uint32)
+    _check(_lib.lib().frieda_verify_pairs(proof._h, _seed_ptr(seed), C.byref(ok), pos.ctypes.data, val.ctypes.data, cap, C.byref(n)))
+    if not ok.value:
+        return False, None, None
+    return True, pos[: n.value].copy(), val[: n.value].copy()
+
+
+def verify_pairs_many(proofs, seeds=None, expected_commitment=None):
+    """frieda_verify_pairs_many on the default context: (status, [(positions, values) or None])."""
+    return default_context().verify_pairs_many(proofs, seeds, expected_commitment)
+
+
+def reconstruct_from_proof_pairs(proofs, seeds, expected_commitment, n_bytes):
+    """frieda_reconstruct_from_proof_pairs on the default context: (bytes, status, n_points)."""
+    return default_context().reconstruct_from_proof_pairs(proofs, seeds, expected_commitment, n_bytes)
 
 
 def verify_many(proofs, seeds=None, expected_commitment=None):

@@ -198,6 +198,12 @@ int frieda_ctx_test_set_arena_limit(frieda_ctx* ctx, uint64_t bytes) {
     return FRIEDA_OK;
 }
 
+int frieda_ctx_test_set_verify_pass_bytes(frieda_ctx* ctx, uint64_t bytes) {
+    if (!ctx) return FRIEDA_ERR_ARG;
+    ctx->c.tuning.test_verify_pass_bytes = bytes;
+    return FRIEDA_OK;
+}
+
 size_t frieda_workspace_bytes(size_t len, uint32_t log_blowup_factor, uint32_t log_last_layer_degree_bound, int prove) {
     return workspace_bytes_per_blob(len, log_blowup_factor, log_last_layer_degree_bound, prove != 0, true);
 }
@@ -547,6 +553,27 @@ int frieda_verify_samples(const frieda_proof* proof, const uint64_t* seed, int* 
     *n_positions = q.size();
     if (cap < q.size()) return FRIEDA_ERR_ARG;
     if (!q.empty()) memcpy(out_positions, q.data(), 4 * q.size());
+    return FRIEDA_OK;
+    FR_GUARD_END(none)
+}
+
+int frieda_verify_pairs(const frieda_proof* proof, const uint64_t* seed, int* ok, uint32_t* out_positions, uint32_t* out_values, size_t cap,
+                        size_t* n_points) {
+    if (!proof || !ok || !n_points || (cap && (!out_positions || !out_values))) return FRIEDA_ERR_ARG;
+    frieda_ctx* none = nullptr;
+    FR_GUARD_BEGIN
+    *n_points = 0;
+    std::vector<uint32_t> q;
+    PairPoints pp;
+    const int rc = verify(proof->p, seed, ok, &q, &pp);
+    if (rc != FRIEDA_OK || !*ok) return rc;
+    if (q.size() != proof->p.evaluations.size()) return FRIEDA_ERR_INVARIANT;  // (the rule of frieda_verify_samples)
+    *n_points = pp.pos.size();
+    if (cap < pp.pos.size()) return FRIEDA_ERR_ARG;
+    if (!pp.pos.empty()) {
+        memcpy(out_positions, pp.pos.data(), 4 * pp.pos.size());
+        memcpy(out_values, pp.val.data(), 16 * pp.val.size());
+    }
     return FRIEDA_OK;
     FR_GUARD_END(none)
 }

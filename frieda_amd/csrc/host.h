@@ -218,14 +218,46 @@ void batch_cut(uint32_t count, uint32_t per_call, uint32_t in_flight, std::vecto
 // returns FRIEDA_OK with *ok set, or FRIEDA_ERR_INVARIANT where the reference panics
 // out_queries (optional): on acceptance, the sorted distinct query positions the transcript sampled — evaluations[i] of the proof is
 // the value of the 4 columns at position out_queries[i] of the bit-reversed codeword (src/proof.rs:62-66)
-int verify(const ProofData& proof, const uint64_t* seed, int* ok, std::vector<uint32_t>* out_queries = nullptr);
+// out_pairs (optional): on acceptance, both members of every opened first-layer pair {2v, 2v + 1} — ascending distinct positions and
+// their column values, from `evaluations` where the position was queried and from first_layer.fri_witness otherwise.  The verifier
+// hashed every one of them into the Merkle path it checked against the commitment: a sibling is as verified as an evaluation.
+struct PairPoints {
+    std::vector<uint32_t> pos;
+    std::vector<QM31> val;
+};
+int verify(const ProofData& proof, const uint64_t* seed, int* ok, std::vector<uint32_t>* out_queries = nullptr, PairPoints* out_pairs = nullptr);
 
+// Pairs mode of verify_many (frieda_verify_pairs_many, frieda_reconstruct_from_proof_pairs): the pair points of every accepted proof, pooled
+// in the caller's order.  The kernel's proofs leave theirs in a device allocation of the call's own (not the arena: the verify passes
+// and the reconstruction re-plan it), gathered there pass by pass (k::verify_pairs_gather); host-route proofs keep theirs in `host`
+// until upload_host_rows.  Entry e: d_pos()[e], d_val()[4 e .. 4 e + 3] — the cell layout of the point reconstruction (log_cell 0).
+struct PairPool {
+    uint8_t* d = nullptr;
+    size_t cap = 0, n = 0;            // entries allocated / pooled
+    std::vector<size_t> off;          // per proof: its first entry
+    std::vector<uint32_t> cnt;        // per proof: its entries (0 unless accepted)
+    std::vector<PairPoints> host;     // per proof: the points of an accepted host-route proof
+    uint32_t* d_pos() const { return reinterpret_cast<uint32_t*>(d); }
+    uint32_t* d_val() const { return reinterpret_cast<uint32_t*>(d + ((4 * cap + 255) & ~(size_t)255)); }
+    int upload_host_rows(Ctx* ctx);   // synchronous; a no-op without host-route proofs
+    PairPool() = default;
+    PairPool(const PairPool&) = delete;
+    PairPool& operator=(const PairPool&) = delete;
+    ~PairPool();
+};
 // Many proofs in one call (verify_many.cpp, verify.hip): out_status[i] = a k::VerifyStatus, per proof the result of verify() whatever the
 // route (device passes for the shapes the kernel takes, from Tuning::verify_device_min eligible proofs on; verify() for the rest).
 // samples: an accepted proof must also hold one evaluation per distinct query (frieda_verify_samples), else VERIFY_INVARIANT;
 // positions (optional): the sampled positions of every accepted proof.  Uses the arena and the pinned block (callers: FR_NO_JOB).
+// pairs (optional, with samples): the pairs mode above.
 int verify_many(Ctx* ctx, const ProofData* const* proofs, const uint64_t* seeds, uint32_t count, const uint8_t* expected_commitment, bool samples,
-                uint8_t* out_status, std::vector<std::vector<uint32_t>>* positions);
+                uint8_t* out_status, std::vector<std::vector<uint32_t>>* positions, PairPool* pairs = nullptr);
+// frieda_reconstruct_points_device (log_cell 0, 4 columns) with the positions already on the device: d_index[n_points] next to
+// d_cells[n_points][4].  *n_distinct receives the number of distinct positions whenever the call got as far as counting them (it is
+// what decides the "fewer than 2^log_coef + 2" error); count_distinct_points stops there.
+int reconstruct_points_pooled(frieda_ctx* ctx, const uint32_t* d_cells, const uint32_t* d_index, uint32_t n_points, uint32_t log_coef, uint32_t log_domain,
+                              size_t len, void* d_out_bytes, uint32_t* n_distinct);
+int count_distinct_points(frieda_ctx* ctx, const uint32_t* d_index, uint32_t n_points, uint32_t log_domain, uint32_t* n_distinct);
 
 // transcript pieces shared by prover and verifier (transcript.cpp)
 void channel_mix_felts(Channel& ch, const std::vector<QM31>& felts);

@@ -70,6 +70,7 @@ struct Tuning {
     bool lds_opt_in_ok = true;           // the 68 KB dynamic-LDS opt-in of the transform kernels was granted: gates FRIEDA_NTT_CPW = 4 and the
                                          // four-columns-side-by-side fold2 kernel (ntt.hip), also against a later set_option
     uint64_t test_arena_limit = 0;       // test hook (frieda_ctx_test_set_arena_limit): ensure_arena refuses more than this many bytes (0 = off)
+    uint64_t test_verify_pass_bytes = 0; // test hook (frieda_ctx_test_set_verify_pass_bytes): staging budget of one verify pass (0 = the default, 32 MB)
 };
 // trees of a proof with at least 2^(this) leaves are built without the two levels above their leaves (tree.hip TreeArgs::skip_bc,
 // decommit.hip node_from_values, prover.cpp's host-planner fallback): ONE rule for the three places, by the blobs of the call
@@ -364,10 +365,19 @@ struct VerifyArgs {
     const uint32_t* img;
     uint32_t* out;   // per proof 2 + q_cap words: status, number of distinct queries, the queries (ascending)
     uint32_t q_cap;  // >= 64, a power of two, >= every proof's n_queries
+    // pairs mode (both set, 16-byte aligned; else both null).  The output row is 3 + q_cap words: status, number of distinct queries,
+    // number of opened first-layer pairs, the queries.  Row `slot` of pair_pos ([2 * q_cap] positions) and pair_val ([2 * q_cap][4] words)
+    // receives both members of every opened pair, ascending — meaningful only where the row's final status is VERIFY_ACCEPTED.
+    uint32_t* pair_pos = nullptr;
+    uint32_t* pair_val = nullptr;
 };
 size_t verify_many_lds_bytes(uint32_t q_cap);
 hipError_t verify_many_init(const CPoint (&gen_pow2)[31]);  // uploads the generator's doublings (once per device)
 void verify_many(const Launch& L, const VerifyArgs& a, uint32_t n_proofs);
+// rows of a pass's pair buffer -> the call's pool.  d_tab[n_rows][3]: row (slot of the pass), entries (2 * pairs), first pool entry;
+// d_pool_pos[entry], d_pool_val[entry][4]: 16-byte aligned, as d_pair_val
+void verify_pairs_gather(const Launch& L, const uint32_t* d_tab, uint32_t n_rows, const uint32_t* d_pair_pos, const uint32_t* d_pair_val, uint32_t q_cap,
+                         uint32_t* d_pool_pos, uint32_t* d_pool_val);
 
 // ---- opening.hip: Level B openings (frieda_dev_gather*, frieda_merkle_decommit*) ----
 constexpr uint32_t OPEN_BAD_WORD = 0xFFFFFFFFu;   // gathered word of an out-of-range index (device forms only; not a canonical M31)

@@ -221,8 +221,12 @@ int frieda_reconstruct_cells_device(frieda_ctx* ctx, const uint32_t* d_cells, co
 namespace {
 // coefficients of `ncols` columns into d_coef[ncols][2^log_coef], or — d_coef == nullptr — into the start of the arena (arena_off bytes
 // reserved there by the caller).  Cells as in interpolate_cells (runs of 2^log_cell entries; repeated cells are dropped).
+// d_index (optional, then cell_index is not read): the cell list already on the device, outside the arena — no copy of it is made.
+// n_distinct (optional): receives the number of distinct cells offered; the argument checks that need it are then made on that number
+// alone, so that it is reported with the error.
 int interpolate_points(frieda_ctx* ctx, const uint32_t* d_cells, const uint32_t* cell_index, uint32_t n_cells, uint32_t ncols, uint32_t log_cell,
-                       uint32_t log_coef, uint32_t log_domain, uint32_t* d_coef, size_t arena_off) {
+                       uint32_t log_coef, uint32_t log_domain, uint32_t* d_coef, size_t arena_off, const uint32_t* d_index = nullptr,
+                       uint32_t* n_distinct = nullptr) {
     Ctx& c = ctx->c;
     FR_NO_JOB(&c);
     if (log_cell > log_domain || log_coef > log_domain || log_coef < 1 || log_domain < 2 || log_domain + 1 > FRIEDA_MAX_LOG_DOMAIN)
@@ -236,7 +240,7 @@ int interpolate_points(frieda_ctx* ctx, const uint32_t* d_cells, const uint32_t*
     // 2^69); every 32-bit position computed in erasure.hip relies on this bound
     if ((uint64_t)n_cells > (0x100000000ull >> log_cell) / ncols) return c.fail(FRIEDA_ERR_ARG, "points: sample buffer beyond 2^32 words");
     const size_t s_cap = (size_t)n_cells << log_cell;  // points offered, repeats included
-    if (s_cap < K + 2)
+    if (s_cap < K + 2 && !n_distinct)
         return c.fail(FRIEDA_ERR_ARG, "points: need at least 2^log_coef + 2 distinct points (the locator polynomial needs two spare samples)");
     // S, the points the locator is built from (all offered points serve the check): the first K + 2 single points, Z_S a product of
     // lines through pairs — or, for samples in cells of M >= 2 entries, the first K / M + 1 whole cells, Z_S a product over cells.
@@ -251,7 +255,7 @@ int interpolate_points(frieda_ctx* ctx, const uint32_t* d_cells, const uint32_t*
     const uint32_t s_use = by_cells ? (uint32_t)((size_t)n_use_cells << log_cell) : (uint32_t)K + 2;
     const uint32_t n_lines = by_cells ? n_use_cells : s_use / 2;  // factors of Z_S
     const bool by_tree = !by_cells && log_coef >= tree_min_log;
-    if (s_use > s_cap) return c.fail(FRIEDA_ERR_ARG, "points: cells of 2^log_cell entries: need 2^(log_coef - log_cell) + 1 distinct cells");
+    if (s_use > s_cap && !n_distinct) return c.fail(FRIEDA_ERR_ARG, "points: cells of 2^log_cell entries: need 2^(log_coef - log_cell) + 1 distinct cells");
 
     // domains: D (log n) and the next canonic domain D' (log n + 1)
     auto make_domain = [](uint32_t lg) {
@@ -276,7 +280,7 @@ int interpolate_points(frieda_ctx* ctx, const uint32_t* d_cells, const uint32_t*
     plan.off = arena_off;
     const size_t o_pos = plan.take(4 * s_cap), o_src = plan.take(4 * s_cap);
     const size_t ded_chunks = k::erasure_sample_lists_chunks(n_cells);
-    const size_t o_idx = plan.take(4 * (size_t)n_cells), o_fc = plan.take(4 * (size_t)n_cells), o_fr = plan.take(4 * (size_t)n_cells);
+    const size_t o_idx = plan.take(d_index ? 0 : 4 * (size_t)n_cells), o_fc = plan.take(4 * (size_t)n_cells), o_fr = plan.take(4 * (size_t)n_cells);
     const size_t o_own = plan.take(4 * (size_t)domain_cells), o_csum = plan.take(4 * ded_chunks), o_coff = plan.take(4 * ded_chunks), o_state = plan.take(8);
     const size_t o_la = plan.take(4 * (size_t)n_lines), o_lb = plan.take(4 * (size_t)n_lines), o_lc = plan.take(4 * (size_t)n_lines);
     const size_t s_max = std::max<size_t>(s_use, K);
@@ -298,8 +302,8 @@ int interpolate_points(frieda_ctx* ctx, const uint32_t* d_cells, const uint32_t*
     auto W32 = [&](size_t off) { return reinterpret_cast<uint32_t*>(A + off); };
     hipStream_t s = c.stream;
     const k::Launch LN = c.launch();
-    FR_HIP(&c, hipMemcpyAsync(A + o_idx, cell_index, 4 * (size_t)n_cells, hipMemcpyHostToDevice, s));
-    FR_HIP(&c, k::erasure_sample_lists(LN, W32(o_idx), n_cells, domain_cells, ncols, log_cell, W32(o_own), W32(o_csum), W32(o_coff), W32(o_fc), W32(o_fr),
+    if (!d_index) FR_HIP(&c, hipMemcpyAsync(A + o_idx, cell_index, 4 * (size_t)n_cells, hipMemcpyHostToDevice, s));
+    FR_HIP(&c, k::erasure_sample_lists(LN, d_index ? d_index : W32(o_idx), n_cells, domain_cells, ncols, log_cell, W32(o_own), W32(o_csum), W32(o_coff), W32(o_fc), W32(o_fr),
                             W32(o_state), W32(o_pos), W32(o_src)));
     uint32_t state[2] = {0, 0};
     FR_HIP(&c, hipMemcpyAsync(state, A + o_state, 8, hipMemcpyDeviceToHost, s));
@@ -307,6 +311,7 @@ int interpolate_points(frieda_ctx* ctx, const uint32_t* d_cells, const uint32_t*
     FR_HIP(&c, hipStreamSynchronize(s));  // (cell_index is host memory of this call; the counts decide whether there is anything to do)
     FR_HIP(&c, hipGetLastError());
     if (state[1]) return c.fail(FRIEDA_ERR_ARG, "points: cell index out of range");
+    if (n_distinct) *n_distinct = state[0];
     const uint32_t s_all = (uint32_t)((size_t)state[0] << log_cell);  // distinct points offered
     if (s_all < K + 2)
         return c.fail(FRIEDA_ERR_ARG, "points: need at least 2^log_coef + 2 distinct points (the locator polynomial needs two spare samples)");
@@ -445,3 +450,49 @@ int frieda_reconstruct_points_device(frieda_ctx* ctx, const uint32_t* d_cells, c
 }
 
 }  // extern "C"
+
+namespace frieda {
+
+int reconstruct_points_pooled(frieda_ctx* ctx, const uint32_t* d_cells, const uint32_t* d_index, uint32_t n_points, uint32_t log_coef, uint32_t log_domain,
+                              size_t len, void* d_out_bytes, uint32_t* n_distinct) {
+    if (!ctx || !d_cells || !d_index || !n_distinct || (len && !d_out_bytes) || n_points == 0 || log_coef > FRIEDA_MAX_LOG_DOMAIN) return FRIEDA_ERR_ARG;
+    const size_t n_felts = (size_t)4 << log_coef;
+    if ((8 * len + 29) / 30 > n_felts) return ctx->c.fail(FRIEDA_ERR_ARG, "len does not fit the polynomial");
+    FR_HIP(&ctx->c, hipSetDevice(ctx->c.device));
+    const size_t coef_bytes = (sizeof(uint32_t) * n_felts + 255) & ~(size_t)255;
+    int rc = interpolate_points(ctx, d_cells, nullptr, n_points, 4, 0, log_coef, log_domain, nullptr, coef_bytes, d_index, n_distinct);
+    if (rc) return rc;
+    k::pack30(ctx->c.launch(), reinterpret_cast<const uint32_t*>(ctx->c.arena), n_felts, static_cast<uint8_t*>(d_out_bytes), len);
+    FR_HIP(&ctx->c, hipGetLastError());
+    return FRIEDA_OK;
+}
+
+// the de-duplication of interpolate_points alone
+int count_distinct_points(frieda_ctx* ctx, const uint32_t* d_index, uint32_t n_points, uint32_t log_domain, uint32_t* n_distinct) {
+    if (!ctx || !n_distinct || (n_points && !d_index) || log_domain > FRIEDA_MAX_LOG_DOMAIN) return FRIEDA_ERR_ARG;
+    *n_distinct = 0;
+    if (!n_points) return FRIEDA_OK;
+    Ctx& c = ctx->c;
+    FR_NO_JOB(&c);
+    FR_HIP(&c, hipSetDevice(c.device));
+    const uint32_t domain = 1u << log_domain;
+    const size_t chunks = k::erasure_sample_lists_chunks(n_points);
+    ArenaPlan plan;
+    const size_t o_pos = plan.take(4 * (size_t)n_points), o_src = plan.take(4 * (size_t)n_points), o_fc = plan.take(4 * (size_t)n_points),
+                 o_fr = plan.take(4 * (size_t)n_points), o_own = plan.take(4 * (size_t)domain), o_csum = plan.take(4 * chunks), o_coff = plan.take(4 * chunks),
+                 o_state = plan.take(8);
+    int rc = c.ensure_arena(plan.off);
+    if (rc) return rc;
+    auto W32 = [&](size_t off) { return reinterpret_cast<uint32_t*>(c.arena + off); };
+    FR_HIP(&c, k::erasure_sample_lists(c.launch(), d_index, n_points, domain, 4, 0, W32(o_own), W32(o_csum), W32(o_coff), W32(o_fc), W32(o_fr), W32(o_state),
+                                       W32(o_pos), W32(o_src)));
+    uint32_t state[2] = {0, 0};
+    FR_HIP(&c, hipMemcpyAsync(state, c.arena + o_state, 8, hipMemcpyDeviceToHost, c.stream));
+    FR_HIP(&c, hipStreamSynchronize(c.stream));
+    FR_HIP(&c, hipGetLastError());
+    if (state[1]) return c.fail(FRIEDA_ERR_ARG, "points: cell index out of range");
+    *n_distinct = state[0];
+    return FRIEDA_OK;
+}
+
+}  // namespace frieda

@@ -152,9 +152,10 @@ QM31 line_poly_eval(const QM31* coeffs, size_t n, const QM31* factors) {
 
 }  // namespace
 
-int verify(const ProofData& proof, const uint64_t* seed, int* ok, std::vector<uint32_t>* out_queries) {
+int verify(const ProofData& proof, const uint64_t* seed, int* ok, std::vector<uint32_t>* out_queries, PairPoints* out_pairs) {
     *ok = 0;
     if (out_queries) out_queries->clear();
+    if (out_pairs) out_pairs->pos.clear(), out_pairs->val.clear();
     const frieda_pcs_config& cfg = proof.pcs_config;
     const uint32_t B = cfg.log_blowup_factor, last = cfg.log_last_layer_degree_bound, L = proof.log_size_bound;
     // CirclePolyDegreeBound::fold_to_line underflows (panics) for L == 0; domain sizes outside the group do too
@@ -255,6 +256,11 @@ int verify(const ProofData& proof, const uint64_t* seed, int* ok, std::vector<ui
     }
     *ok = 1;
     if (out_queries) *out_queries = queries;
+    if (out_pairs) {
+        // what merkle_verify hashed into the first layer's leaves: both members of every opened pair
+        out_pairs->pos = se.decommitment_positions;
+        for (const auto& pr : se.subset_evals) out_pairs->val.insert(out_pairs->val.end(), pr.begin(), pr.end());
+    }
     return FRIEDA_OK;
 }
 

@@ -76,6 +76,9 @@ __device__ __forceinline__ Group group_of(const uint32_t* p, uint32_t c, uint32_
 
 __device__ __forceinline__ QM31 load_qm(const uint32_t* p) { return QM31{p[0], p[1], p[2], p[3]}; }
 
+// PAIRS: the first layer's opened pairs also go to the proof's row of a.pair_pos / a.pair_val (frieda_verify_pairs_many) — tentatively:
+// a later layer may still reject the proof, and nothing reads the row unless the final status is VERIFY_ACCEPTED.
+template <bool PAIRS>
 __global__ __launch_bounds__(64) void verify_many_kernel(VerifyArgs a) {
     extern __shared__ uint32_t lds[];
     const uint32_t Q = a.q_cap;
@@ -89,7 +92,8 @@ __global__ __launch_bounds__(64) void verify_many_kernel(VerifyArgs a) {
     const uint32_t lane = threadIdx.x, slot = blockIdx.x;
     const VerifyHeader hd = reinterpret_cast<const VerifyHeader*>(a.img)[slot];
     const uint32_t* img = a.img + hd.off_words;
-    uint32_t* out = a.out + (size_t)slot * (2 + a.q_cap);
+    constexpr uint32_t HEAD = PAIRS ? 3 : 2;  // words of the output row before the queries
+    uint32_t* out = a.out + (size_t)slot * (HEAD + a.q_cap);
     const uint32_t n = hd.n, nl = hd.n_inner, nq = hd.n_queries;
     const uint32_t* tab = img;  // per layer: n_fri_witness, n_hash_witness, n_column_witness, offset of the layer's words
     const uint32_t* last_poly = img + hd.off_last;
@@ -121,7 +125,7 @@ __global__ __launch_bounds__(64) void verify_many_kernel(VerifyArgs a) {
 
     // ---- 2. Queries::generate, sorted in s_hp and de-duplicated into s_pos ----
     const uint32_t nu = qdev::generate_queries<64>(ch, n, nq, s_hp, s_pos);
-    for (uint32_t i = lane; i < nu; i += 64) out[2 + i] = s_pos[i];
+    for (uint32_t i = lane; i < nu; i += 64) out[HEAD + i] = s_pos[i];
     if (lane == 0) out[1] = nu;
 
     // ---- 3 + 4. the layers ----
@@ -173,6 +177,17 @@ __global__ __launch_bounds__(64) void verify_many_kernel(VerifyArgs a) {
                 const uint32_t it = m31_inv(li ? pt.x : pt.y);
                 const QM31 f0 = qm_add(l, r), f1 = qm_scale(qm_sub(l, r), it);
                 const QM31 f = qm_add(f0, qm_mul(alpha, f1));
+                if constexpr (PAIRS) {
+                    if (li == 0) {
+                        // both members of the opened pair, as the leaves above hashed them: entries 2 k, 2 k + 1 of the proof's row
+                        // (k < |U_1| <= n_queries <= q_cap; positions ascend with k)
+                        const size_t e = (size_t)slot * 2 * Q + 2 * g.k;
+                        *reinterpret_cast<uint2*>(a.pair_pos + e) = make_uint2(2 * v, 2 * v + 1);
+                        uint4* pv = reinterpret_cast<uint4*>(a.pair_val + 4 * e);
+                        pv[0] = make_uint4(l.a, l.b, l.c, l.d);
+                        pv[1] = make_uint4(r.a, r.b, r.c, r.d);
+                    }
+                }
                 s_pos[g.k] = v;
                 s_ev[4 * g.k] = f.a, s_ev[4 * g.k + 1] = f.b, s_ev[4 * g.k + 2] = f.c, s_ev[4 * g.k + 3] = f.d;
             }
@@ -185,6 +200,9 @@ __global__ __launch_bounds__(64) void verify_many_kernel(VerifyArgs a) {
         }
         if (__any(bad) || wbase != nw || ncw != 0) VK_FINISH(VERIFY_REJECTED);
         c = kbase;  // |U_{li+1}|: the nodes of level m - 1
+        if constexpr (PAIRS) {
+            if (li == 0 && lane == 0) out[2] = kbase;  // the opened pairs of the first layer
+        }
         // ---- the Merkle walk of this layer: levels m - 2 .. 0 ----
         uint32_t cn = c, hbase = 0;
         for (uint32_t lv = m - 1; lv > 0; lv--) {
@@ -279,6 +297,24 @@ __global__ __launch_bounds__(64) void verify_many_kernel(VerifyArgs a) {
 #undef VK_FINISH
 }
 
+// One wave per accepted proof of a pass: row tab[3 w] of the pass's pair buffer (tab[3 w + 1] entries) -> entry tab[3 w + 2] on of the
+// call's pool: positions to pool_pos, the four column words of an entry to pool_val[.][4] — the cell layout of erasure_sample_lists /
+// interpolate_points for log_cell 0, ncols 4.  The table comes from the host, which has the counts from the status rows.
+__global__ __launch_bounds__(256) void pairs_gather_kernel(const uint32_t* __restrict__ tab, uint32_t n_rows, const uint32_t* __restrict__ pair_pos,
+                                                           const uint32_t* __restrict__ pair_val, uint32_t q_cap, uint32_t* __restrict__ pool_pos,
+                                                           uint32_t* __restrict__ pool_val) {
+    const uint32_t w = blockIdx.x * (blockDim.x / 64) + threadIdx.x / 64, lane = threadIdx.x & 63;
+    if (w >= n_rows) return;
+    const uint32_t row = tab[3 * w], cnt = tab[3 * w + 1];
+    const size_t src = (size_t)row * 2 * q_cap, dst = tab[3 * w + 2];
+    const uint4* sv = reinterpret_cast<const uint4*>(pair_val) + src;
+    uint4* dv = reinterpret_cast<uint4*>(pool_val) + dst;
+    for (uint32_t i = lane; i < cnt; i += 64) {
+        pool_pos[dst + i] = pair_pos[src + i];
+        dv[i] = sv[i];
+    }
+}
+
 }  // namespace
 
 size_t verify_many_lds_bytes(uint32_t q_cap) { return sizeof(uint32_t) * 14 * (size_t)q_cap; }
@@ -287,7 +323,17 @@ hipError_t verify_many_init(const CPoint (&gen_pow2)[31]) { return hipMemcpyToSy
 
 void verify_many(const Launch& L, const VerifyArgs& a, uint32_t n_proofs) {
     Scope scope(L, "verify_many", 0.0);
-    verify_many_kernel<<<dim3(n_proofs), 64, verify_many_lds_bytes(a.q_cap), L.stream>>>(a);
+    if (a.pair_pos)
+        verify_many_kernel<true><<<dim3(n_proofs), 64, verify_many_lds_bytes(a.q_cap), L.stream>>>(a);
+    else
+        verify_many_kernel<false><<<dim3(n_proofs), 64, verify_many_lds_bytes(a.q_cap), L.stream>>>(a);
+}
+
+void verify_pairs_gather(const Launch& L, const uint32_t* d_tab, uint32_t n_rows, const uint32_t* d_pair_pos, const uint32_t* d_pair_val, uint32_t q_cap,
+                         uint32_t* d_pool_pos, uint32_t* d_pool_val) {
+    if (!n_rows) return;
+    Scope scope(L, "verify_pairs_gather", 0.0);
+    pairs_gather_kernel<<<dim3((n_rows + 3) / 4), 256, 0, L.stream>>>(d_tab, n_rows, d_pair_pos, d_pair_val, q_cap, d_pool_pos, d_pool_val);
 }
 
 }  // namespace k

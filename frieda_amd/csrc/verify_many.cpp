@@ -1,4 +1,5 @@
-// verify_many.cpp — frieda_verify_many / frieda_verify_samples_many / frieda_reconstruct_from_proofs: the host side of verify.hip.
+// verify_many.cpp — frieda_verify_many / frieda_verify_samples_many / frieda_reconstruct_from_proofs and their pair forms
+// (frieda_verify_pairs_many / frieda_reconstruct_from_proof_pairs): the host side of verify.hip.
 //
 // Per proof the result is that of verifier.cpp::verify, whatever the route.  The checks that hash nothing and that the reference makes
 // before anything else run here (the L, L + B range, InvalidNumFriLayers, LastLayerDegreeInvalid): such a proof has its status without
@@ -7,7 +8,8 @@
 // a shape the kernel does not take (more than VERIFY_MAX_QUERIES queries, a last layer above DT_MAX_LAST_POLY, more than DT_MAX_LAYERS
 // layers, no queries at all) go through verify() inside the same call.  The rest is flattened into the context's pinned staging block
 // in passes bounded by PASS_BYTES — header, layer table, words — uploaded, verified by one launch per pass, and one status word and
-// the sampled positions per proof come back.
+// the sampled positions per proof come back.  In pairs mode the kernel also leaves both members of every opened first-layer pair in a
+// per-pass buffer; once the statuses are known, a gather launch copies the rows of the accepted proofs into the call's PairPool.
 #include <string.h>
 
 #include <algorithm>
@@ -20,7 +22,7 @@ namespace frieda {
 
 namespace {
 
-constexpr size_t PASS_BYTES = (size_t)32 << 20;  // staging budget of one upload (a lone larger proof is a pass of its own)
+constexpr size_t PASS_BYTES = (size_t)32 << 20;  // staging budget of one upload (a lone larger proof is a pass of its own); test hook: Tuning::test_verify_pass_bytes
 
 size_t image_words(const ProofData& p) {
     size_t w = 4 * (p.inner_layers.size() + 1);
@@ -91,10 +93,10 @@ bool device_shape(const ProofData& p) {
            image_words(p) < ((size_t)1 << 30);
 }
 
-void host_route(const ProofData& p, const uint64_t* seed, bool samples, uint8_t& status, std::vector<uint32_t>* pos) {
+void host_route(const ProofData& p, const uint64_t* seed, bool samples, uint8_t& status, std::vector<uint32_t>* pos, PairPoints* pairs) {
     int ok = 0;
     std::vector<uint32_t> q;
-    const int rc = verify(p, seed, &ok, &q);
+    const int rc = verify(p, seed, &ok, &q, pairs);
     if (rc != FRIEDA_OK)
         status = k::VERIFY_INVARIANT;
     else if (!ok)
@@ -104,6 +106,7 @@ void host_route(const ProofData& p, const uint64_t* seed, bool samples, uint8_t&
     else
         status = k::VERIFY_ACCEPTED;
     if (pos && status == k::VERIFY_ACCEPTED) *pos = std::move(q);
+    if (pairs && status != k::VERIFY_ACCEPTED) pairs->pos.clear(), pairs->val.clear();
 }
 
 int init_device_tables(Ctx* ctx) {
@@ -118,11 +121,60 @@ int init_device_tables(Ctx* ctx) {
     return FRIEDA_OK;
 }
 
+int pool_alloc(Ctx* ctx, PairPool& pool) {
+    if (pool.d || !pool.cap) return FRIEDA_OK;
+    FR_HIP(ctx, hipSetDevice(ctx->device));
+    void* d = nullptr;
+    const hipError_t e = hipMalloc(&d, ((4 * pool.cap + 255) & ~(size_t)255) + 16 * pool.cap);
+    if (e != hipSuccess) {
+        ctx->err = std::string("hipMalloc: ") + hipGetErrorString(e);
+        return FRIEDA_ERR_NOMEM;
+    }
+    pool.d = static_cast<uint8_t*>(d);
+    return FRIEDA_OK;
+}
+
 }  // namespace
 
+PairPool::~PairPool() {
+    if (d) (void)hipFree(d);
+}
+
+int PairPool::upload_host_rows(Ctx* ctx) {
+    bool any = false;
+    for (size_t i = 0; i < host.size(); i++) {
+        if (host[i].pos.empty()) continue;
+        if (!any) {
+            const int rc = pool_alloc(ctx, *this);
+            if (rc) return rc;
+            any = true;
+        }
+        FR_HIP(ctx, hipMemcpyAsync(d_pos() + off[i], host[i].pos.data(), 4 * host[i].pos.size(), hipMemcpyHostToDevice, ctx->stream));
+        FR_HIP(ctx, hipMemcpyAsync(d_val() + 4 * off[i], host[i].val.data(), 16 * host[i].val.size(), hipMemcpyHostToDevice, ctx->stream));
+    }
+    if (any) FR_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return FRIEDA_OK;
+}
+
 int verify_many(Ctx* ctx, const ProofData* const* proofs, const uint64_t* seeds, uint32_t count, const uint8_t* expected_commitment, bool samples,
-                uint8_t* out_status, std::vector<std::vector<uint32_t>>* positions) {
+                uint8_t* out_status, std::vector<std::vector<uint32_t>>* positions, PairPool* pairs) {
     if (positions) positions->assign(count, {});
+    if (pairs) {
+        pairs->off.assign(count, 0);
+        pairs->cnt.assign(count, 0);
+        pairs->host.clear();
+        pairs->host.resize(count);
+        pairs->n = pairs->cap = 0;
+    }
+    // the pool is filled in the caller's order: a proof's offset is fixed once every accepted proof before it has its count (the host
+    // route runs first, the kernel's proofs come in ascending order pass by pass)
+    uint32_t cursor = 0;
+    auto place_up_to = [&](uint32_t end) {
+        for (; cursor < end; cursor++) {
+            pairs->off[cursor] = pairs->n;
+            pairs->n += pairs->cnt[cursor];
+        }
+    };
     std::vector<uint32_t> dev;  // indices of the proofs the kernel takes
     std::vector<uint32_t> host;
     for (uint32_t i = 0; i < count; i++) {
@@ -138,32 +190,49 @@ int verify_many(Ctx* ctx, const ProofData* const* proofs, const uint64_t* seeds,
         host.insert(host.end(), dev.begin(), dev.end());
         dev.clear();
     }
-    for (uint32_t i : host) host_route(*proofs[i], seeds ? seeds + i : nullptr, samples, out_status[i], positions ? &(*positions)[i] : nullptr);
-    if (dev.empty()) return FRIEDA_OK;
+    for (uint32_t i : host) {
+        host_route(*proofs[i], seeds ? seeds + i : nullptr, samples, out_status[i], positions ? &(*positions)[i] : nullptr, pairs ? &pairs->host[i] : nullptr);
+        if (pairs) pairs->cnt[i] = (uint32_t)pairs->host[i].pos.size();
+    }
+    if (pairs) {
+        for (uint32_t i : host) pairs->cap += 2 * (size_t)proofs[i]->pcs_config.n_queries;
+        for (uint32_t i : dev) pairs->cap += 2 * (size_t)proofs[i]->pcs_config.n_queries;
+    }
+    if (dev.empty()) {
+        if (pairs) place_up_to(count);
+        return FRIEDA_OK;
+    }
 
     FR_HIP(ctx, hipSetDevice(ctx->device));
     int rc = init_device_tables(ctx);
     if (rc) return rc;
+    if (pairs) {
+        rc = pool_alloc(ctx, *pairs);
+        if (rc) return rc;
+    }
     hipStream_t s = ctx->stream;
-    const size_t hdr_words = sizeof(k::VerifyHeader) / 4;
+    const size_t hdr_words = sizeof(k::VerifyHeader) / 4, head = pairs ? 3 : 2;  // (head: words of an output row before the queries)
+    const size_t pass_bytes = ctx->tuning.test_verify_pass_bytes ? (size_t)ctx->tuning.test_verify_pass_bytes : PASS_BYTES;
     for (size_t first = 0; first < dev.size();) {
         // the proofs of this pass
         size_t end = first, words = 0;
         uint32_t q_cap = 64;
         while (end < dev.size()) {
             const size_t w = hdr_words + image_words(*proofs[dev[end]]);
-            if (end > first && 4 * (words + w) > PASS_BYTES) break;
+            if (end > first && 4 * (words + w) > pass_bytes) break;
             words += w;
             while (q_cap < proofs[dev[end]]->pcs_config.n_queries) q_cap <<= 1;
             end++;
         }
-        const size_t np = end - first, in_bytes = (4 * words + 255) & ~(size_t)255, out_bytes = 4 * np * (2 + (size_t)q_cap);
+        const size_t np = end - first, in_bytes = (4 * words + 255) & ~(size_t)255, out_bytes = 4 * np * (head + (size_t)q_cap);
+        const size_t tab_bytes = pairs ? 12 * np : 0, row = 2 * (size_t)q_cap;  // (row: entries of a proof in the pass's pair buffer)
         if (words >= ((size_t)1 << 32)) return ctx->fail(FRIEDA_ERR_ARG, "verify_many: one proof beyond 2^32 words");
         ArenaPlan ap;
         const size_t a_in = ap.take(in_bytes), a_out = ap.take(out_bytes);
+        const size_t a_pp = ap.take(pairs ? 4 * np * row : 0), a_pv = ap.take(pairs ? 16 * np * row : 0), a_tab = ap.take(tab_bytes);
         rc = ctx->ensure_arena(ap.off);
         if (rc) return rc;
-        rc = ensure_pinned(ctx, in_bytes + out_bytes);
+        rc = ensure_pinned(ctx, in_bytes + out_bytes + tab_bytes);
         if (rc) return rc;
         uint32_t* pin = static_cast<uint32_t*>(ctx->pinned);
         k::VerifyHeader* hdr = reinterpret_cast<k::VerifyHeader*>(pin);
@@ -178,22 +247,45 @@ int verify_many(Ctx* ctx, const ProofData* const* proofs, const uint64_t* seeds,
         va.img = reinterpret_cast<const uint32_t*>(ctx->arena + a_in);
         va.out = reinterpret_cast<uint32_t*>(ctx->arena + a_out);
         va.q_cap = q_cap;
+        if (pairs) {
+            va.pair_pos = reinterpret_cast<uint32_t*>(ctx->arena + a_pp);
+            va.pair_val = reinterpret_cast<uint32_t*>(ctx->arena + a_pv);
+        }
         k::verify_many(ctx->launch(), va, (uint32_t)np);
         FR_HIP(ctx, hipGetLastError());
         uint32_t* res = pin + in_bytes / 4;
         FR_HIP(ctx, hipMemcpyAsync(res, ctx->arena + a_out, out_bytes, hipMemcpyDeviceToHost, s));
         FR_HIP(ctx, hipStreamSynchronize(s));
+        uint32_t* tab = res + out_bytes / 4;
+        uint32_t n_rows = 0;
         for (size_t j = 0; j < np; j++) {
             const uint32_t i = dev[first + j];
-            const uint32_t* r = res + j * (2 + (size_t)q_cap);
+            const uint32_t* r = res + j * (head + (size_t)q_cap);
             uint8_t st = (uint8_t)r[0];
             if (r[0] > k::VERIFY_INVARIANT) return ctx->fail(FRIEDA_ERR_INVARIANT, "verify_many: the kernel left no status");
             if (st == k::VERIFY_ACCEPTED && samples && r[1] != proofs[i]->evaluations.size()) st = k::VERIFY_INVARIANT;
             out_status[i] = st;
-            if (positions && st == k::VERIFY_ACCEPTED) (*positions)[i].assign(r + 2, r + 2 + r[1]);
+            if (positions && st == k::VERIFY_ACCEPTED) (*positions)[i].assign(r + head, r + head + r[1]);
+            if (pairs && st == k::VERIFY_ACCEPTED) {
+                if (r[2] == 0 || r[2] > r[1] || r[1] > proofs[i]->pcs_config.n_queries) return ctx->fail(FRIEDA_ERR_INVARIANT, "verify_many: the kernel left no pair count");
+                pairs->cnt[i] = 2 * r[2];
+                place_up_to(i + 1);
+                if (pairs->off[i] + pairs->cnt[i] > pairs->cap || pairs->cap > 0xFFFFFFFFull) return ctx->fail(FRIEDA_ERR_INVARIANT, "verify_many: pair pool overrun");
+                tab[3 * n_rows] = (uint32_t)j, tab[3 * n_rows + 1] = pairs->cnt[i], tab[3 * n_rows + 2] = (uint32_t)pairs->off[i];
+                n_rows++;
+            }
+        }
+        if (n_rows) {
+            // (the table sits in the pinned block the next pass overwrites: wait for the copy)
+            FR_HIP(ctx, hipMemcpyAsync(ctx->arena + a_tab, tab, 12 * (size_t)n_rows, hipMemcpyHostToDevice, s));
+            k::verify_pairs_gather(ctx->launch(), reinterpret_cast<const uint32_t*>(ctx->arena + a_tab), n_rows, va.pair_pos, va.pair_val, q_cap,
+                                   pairs->d_pos(), pairs->d_val());
+            FR_HIP(ctx, hipGetLastError());
+            FR_HIP(ctx, hipStreamSynchronize(s));
         }
         first = end;
     }
+    if (pairs) place_up_to(count);
     return FRIEDA_OK;
 }
 
@@ -204,7 +296,8 @@ using namespace frieda;
 extern "C" {
 
 static int verify_many_common(frieda_ctx* ctx, const frieda_proof* const* proofs, const uint64_t* seeds, uint32_t count,
-                              const uint8_t* expected_commitment, bool samples, uint8_t* out_status, std::vector<std::vector<uint32_t>>* positions) {
+                              const uint8_t* expected_commitment, bool samples, uint8_t* out_status, std::vector<std::vector<uint32_t>>* positions,
+                              PairPool* pairs = nullptr) {
     if (!ctx) return FRIEDA_ERR_ARG;
     if (count == 0) return FRIEDA_OK;
     if (!proofs || !out_status) return FRIEDA_ERR_ARG;
@@ -214,7 +307,7 @@ static int verify_many_common(frieda_ctx* ctx, const frieda_proof* const* proofs
     FR_GUARD_BEGIN
     std::vector<const ProofData*> ps(count);
     for (uint32_t i = 0; i < count; i++) ps[i] = &proofs[i]->p;
-    return verify_many(&ctx->c, ps.data(), seeds, count, expected_commitment, samples, out_status, positions);
+    return verify_many(&ctx->c, ps.data(), seeds, count, expected_commitment, samples, out_status, positions, pairs);
     FR_GUARD_END(ctx)
 }
 
@@ -297,6 +390,100 @@ int frieda_reconstruct_from_proofs(frieda_ctx* ctx, const frieda_proof* const* p
     (void)hipStreamSynchronize(ctx->c.stream);
     (void)hipFree(d_cells);
     (void)hipFree(d_out);
+    if (rc != FRIEDA_OK) return rc;
+    uint8_t root[32];
+    rc = commit_host(&ctx->c, bytes.data(), len, B, root);
+    if (rc != FRIEDA_OK) return rc;
+    if (memcmp(root, expected_commitment, 32) != 0) return ctx->c.fail(FRIEDA_ERR_ARG, "the rebuilt blob does not commit to expected_commitment (wrong len?)");
+    if (len) memcpy(out_bytes, bytes.data(), len);
+    return FRIEDA_OK;
+    FR_GUARD_END(ctx)
+}
+
+int frieda_verify_pairs_many(frieda_ctx* ctx, const frieda_proof* const* proofs, const uint64_t* seeds, uint32_t count,
+                             const uint8_t* expected_commitment, uint8_t* out_status, uint32_t* out_positions, uint32_t* out_values, size_t pitch,
+                             uint32_t* out_n_points) {
+    if (!ctx) return FRIEDA_ERR_ARG;
+    if (count == 0) return FRIEDA_OK;
+    if (!proofs || !out_status || !out_positions || !out_values || !out_n_points) return FRIEDA_ERR_ARG;
+    for (uint32_t i = 0; i < count; i++) {
+        if (!proofs[i]) return ctx->c.fail(FRIEDA_ERR_ARG, "null proof " + std::to_string(i));
+        if (pitch < 2 * (size_t)proofs[i]->p.pcs_config.n_queries)
+            return ctx->c.fail(FRIEDA_ERR_ARG, "pitch smaller than 2 * n_queries of proof " + std::to_string(i));
+    }
+    FR_GUARD_BEGIN
+    PairPool pool;
+    const int rc = verify_many_common(ctx, proofs, seeds, count, expected_commitment, true, out_status, nullptr, &pool);
+    if (rc != FRIEDA_OK) return rc;
+    // the gathered rows of the kernel's proofs come back in one copy each (the entries between them, kept for host-route proofs, are not read)
+    std::vector<uint32_t> pos, val;
+    if (pool.d && pool.n) {
+        pos.resize(pool.n);
+        val.resize(4 * pool.n);
+        FR_HIP(&ctx->c, hipMemcpyAsync(pos.data(), pool.d_pos(), 4 * pool.n, hipMemcpyDeviceToHost, ctx->c.stream));
+        FR_HIP(&ctx->c, hipMemcpyAsync(val.data(), pool.d_val(), 16 * pool.n, hipMemcpyDeviceToHost, ctx->c.stream));
+        FR_HIP(&ctx->c, hipStreamSynchronize(ctx->c.stream));
+    }
+    for (uint32_t i = 0; i < count; i++) {
+        const size_t n = pool.cnt[i];
+        out_n_points[i] = (uint32_t)n;
+        if (!n) continue;
+        const PairPoints& h = pool.host[i];
+        memcpy(out_positions + (size_t)i * pitch, h.pos.empty() ? pos.data() + pool.off[i] : h.pos.data(), 4 * n);
+        memcpy(out_values + 4 * (size_t)i * pitch, h.pos.empty() ? val.data() + 4 * pool.off[i] : reinterpret_cast<const uint32_t*>(h.val.data()), 16 * n);
+    }
+    return FRIEDA_OK;
+    FR_GUARD_END(ctx)
+}
+
+int frieda_reconstruct_from_proof_pairs(frieda_ctx* ctx, const frieda_proof* const* proofs, const uint64_t* seeds, uint32_t count,
+                                        const uint8_t expected_commitment[32], size_t len, uint8_t* out_bytes, uint8_t* out_status, size_t* n_points) {
+    if (!ctx || !proofs || !expected_commitment || !out_status || !n_points || count == 0 || (len && !out_bytes)) return FRIEDA_ERR_ARG;
+    *n_points = 0;
+    FR_GUARD_BEGIN
+    PairPool pool;
+    int rc = verify_many_common(ctx, proofs, seeds, count, expected_commitment, true, out_status, nullptr, &pool);
+    if (rc != FRIEDA_OK) return rc;
+    rc = pool.upload_host_rows(&ctx->c);
+    if (rc != FRIEDA_OK) return rc;
+    bool have_shape = false;
+    uint32_t L = 0, B = 0, nd = 0;
+    for (uint32_t i = 0; i < count; i++) {
+        if (out_status[i] != k::VERIFY_ACCEPTED) continue;
+        const ProofData& p = proofs[i]->p;
+        if (!have_shape) {
+            L = p.log_size_bound, B = p.pcs_config.log_blowup_factor;
+            have_shape = true;
+        } else if (p.log_size_bound != L || p.pcs_config.log_blowup_factor != B) {
+            // the points pooled before the proof that disagrees: a prefix of the pool, which is in the caller's order
+            rc = count_distinct_points(ctx, pool.d_pos(), (uint32_t)pool.off[i], L + B, &nd);
+            if (rc != FRIEDA_OK) return rc;
+            *n_points = nd;
+            return ctx->c.fail(FRIEDA_ERR_ARG, "accepted proofs disagree on the shape of the codeword");
+        }
+    }
+    if (!have_shape) return ctx->c.fail(FRIEDA_ERR_ARG, "no proof was accepted");
+    const size_t need = ((size_t)1 << L) + 2;
+    auto too_few = [&]() { return ctx->c.fail(FRIEDA_ERR_ARG, std::to_string(nd) + " distinct verified points, " + std::to_string(need) + " needed"); };
+    if ((8 * len + 29) / 30 > ((size_t)4 << L) || pool.n == 0) {
+        rc = count_distinct_points(ctx, pool.d_pos(), (uint32_t)pool.n, L + B, &nd);
+        if (rc != FRIEDA_OK) return rc;
+        *n_points = nd;
+        return nd < need ? too_few() : ctx->c.fail(FRIEDA_ERR_ARG, "len does not fit the polynomial");
+    }
+    void* d_out = nullptr;
+    const hipError_t e = hipMalloc(&d_out, len ? len : 1);
+    if (e != hipSuccess) {
+        ctx->c.err = std::string("hipMalloc: ") + hipGetErrorString(e);
+        return FRIEDA_ERR_NOMEM;
+    }
+    std::vector<uint8_t> bytes(len);
+    rc = reconstruct_points_pooled(ctx, pool.d_val(), pool.d_pos(), (uint32_t)pool.n, L, L + B, len, d_out, &nd);
+    *n_points = nd;
+    if (rc == FRIEDA_OK) rc = frieda_dev_download(ctx, bytes.data(), d_out, len);
+    (void)hipStreamSynchronize(ctx->c.stream);
+    (void)hipFree(d_out);
+    if (rc == FRIEDA_ERR_ARG && nd < need) return too_few();
     if (rc != FRIEDA_OK) return rc;
     uint8_t root[32];
     rc = commit_host(&ctx->c, bytes.data(), len, B, root);

@@ -274,6 +274,53 @@ class Context {
         out.resize(len);
         return out;
     }
+    // every point the accepted proofs authenticate (frieda_verify_pairs_many): per proof the ascending positions of both members of every
+    // opened first-layer pair and their values; empty for a proof that is not accepted
+    struct PairRows {
+        std::vector<uint8_t> status;
+        std::vector<std::vector<uint32_t>> positions;
+        std::vector<std::vector<QM31>> values;
+    };
+    PairRows verify_pairs_many(const std::vector<const Proof*>& proofs, const std::vector<uint64_t>& seeds = {}, const Commitment* expected_commitment = nullptr) {
+        PairRows out{std::vector<uint8_t>(proofs.size()), std::vector<std::vector<uint32_t>>(proofs.size()), std::vector<std::vector<QM31>>(proofs.size())};
+        if (proofs.empty()) return out;
+        if (!seeds.empty() && seeds.size() != proofs.size()) throw Error(FRIEDA_ERR_ARG, "verify_pairs_many: one seed per proof");
+        std::vector<const frieda_proof*> hs;
+        size_t pitch = 1;
+        for (const Proof* p : proofs) {
+            hs.push_back(p->handle());
+            pitch = std::max<size_t>(pitch, 2 * (size_t)frieda_proof_pcs_config(p->handle()).n_queries);
+        }
+        std::vector<uint32_t> pos(pitch * hs.size()), val(4 * pitch * hs.size()), n(hs.size());
+        check(frieda_verify_pairs_many(h_, hs.data(), seeds.empty() ? nullptr : seeds.data(), (uint32_t)hs.size(),
+                                       expected_commitment ? expected_commitment->data() : nullptr, out.status.data(), pos.data(), val.data(), pitch, n.data()),
+              h_);
+        for (size_t i = 0; i < hs.size(); i++) {
+            out.positions[i].assign(pos.begin() + i * pitch, pos.begin() + i * pitch + n[i]);
+            out.values[i].resize(n[i]);
+            for (size_t j = 0; j < n[i]; j++)
+                for (int c = 0; c < 4; c++) out.values[i][j].v[c] = val[4 * (i * pitch + j) + c];
+        }
+        return out;
+    }
+    // frieda_reconstruct_from_proof_pairs: reconstruct_from_proofs with the pair points as the pool (about half as many proofs needed)
+    std::vector<uint8_t> reconstruct_from_proof_pairs(const std::vector<const Proof*>& proofs, const std::vector<uint64_t>& seeds,
+                                                      const Commitment& expected_commitment, size_t len, std::vector<uint8_t>* out_status = nullptr,
+                                                      size_t* n_points = nullptr) {
+        if (!seeds.empty() && seeds.size() != proofs.size()) throw Error(FRIEDA_ERR_ARG, "reconstruct_from_proof_pairs: one seed per proof");
+        std::vector<const frieda_proof*> hs;
+        for (const Proof* p : proofs) hs.push_back(p->handle());
+        std::vector<uint8_t> status(hs.size() + 1), out(len + 1);
+        size_t np = 0;
+        const int rc = frieda_reconstruct_from_proof_pairs(h_, hs.data(), seeds.empty() ? nullptr : seeds.data(), (uint32_t)hs.size(),
+                                                           expected_commitment.data(), len, out.data(), status.data(), &np);
+        status.resize(hs.size());
+        if (out_status) *out_status = status;
+        if (n_points) *n_points = np;
+        check(rc, h_);
+        out.resize(len);
+        return out;
+    }
     // Level B openings over caller device buffers (frieda_dev_gather, frieda_dev_gather_hashes, frieda_merkle_decommit)
     // rows[i * ncols + c] = column c at idx[i]
     std::vector<uint32_t> dev_gather(const uint32_t* d_cols, size_t stride, uint32_t ncols, const std::vector<uint64_t>& idx) {
@@ -408,6 +455,22 @@ inline std::optional<std::vector<uint32_t>> verify_samples(const Proof& proof, s
     if (!ok) return std::nullopt;
     pos.resize(n);
     return pos;
+}
+// verify + every point the accepted proof authenticates (frieda_verify_pairs): the ascending positions of both members of every opened
+// first-layer pair and their values; nullopt when the proof is rejected
+inline std::optional<std::pair<std::vector<uint32_t>, std::vector<QM31>>> verify_pairs(const Proof& proof, std::optional<uint64_t> seed) {
+    int ok = 0;
+    uint64_t s = seed.value_or(0);
+    const size_t cap = 2 * (size_t)frieda_proof_pcs_config(proof.handle()).n_queries + 1;
+    std::vector<uint32_t> pos(cap), val(4 * cap);
+    size_t n = 0;
+    check(frieda_verify_pairs(proof.handle(), seed ? &s : nullptr, &ok, pos.data(), val.data(), cap, &n));
+    if (!ok) return std::nullopt;
+    pos.resize(n);
+    std::vector<QM31> values(n);
+    for (size_t i = 0; i < n; i++)
+        for (int c = 0; c < 4; c++) values[i].v[c] = val[4 * i + c];
+    return std::make_pair(pos, values);
 }
 }  // namespace api
 

@@ -138,7 +138,8 @@ int frieda_commit_and_generate_proof_device(frieda_ctx* ctx, const void* d_data,
  * context") and leaves the proof untouched: frieda_commit*, frieda_commit_batch*, a second _begin, frieda_merkle_root,
  * frieda_merkle_commit_layer, frieda_grind, frieda_reconstruct*_device, frieda_circle_interpolate_cells,
  * frieda_ctx_release_workspace, frieda_dev_gather, frieda_dev_gather_hashes, frieda_merkle_decommit (and
- * frieda_merkle_decommit_device beyond 512 positions), frieda_verify_many, frieda_verify_samples_many, frieda_reconstruct_from_proofs.  Level B calls that only read the twiddle cache and caller buffers stay available.
+ * frieda_merkle_decommit_device beyond 512 positions), frieda_verify_many, frieda_verify_samples_many, frieda_reconstruct_from_proofs,
+ * frieda_verify_pairs_many, frieda_reconstruct_from_proof_pairs (frieda_verify_pairs is host-only and takes no context).  Level B calls that only read the twiddle cache and caller buffers stay available.
  * A blob passed to _begin_device must stay valid until _finish returns. */
 int frieda_prove_begin(frieda_ctx* ctx, const uint8_t* data, size_t len, const uint64_t* seed, frieda_pcs_config cfg);
 int frieda_prove_begin_device(frieda_ctx* ctx, const void* d_data, size_t len, const uint64_t* seed, frieda_pcs_config cfg);
@@ -253,6 +254,35 @@ int frieda_verify_samples_many(frieda_ctx* ctx, const frieda_proof* const* proof
 int frieda_reconstruct_from_proofs(frieda_ctx* ctx, const frieda_proof* const* proofs, const uint64_t* seeds, uint32_t count,
                                    const uint8_t expected_commitment[32], size_t len, uint8_t* out_bytes, uint8_t* out_status,
                                    size_t* n_points);
+/* Every point an accepted proof authenticates.  A proof opens the first FRI layer in pairs {2v, 2v + 1} of the bit-reversed codeword;
+ * where only one member of a pair was queried, the other's four column values travel in the first layer's fri_witness, and the verifier
+ * hashes that leaf into the Merkle path it checks against the commitment.  In an accepted proof the sibling is therefore exactly as
+ * verified as an evaluation, and a client that pools both needs about half as many proofs for the same number of distinct points.
+ * frieda_verify_pairs (host, one proof; the counterpart of frieda_verify_samples): on acceptance out_positions receives the ascending,
+ * distinct positions of both members of every opened pair and out_values[4 i .. 4 i + 3] the column words at out_positions[i] — from
+ * the proof's evaluations where the position was queried, from the first layer's fri_witness otherwise.  *n_points receives the count
+ * (at most 2 * n_queries; 0 when the proof is rejected); FRIEDA_ERR_ARG when cap (in points) is smaller than that;
+ * FRIEDA_ERR_INVARIANT as frieda_verify_samples: accepted, but not one evaluation per distinct query. */
+int frieda_verify_pairs(const frieda_proof* proof, const uint64_t* seed, int* ok, uint32_t* out_positions, uint32_t* out_values, size_t cap,
+                        size_t* n_points);
+/* The same for many proofs in one call, with the status bytes of frieda_verify_samples_many: row i holds out_n_points[i] points, its
+ * positions at out_positions + i * pitch and its values at out_values + 4 * i * pitch (pitch in points).  Rows of proofs that are
+ * not accepted are not written (their count is 0), and neither is the part of a row beyond out_n_points[i].  pitch < 2 * n_queries
+ * of any proof: FRIEDA_ERR_ARG before anything runs.  Status and points are the same whichever route a proof takes
+ * (FRIEDA_VERIFY_DEVICE_MIN and the shapes the kernel refuses, as above). */
+int frieda_verify_pairs_many(frieda_ctx* ctx, const frieda_proof* const* proofs, const uint64_t* seeds, uint32_t count,
+                             const uint8_t* expected_commitment, uint8_t* out_status, uint32_t* out_positions, uint32_t* out_values,
+                             size_t pitch, uint32_t* out_n_points);
+/* frieda_reconstruct_from_proofs with the pair points as the pool: same contract, same error cases (the shape rule, the len check, the
+ * commitment check, out_bytes untouched on error), about half as many proofs needed.  *n_points receives the number of distinct
+ * verified points pooled.  The points of the proofs the kernel verified are pooled and de-duplicated inside the library's own
+ * workspace and go straight into the reconstruction; proofs that took the host verifier add theirs to the same pool.  WHICH
+ * occurrence of a position that several proofs opened is kept is unspecified — it cannot matter: two accepted proofs under one
+ * commitment cannot hold different values for a position without a Blake2s collision, and the reconstruction compares every distinct
+ * sample it keeps with the re-encoded result.  *n_points and the bytes are deterministic. */
+int frieda_reconstruct_from_proof_pairs(frieda_ctx* ctx, const frieda_proof* const* proofs, const uint64_t* seeds, uint32_t count,
+                                        const uint8_t expected_commitment[32], size_t len, uint8_t* out_bytes, uint8_t* out_status,
+                                        size_t* n_points);
 
 /* ---- batch policy: how a stream of equal-length blobs is cut into batched calls ("bytes in flight") -------------------------
  * Every kernel of a batched call covers all its blobs, so the launch / Fiat-Shamir latency chain is paid once per call: small

@@ -23,6 +23,11 @@ int frieda_ctx_test_set_grind_first_log(frieda_ctx* ctx, uint32_t log_first);
  * tests of frieda_prove_many / frieda_commit_many's retry with smaller calls. */
 int frieda_ctx_test_set_arena_limit(frieda_ctx* ctx, uint64_t bytes);
 
+/* The staging budget of one pass of frieda_verify_many and its kin (default 32 MB; a lone larger proof is a pass of its own).  A small
+ * value makes a handful of small proofs take several passes, so that a test reaches the pass loop and the pool offsets that continue
+ * across passes.  0 restores the default. */
+int frieda_ctx_test_set_verify_pass_bytes(frieda_ctx* ctx, uint64_t bytes);
+
 /* The parser of sysfs CPU lists ("0-3,8,10-11\n") behind frieda_multi's NUMA placement, for the CPU tests: *n receives the count,
  * out_cpus (cap entries) the CPUs in order.  FRIEDA_ERR_FORMAT for malformed text, FRIEDA_ERR_ARG when cap is too small. */
 int frieda_test_parse_cpulist(const char* text, int* out_cpus, size_t cap, size_t* n);
