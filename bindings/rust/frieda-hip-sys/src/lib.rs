@@ -96,6 +96,7 @@ extern "C" {
     pub fn frieda_encode_device(ctx: *mut frieda_ctx, d_data: *const c_void, len: usize, log_blowup_factor: u32, out: *mut *mut frieda_encoded) -> c_int;
     pub fn frieda_encoded_commitment(enc: *const frieda_encoded, out_root: *mut u8) -> c_int;
     pub fn frieda_encoded_bytes(enc: *const frieda_encoded) -> usize;
+    pub fn frieda_encoded_shape(enc: *const frieda_encoded, log_size_bound: *mut u32, log_domain: *mut u32) -> c_int;
     pub fn frieda_encoded_free(enc: *mut frieda_encoded);
     pub fn frieda_prove_seeds_begin(ctx: *mut frieda_ctx, enc: *const frieda_encoded, seeds: *const u64, n_seeds: u32, cfg: frieda_pcs_config) -> c_int;
     pub fn frieda_prove_seeds_finish(ctx: *mut frieda_ctx, out_proofs: *mut *mut frieda_proof) -> c_int;
@@ -132,6 +133,12 @@ extern "C" {
     pub fn frieda_verify_pairs_many(ctx: *mut frieda_ctx, proofs: *const *const frieda_proof, seeds: *const u64, count: u32, expected_commitment: *const u8, out_status: *mut u8, out_positions: *mut u32, out_values: *mut u32, pitch: usize, out_n_points: *mut u32) -> c_int;
     /// frieda_reconstruct_from_proofs with the pair points as the pool: about half as many proofs needed
     pub fn frieda_reconstruct_from_proof_pairs(ctx: *mut frieda_ctx, proofs: *const *const frieda_proof, seeds: *const u64, count: u32, expected_commitment: *const u8, len: usize, out_bytes: *mut u8, out_status: *mut u8, n_points: *mut usize) -> c_int;
+    /// authenticated cells: values[n_cells][4][2^log_cell] cell-major, paths[n_cells][log_domain - log_cell][32] bottom-up, one status byte per cell
+    pub fn frieda_open_cells(ctx: *mut frieda_ctx, enc: *const frieda_encoded, log_cell: u32, cell_index: *const u32, n_cells: u32, out_values: *mut u32, out_paths: *mut u8) -> c_int;
+    pub fn frieda_verify_cells(commitment: *const u8, log_domain: u32, log_cell: u32, cell_index: *const u32, n_cells: u32, values: *const u32, paths: *const u8, out_status: *mut u8) -> c_int;
+    pub fn frieda_verify_cells_many(ctx: *mut frieda_ctx, commitment: *const u8, log_domain: u32, log_cell: u32, cell_index: *const u32, n_cells: u32, values: *const u32, paths: *const u8, out_status: *mut u8) -> c_int;
+    /// verify the cells, drop the rejected ones, rebuild the blob and check it against the commitment
+    pub fn frieda_reconstruct_from_opened_cells(ctx: *mut frieda_ctx, commitment: *const u8, log_blowup_factor: u32, len: usize, log_cell: u32, cell_index: *const u32, n_cells: u32, values: *const u32, paths: *const u8, out_bytes: *mut u8, out_status: *mut u8, n_cells_used: *mut usize) -> c_int;
 
     // struct Proof
     pub fn frieda_proof_free(p: *mut frieda_proof);

@@ -16,6 +16,8 @@ TESTING_HEADER_PATH = os.path.join(_ROOT, "include", "frieda_hip_testing.h")  # 
 
 OK, ERR_ARG, ERR_HIP, ERR_INVARIANT, ERR_NOMEM, ERR_FORMAT = 0, 1, 2, 3, 4, 5
 VERIFY_REJECTED, VERIFY_ACCEPTED, VERIFY_INVARIANT, VERIFY_WRONG_COMMITMENT = 0, 1, 2, 3  # status bytes of frieda_verify_many
+CELL_REJECTED, CELL_ACCEPTED = 0, 1  # status bytes of frieda_verify_cells*
+MAX_LOG_OPEN_CELL = 10
 
 
 class PcsConfigC(C.Structure):
@@ -112,6 +114,7 @@ def lib():
         "frieda_encoded_commitment": (C.c_int, [vp, vp]),
         "frieda_encoded_bytes": (sz, [vp]),
         "frieda_encoded_free": (None, [vp]),
+        "frieda_encoded_shape": (C.c_int, [vp, C.POINTER(u32), C.POINTER(u32)]),
         "frieda_prove_seeds_begin": (C.c_int, [vp, vp, u64p, u32, PcsConfigC]),
         "frieda_prove_seeds_finish": (C.c_int, [vp, pp]),
         "frieda_prove_seeds": (C.c_int, [vp, vp, u64p, u32, PcsConfigC, pp]),
@@ -140,6 +143,10 @@ def lib():
         "frieda_verify_pairs": (C.c_int, [vp, u64p, C.POINTER(C.c_int), vp, vp, sz, C.POINTER(sz)]),
         "frieda_verify_pairs_many": (C.c_int, [vp, pp, u64p, u32, vp, vp, vp, vp, sz, vp]),
         "frieda_reconstruct_from_proof_pairs": (C.c_int, [vp, pp, u64p, u32, vp, sz, vp, vp, C.POINTER(sz)]),
+        "frieda_open_cells": (C.c_int, [vp, vp, u32, vp, u32, vp, vp]),
+        "frieda_verify_cells": (C.c_int, [vp, u32, u32, vp, u32, vp, vp, vp]),
+        "frieda_verify_cells_many": (C.c_int, [vp, vp, u32, u32, vp, u32, vp, vp, vp]),
+        "frieda_reconstruct_from_opened_cells": (C.c_int, [vp, vp, u32, sz, u32, vp, u32, vp, vp, vp, vp, C.POINTER(sz)]),
         "frieda_proof_free": (None, [vp]),
         "frieda_proof_clone": (C.c_int, [vp, pp]),
         "frieda_proof_proof_of_work": (u64, [vp]),

@@ -527,6 +527,69 @@ class Context:
         return out[:n_bytes].tobytes(), status[:count], n.value
 
 
+    # ---- authenticated cells (frieda_verify_cells_many, frieda_reconstruct_from_opened_cells; Encoded.open_cells is the provider's half) ----
+    def verify_cells_many(self, commitment, log_domain, log_cell, cell_index, values, paths):
+        """One status byte per cell (numpy uint8: CELL_ACCEPTED / CELL_REJECTED), verified on the device; the bytes verify_cells() gives."""
+        idx, val, pth = _cell_arrays(log_domain, log_cell, cell_index, values, paths)
+        status = np.zeros(len(idx), dtype=np.uint8)
+        com = (C.c_uint8 * 32)(*commitment)
+        _check(
+            self._L.frieda_verify_cells_many(self._h, com, log_domain, log_cell, idx.ctypes.data, len(idx), val.ctypes.data, pth.ctypes.data, status.ctypes.data),
+            self._h,
+        )
+        return status
+
+    def reconstruct_from_opened_cells(self, commitment, log_blowup_factor, n_bytes, log_cell, cell_index, values, paths):
+        """Verify the cells against the commitment, drop the rejected ones and rebuild the blob from the rest: (bytes, status,
+        n_cells_used).  Raises FriedaError (with .n_cells_used and .cell_status set) when the accepted cells do not suffice or the result
+        does not commit to `commitment`."""
+        log_domain = codec_log_size(n_bytes) + log_blowup_factor
+        idx, val, pth = _cell_arrays(log_domain, log_cell, cell_index, values, paths)
+        count = len(idx)
+        status = np.zeros(max(count, 1), dtype=np.uint8)
+        out = np.zeros(max(n_bytes, 1), dtype=np.uint8)
+        n = C.c_size_t(0)
+        com = (C.c_uint8 * 32)(*commitment)
+        try:
+            _check(
+                self._L.frieda_reconstruct_from_opened_cells(
+                    self._h, com, log_blowup_factor, n_bytes, log_cell, idx.ctypes.data, count, val.ctypes.data, pth.ctypes.data, out.ctypes.data,
+                    status.ctypes.data, C.byref(n)
+                ),
+                self._h,
+            )
+        except FriedaError as e:
+            e.n_cells_used = n.value
+            e.cell_status = status[:count]
+            raise
+        return out[:n_bytes].tobytes(), status[:count], n.value
+
+
+def codec_log_size(n_bytes):
+    """log2 of the coefficients per column of a blob of n_bytes (frieda_codec_shape)."""
+    a, b, lg = C.c_size_t(0), C.c_size_t(0), C.c_uint32(0)
+    _check(_lib.lib().frieda_codec_shape(n_bytes, C.byref(a), C.byref(b), C.byref(lg)))
+    return int(lg.value)
+
+
+def _cell_arrays(log_domain, log_cell, cell_index, values, paths):
+    """the three host arrays of a cells call, contiguous and of the shapes the C ABI reads: a short array must not reach the library"""
+    if not 0 <= log_cell <= log_domain:
+        raise FriedaError(_lib.ERR_ARG, "log_cell out of range")
+    idx = np.ascontiguousarray(cell_index, dtype=np.uint32).reshape(-1)
+    val = np.ascontiguousarray(values, dtype=np.uint32).reshape(-1)
+    pth = np.ascontiguousarray(paths, dtype=np.uint8).reshape(-1)
+    if val.size != (len(idx) * 4) << log_cell or pth.size != len(idx) * 32 * (log_domain - log_cell):
+        raise FriedaError(_lib.ERR_ARG, "values / paths do not have the shape of the cell list")
+    if pth.size == 0:
+        pth = np.zeros(1, dtype=np.uint8)
+    if val.size == 0:
+        val = np.zeros(1, dtype=np.uint32)
+    if idx.size == 0:
+        idx = np.zeros(0, dtype=np.uint32)
+    return idx, val, pth
+
+
 class Encoded:
     """An encoded blob on the device (frieda_encoded): evaluations + first-layer tree + root, in an allocation of its own that outlives
     the context's workspace.  Only read by proving: several contexts of its device may prove from it at once.  close() frees it."""
@@ -550,6 +613,29 @@ class Encoded:
     @property
     def nbytes(self):
         return int(_lib.lib().frieda_encoded_bytes(self._handle()))
+
+    @property
+    def shape(self):
+        """(log_size_bound, log_domain) of the encoded codeword (frieda_encoded_shape)"""
+        a, b = C.c_uint32(0), C.c_uint32(0)
+        _check(_lib.lib().frieda_encoded_shape(self._handle(), C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
+
+    def open_cells(self, ctx, log_cell, cell_index):
+        """Cells of the codeword with their Merkle paths to `commitment` (frieda_open_cells, on `ctx`, which must be on the blob's
+        device): (values uint32 [n, 4, 2^log_cell], paths uint8 [n, log_domain - log_cell, 32])."""
+        log_domain = self.shape[1]
+        if not 0 <= log_cell <= log_domain:
+            raise FriedaError(_lib.ERR_ARG, "log_cell out of range")
+        idx = np.ascontiguousarray(cell_index, dtype=np.uint32).reshape(-1)
+        values = np.zeros((len(idx), 4, 1 << log_cell), dtype=np.uint32)
+        paths = np.zeros((len(idx), log_domain - log_cell, 32), dtype=np.uint8)
+        _check(
+            _lib.lib().frieda_open_cells(ctx._h, self._handle(), log_cell, idx.ctypes.data, len(idx), values.ctypes.data if values.size else None,
+                                         paths.ctypes.data if paths.size else None),
+            ctx._h,
+        )
+        return values, paths
 
     def close(self):
         if self._h:
@@ -965,3 +1051,28 @@ def verify_samples_many(proofs, seeds=None, expected_commitment=None):
 def reconstruct_from_proofs(proofs, seeds, expected_commitment, n_bytes):
     """frieda_reconstruct_from_proofs on the default context: (bytes, status, n_points)."""
     return default_context().reconstruct_from_proofs(proofs, seeds, expected_commitment, n_bytes)
+
+
+def open_cells(encoded, log_cell, cell_index):
+    """Encoded.open_cells on the default context: (values, paths)."""
+    return encoded.open_cells(default_context(), log_cell, cell_index)
+
+
+def verify_cells(commitment, log_domain, log_cell, cell_index, values, paths):
+    """The host verifier of opened cells (frieda_verify_cells: no context, one core): one status byte per cell (numpy uint8), CELL_ACCEPTED
+    when every word is a canonical M31 and the cell's subtree root, carried up its path, equals the commitment."""
+    idx, val, pth = _cell_arrays(log_domain, log_cell, cell_index, values, paths)
+    status = np.zeros(len(idx), dtype=np.uint8)
+    com = (C.c_uint8 * 32)(*commitment)
+    _check(_lib.lib().frieda_verify_cells(com, log_domain, log_cell, idx.ctypes.data, len(idx), val.ctypes.data, pth.ctypes.data, status.ctypes.data))
+    return status
+
+
+def verify_cells_many(commitment, log_domain, log_cell, cell_index, values, paths):
+    """frieda_verify_cells_many on the default context: one status byte per cell, verified on the device."""
+    return default_context().verify_cells_many(commitment, log_domain, log_cell, cell_index, values, paths)
+
+
+def reconstruct_from_opened_cells(commitment, log_blowup_factor, n_bytes, log_cell, cell_index, values, paths):
+    """frieda_reconstruct_from_opened_cells on the default context: (bytes, status, n_cells_used)."""
+    return default_context().reconstruct_from_opened_cells(commitment, log_blowup_factor, n_bytes, log_cell, cell_index, values, paths)

@@ -471,6 +471,96 @@ void frieda_encoded_free(frieda_encoded* enc) {
     delete enc;
 }
 
+int frieda_encoded_shape(const frieda_encoded* enc, uint32_t* log_size_bound, uint32_t* log_domain) {
+    if (!enc || !log_size_bound || !log_domain) return FRIEDA_ERR_ARG;
+    *log_size_bound = enc->e.L;
+    *log_domain = enc->e.n;
+    return FRIEDA_OK;
+}
+
+// ---- authenticated cells (cells_host.cpp) ----
+int frieda_open_cells(frieda_ctx* ctx, const frieda_encoded* enc, uint32_t log_cell, const uint32_t* cell_index, uint32_t n_cells,
+                      uint32_t* out_values, uint8_t* out_paths) {
+    if (!ctx || !enc) return FRIEDA_ERR_ARG;
+    if (n_cells == 0) return FRIEDA_OK;
+    if (!cell_index || !out_values || (!out_paths && log_cell != enc->e.n)) return FRIEDA_ERR_ARG;
+    if (const char* bad = cells_args_error(enc->e.n, log_cell, cell_index, n_cells)) return ctx->c.fail(FRIEDA_ERR_ARG, std::string("open_cells: ") + bad);
+    FR_GUARD_BEGIN
+    return open_cells(&ctx->c, enc->e, log_cell, cell_index, n_cells, out_values, out_paths);
+    FR_GUARD_END(ctx)
+}
+
+int frieda_verify_cells(const uint8_t commitment[32], uint32_t log_domain, uint32_t log_cell, const uint32_t* cell_index, uint32_t n_cells,
+                        const uint32_t* values, const uint8_t* paths, uint8_t* out_status) {
+    if (n_cells == 0) return FRIEDA_OK;
+    if (!commitment || !cell_index || !values || !out_status) return FRIEDA_ERR_ARG;
+    if (cells_args_error(log_domain, log_cell, cell_index, n_cells) || (!paths && log_cell != log_domain)) return FRIEDA_ERR_ARG;
+    try {
+        verify_cells_host(commitment, log_domain, log_cell, cell_index, n_cells, values, paths, out_status);
+    } catch (const std::bad_alloc&) {
+        return FRIEDA_ERR_NOMEM;
+    }
+    return FRIEDA_OK;
+}
+
+int frieda_verify_cells_many(frieda_ctx* ctx, const uint8_t commitment[32], uint32_t log_domain, uint32_t log_cell, const uint32_t* cell_index,
+                             uint32_t n_cells, const uint32_t* values, const uint8_t* paths, uint8_t* out_status) {
+    if (!ctx) return FRIEDA_ERR_ARG;
+    if (n_cells == 0) return FRIEDA_OK;
+    if (!commitment || !cell_index || !values || !out_status || (!paths && log_cell != log_domain)) return FRIEDA_ERR_ARG;
+    if (const char* bad = cells_args_error(log_domain, log_cell, cell_index, n_cells)) return ctx->c.fail(FRIEDA_ERR_ARG, std::string("verify_cells_many: ") + bad);
+    FR_NO_JOB(&ctx->c);
+    FR_GUARD_BEGIN
+    return verify_cells_device(&ctx->c, commitment, log_domain, log_cell, cell_index, n_cells, values, paths, out_status, nullptr);
+    FR_GUARD_END(ctx)
+}
+
+int frieda_reconstruct_from_opened_cells(frieda_ctx* ctx, const uint8_t commitment[32], uint32_t log_blowup_factor, size_t len, uint32_t log_cell,
+                                         const uint32_t* cell_index, uint32_t n_cells, const uint32_t* values, const uint8_t* paths,
+                                         uint8_t* out_bytes, uint8_t* out_status, size_t* n_cells_used) {
+    if (!ctx || !commitment || !n_cells_used || (len && !out_bytes) || (n_cells && (!cell_index || !values || !out_status))) return FRIEDA_ERR_ARG;
+    *n_cells_used = 0;
+    if (log_blowup_factor > FRIEDA_MAX_LOG_DOMAIN || len > ((size_t)1 << 40)) return ctx->c.fail(FRIEDA_ERR_ARG, "reconstruct_from_opened_cells: shape out of range");
+    const uint32_t L = codec_shape(len).log_size, n = L + log_blowup_factor;
+    if (L < 1 || n < 2 || n + 1 > FRIEDA_MAX_LOG_DOMAIN) return ctx->c.fail(FRIEDA_ERR_ARG, "reconstruct_from_opened_cells: shape out of range");
+    if (const char* bad = cells_args_error(n, log_cell, cell_index, n_cells)) return ctx->c.fail(FRIEDA_ERR_ARG, std::string("reconstruct_from_opened_cells: ") + bad);
+    if (n_cells && !paths && log_cell != n) return FRIEDA_ERR_ARG;
+    FR_NO_JOB(&ctx->c);
+    FR_GUARD_BEGIN
+    const size_t need = log_cell ? (((size_t)1 << L) >> log_cell) + 1 : ((size_t)1 << L) + 2;
+    uint32_t nd = 0;
+    auto too_few = [&]() {
+        return ctx->c.fail(FRIEDA_ERR_ARG, std::to_string(nd) + " distinct accepted cells, " + std::to_string(need) + " needed");
+    };
+    if (n_cells == 0) return too_few();
+    CellPool pool;
+    int rc = verify_cells_device(&ctx->c, commitment, n, log_cell, cell_index, n_cells, values, paths, out_status, &pool);
+    if (rc != FRIEDA_OK) return rc;
+    if (pool.n == 0) return too_few();
+    void* d_out = nullptr;
+    const hipError_t e = hipMalloc(&d_out, len ? len : 1);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        ctx->c.err = std::string("hipMalloc: ") + hipGetErrorString(e);
+        return FRIEDA_ERR_NOMEM;
+    }
+    std::vector<uint8_t> bytes(len);
+    rc = reconstruct_cells_pooled(ctx, pool.d_val(), pool.d_idx(), (uint32_t)pool.n, log_cell, L, n, len, d_out, &nd);
+    *n_cells_used = nd;
+    if (rc == FRIEDA_OK) rc = frieda_dev_download(ctx, bytes.data(), d_out, len);
+    (void)hipStreamSynchronize(ctx->c.stream);
+    (void)hipFree(d_out);
+    if (rc == FRIEDA_ERR_ARG && nd < need) return too_few();
+    if (rc != FRIEDA_OK) return rc;
+    uint8_t root[32];
+    rc = commit_host(&ctx->c, bytes.data(), len, log_blowup_factor, root);
+    if (rc != FRIEDA_OK) return rc;
+    if (memcmp(root, commitment, 32) != 0) return ctx->c.fail(FRIEDA_ERR_ARG, "the rebuilt blob does not commit to the commitment (wrong len?)");
+    if (len) memcpy(out_bytes, bytes.data(), len);
+    return FRIEDA_OK;
+    FR_GUARD_END(ctx)
+}
+
 int frieda_prove_seeds_begin(frieda_ctx* ctx, const frieda_encoded* enc, const uint64_t* seeds, uint32_t n_seeds, frieda_pcs_config cfg) {
     if (!ctx) return FRIEDA_ERR_ARG;
     FR_GUARD_BEGIN

@@ -259,6 +259,40 @@ int reconstruct_points_pooled(frieda_ctx* ctx, const uint32_t* d_cells, const ui
                               size_t len, void* d_out_bytes, uint32_t* n_distinct);
 int count_distinct_points(frieda_ctx* ctx, const uint32_t* d_index, uint32_t n_points, uint32_t log_domain, uint32_t* n_distinct);
 
+// The same with whole cells of 2^log_cell entries as the pool (frieda_reconstruct_from_opened_cells): d_cells[n_cells][4][2^log_cell] next to
+// d_index[n_cells], both on the device and outside the arena.
+int reconstruct_cells_pooled(frieda_ctx* ctx, const uint32_t* d_cells, const uint32_t* d_index, uint32_t n_cells, uint32_t log_cell, uint32_t log_coef,
+                             uint32_t log_domain, size_t len, void* d_out_bytes, uint32_t* n_distinct);
+
+// ---- authenticated cells (cells_host.cpp, cells.hip) ----
+// The accepted cells of a frieda_reconstruct_from_opened_cells call, in the caller's order, in a device allocation of the call's own
+// (not the arena: the verify passes and the reconstruction re-plan it).  Entry e: d_idx()[e], d_val()[e][4][2^log_cell] — the cell
+// layout of the point reconstruction.
+struct CellPool {
+    uint8_t* d = nullptr;
+    size_t cap = 0, n = 0;  // entries allocated / pooled
+    uint32_t log_cell = 0;
+    uint32_t* d_idx() const { return reinterpret_cast<uint32_t*>(d); }
+    uint32_t* d_val() const { return reinterpret_cast<uint32_t*>(d + ((4 * cap + 255) & ~(size_t)255)); }
+    CellPool() = default;
+    CellPool(const CellPool&) = delete;
+    CellPool& operator=(const CellPool&) = delete;
+    ~CellPool();
+};
+// the argument rule of every cells entry point: log_cell <= min(log_domain, FRIEDA_MAX_LOG_OPEN_CELL), every index < 2^(log_domain - log_cell);
+// null when it holds, else what is wrong
+const char* cells_args_error(uint32_t log_domain, uint32_t log_cell, const uint32_t* cell_index, uint32_t n_cells);
+// one status byte per cell (FRIEDA_CELL_*): every word a canonical M31 and the subtree root, carried up the path, equal to the commitment.
+// values[n_cells][4][2^log_cell], paths[n_cells][log_domain - log_cell][32] bottom-up.  Arguments already checked (cells_args_error).
+void verify_cells_host(const uint8_t commitment[32], uint32_t log_domain, uint32_t log_cell, const uint32_t* cell_index, uint32_t n_cells,
+                       const uint32_t* values, const uint8_t* paths, uint8_t* out_status);
+// the same status bytes from the kernels, staged in passes; pool (optional): receives the accepted cells.  Uses the arena and the pinned
+// block (callers: FR_NO_JOB).
+int verify_cells_device(Ctx* ctx, const uint8_t commitment[32], uint32_t log_domain, uint32_t log_cell, const uint32_t* cell_index, uint32_t n_cells,
+                        const uint32_t* values, const uint8_t* paths, uint8_t* out_status, CellPool* pool);
+// cells of an encoded blob with their paths: one upload of the indices, the launches, one download, one synchronisation
+int open_cells(Ctx* ctx, const Encoded& enc, uint32_t log_cell, const uint32_t* cell_index, uint32_t n_cells, uint32_t* out_values, uint8_t* out_paths);
+
 // transcript pieces shared by prover and verifier (transcript.cpp)
 void channel_mix_felts(Channel& ch, const std::vector<QM31>& felts);
 std::vector<uint32_t> generate_queries(Channel& ch, uint32_t log_domain_size, uint32_t n_queries);

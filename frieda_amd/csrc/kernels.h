@@ -379,6 +379,34 @@ void verify_many(const Launch& L, const VerifyArgs& a, uint32_t n_proofs);
 void verify_pairs_gather(const Launch& L, const uint32_t* d_tab, uint32_t n_rows, const uint32_t* d_pair_pos, const uint32_t* d_pair_val, uint32_t q_cap,
                          uint32_t* d_pool_pos, uint32_t* d_pool_val);
 
+// ---- cells.hip: authenticated cells of an encoded blob (frieda_open_cells, frieda_verify_cells_many) ----
+// A cell is an aligned run of 2^log_cell entries of every column of the bit-reversed codeword; its path is the n - log_cell siblings from
+// its subtree root (node `cell` of level n - log_cell) up to the root, bottom-up.
+constexpr uint32_t CELLS_MAX_LOG_CELL = 10;  // = FRIEDA_MAX_LOG_OPEN_CELL
+struct CellsOpenArgs {
+    const uint32_t* eval;  // the encoded blob: 4 columns of 2^n words
+    const uint8_t* tree;   // its first-layer tree, leaves-first; the leaf hashes are not stored, and for n >= skip_log neither are levels n - 1, n - 2
+    uint32_t n, log_cell, skip_log, n_cells;
+    const uint32_t* idx;   // n_cells cell indices, each < 2^(n - log_cell) (checked by the caller)
+    uint32_t* out_values;  // [n_cells][4][2^log_cell], 16-byte aligned
+    uint4* out_paths;      // [n_cells][n - log_cell] hashes
+};
+void cells_open(const Launch& L, const CellsOpenArgs& a);
+struct CellsVerifyArgs {
+    const uint32_t* values;  // [n_cells][4][2^log_cell], 16-byte aligned
+    const uint4* paths;      // level-major: [n - log_cell][n_cells] hashes
+    const uint32_t* idx;     // n_cells cell indices, each < 2^(n - log_cell)
+    uint32_t* roots;         // scratch between the two launches: [8][n_cells] words (not used for log_cell 0)
+    uint32_t* bad;           // scratch: [n_cells]
+    uint32_t* status;        // out: [n_cells], 1 = accepted, 0 = rejected
+    uint32_t n, log_cell, n_cells;
+    uint32_t commitment[8];
+};
+void cells_verify(const Launch& L, const CellsVerifyArgs& a);
+// cells of a pass -> the call's pool.  d_tab[n_rows][2]: slot of the pass, entry of the pool; d_pool_idx[entry], d_pool_val[entry][4][2^log_cell]
+void cells_gather(const Launch& L, const uint32_t* d_tab, uint32_t n_rows, const uint32_t* d_values, const uint32_t* d_idx, uint32_t log_cell,
+                  uint32_t* d_pool_idx, uint32_t* d_pool_val);
+
 // ---- opening.hip: Level B openings (frieda_dev_gather*, frieda_merkle_decommit*) ----
 constexpr uint32_t OPEN_BAD_WORD = 0xFFFFFFFFu;   // gathered word of an out-of-range index (device forms only; not a canonical M31)
 constexpr uint32_t OPEN_BAD_COUNT = 0xFFFFFFFFu;  // decommit count word: the positions were not strictly ascending and in range

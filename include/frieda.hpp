@@ -132,6 +132,12 @@ class Encoded {
         return c;
     }
     size_t bytes() const { return frieda_encoded_bytes(h_); }
+    // {log_size_bound, log_domain} of the encoded codeword (frieda_encoded_shape)
+    std::pair<uint32_t, uint32_t> shape() const {
+        uint32_t l = 0, n = 0;
+        check(frieda_encoded_shape(h_, &l, &n));
+        return {l, n};
+    }
     const frieda_encoded* handle() const { return h_; }
 
   private:
@@ -321,6 +327,54 @@ class Context {
         out.resize(len);
         return out;
     }
+    // ---- authenticated cells (frieda_open_cells, frieda_verify_cells*, frieda_reconstruct_from_opened_cells) ----
+    // values[n_cells][4][2^log_cell] cell-major, paths[n_cells][log_domain - log_cell][32] bottom-up
+    struct OpenedCells {
+        std::vector<uint32_t> values;
+        std::vector<uint8_t> paths;
+    };
+    // a short vector must not reach the library: values / paths have exactly the shape of the cell list
+    static void check_cell_shapes(const char* who, uint32_t log_domain, uint32_t log_cell, size_t n_cells, size_t n_values, size_t n_path_bytes) {
+        if (log_cell > log_domain || log_cell > FRIEDA_MAX_LOG_OPEN_CELL) throw Error(FRIEDA_ERR_ARG, std::string(who) + ": log_cell out of range");
+        if (n_values != (n_cells * 4) << log_cell || n_path_bytes != n_cells * 32 * (size_t)(log_domain - log_cell))
+            throw Error(FRIEDA_ERR_ARG, std::string(who) + ": values / paths do not have the shape of the cell list");
+    }
+    OpenedCells open_cells(const Encoded& enc, uint32_t log_cell, const std::vector<uint32_t>& cell_index) {
+        const uint32_t n = enc.shape().second;
+        if (log_cell > n) throw Error(FRIEDA_ERR_ARG, "open_cells: log_cell beyond log_domain");
+        OpenedCells out{std::vector<uint32_t>((cell_index.size() * 4) << log_cell), std::vector<uint8_t>(cell_index.size() * 32 * (n - log_cell))};
+        check(frieda_open_cells(h_, enc.handle(), log_cell, cell_index.data(), (uint32_t)cell_index.size(), out.values.data(), out.paths.data()), h_);
+        return out;
+    }
+    // one status byte per cell (FRIEDA_CELL_ACCEPTED / _REJECTED), verified on the GPU; verify_cells below is the host form
+    std::vector<uint8_t> verify_cells_many(const Commitment& commitment, uint32_t log_domain, uint32_t log_cell, const std::vector<uint32_t>& cell_index,
+                                           const std::vector<uint32_t>& values, const std::vector<uint8_t>& paths) {
+        check_cell_shapes("verify_cells_many", log_domain, log_cell, cell_index.size(), values.size(), paths.size());
+        std::vector<uint8_t> status(cell_index.size());
+        check(frieda_verify_cells_many(h_, commitment.data(), log_domain, log_cell, cell_index.data(), (uint32_t)cell_index.size(), values.data(), paths.data(),
+                                       status.data()),
+              h_);
+        return status;
+    }
+    std::vector<uint8_t> reconstruct_from_opened_cells(const Commitment& commitment, uint32_t log_blowup_factor, size_t len, uint32_t log_cell,
+                                                       const std::vector<uint32_t>& cell_index, const std::vector<uint32_t>& values,
+                                                       const std::vector<uint8_t>& paths, std::vector<uint8_t>* out_status = nullptr,
+                                                       size_t* n_cells_used = nullptr) {
+        size_t n_felts = 0, n_padded = 0;
+        uint32_t log_size = 0;
+        check(frieda_codec_shape(len, &n_felts, &n_padded, &log_size));
+        check_cell_shapes("reconstruct_from_opened_cells", log_size + log_blowup_factor, log_cell, cell_index.size(), values.size(), paths.size());
+        std::vector<uint8_t> status(cell_index.size() + 1), out(len + 1);
+        size_t used = 0;
+        const int rc = frieda_reconstruct_from_opened_cells(h_, commitment.data(), log_blowup_factor, len, log_cell, cell_index.data(), (uint32_t)cell_index.size(),
+                                                            values.data(), paths.data(), out.data(), status.data(), &used);
+        status.resize(cell_index.size());
+        if (out_status) *out_status = status;
+        if (n_cells_used) *n_cells_used = used;
+        check(rc, h_);
+        out.resize(len);
+        return out;
+    }
     // Level B openings over caller device buffers (frieda_dev_gather, frieda_dev_gather_hashes, frieda_merkle_decommit)
     // rows[i * ncols + c] = column c at idx[i]
     std::vector<uint32_t> dev_gather(const uint32_t* d_cols, size_t stride, uint32_t ncols, const std::vector<uint64_t>& idx) {
@@ -471,6 +525,14 @@ inline std::optional<std::pair<std::vector<uint32_t>, std::vector<QM31>>> verify
     for (size_t i = 0; i < n; i++)
         for (int c = 0; c < 4; c++) values[i].v[c] = val[4 * i + c];
     return std::make_pair(pos, values);
+}
+// host verifier of opened cells (frieda_verify_cells): one status byte per cell, no context
+inline std::vector<uint8_t> verify_cells(const Commitment& commitment, uint32_t log_domain, uint32_t log_cell, const std::vector<uint32_t>& cell_index,
+                                         const std::vector<uint32_t>& values, const std::vector<uint8_t>& paths) {
+    Context::check_cell_shapes("verify_cells", log_domain, log_cell, cell_index.size(), values.size(), paths.size());
+    std::vector<uint8_t> status(cell_index.size());
+    check(frieda_verify_cells(commitment.data(), log_domain, log_cell, cell_index.data(), (uint32_t)cell_index.size(), values.data(), paths.data(), status.data()));
+    return status;
 }
 }  // namespace api
 

@@ -139,7 +139,8 @@ int frieda_commit_and_generate_proof_device(frieda_ctx* ctx, const void* d_data,
  * frieda_merkle_commit_layer, frieda_grind, frieda_reconstruct*_device, frieda_circle_interpolate_cells,
  * frieda_ctx_release_workspace, frieda_dev_gather, frieda_dev_gather_hashes, frieda_merkle_decommit (and
  * frieda_merkle_decommit_device beyond 512 positions), frieda_verify_many, frieda_verify_samples_many, frieda_reconstruct_from_proofs,
- * frieda_verify_pairs_many, frieda_reconstruct_from_proof_pairs (frieda_verify_pairs is host-only and takes no context).  Level B calls that only read the twiddle cache and caller buffers stay available.
+ * frieda_verify_pairs_many, frieda_reconstruct_from_proof_pairs (frieda_verify_pairs is host-only and takes no context),
+ * frieda_open_cells, frieda_verify_cells_many, frieda_reconstruct_from_opened_cells (frieda_verify_cells is host-only and takes no context).  Level B calls that only read the twiddle cache and caller buffers stay available.
  * A blob passed to _begin_device must stay valid until _finish returns. */
 int frieda_prove_begin(frieda_ctx* ctx, const uint8_t* data, size_t len, const uint64_t* seed, frieda_pcs_config cfg);
 int frieda_prove_begin_device(frieda_ctx* ctx, const void* d_data, size_t len, const uint64_t* seed, frieda_pcs_config cfg);
@@ -182,6 +183,9 @@ int frieda_encode_device(frieda_ctx* ctx, const void* d_data, size_t len, uint32
 int frieda_encoded_commitment(const frieda_encoded* enc, uint8_t out_root[32]);
 size_t frieda_encoded_bytes(const frieda_encoded* enc); /* device memory it holds */
 void frieda_encoded_free(frieda_encoded* enc);
+/* the shape of the encoded codeword: 2^log_size_bound coefficients per column, 2^log_domain evaluations (log_domain = log_size_bound +
+ * log_blowup_factor): what frieda_open_cells and the frieda_verify_cells* calls of its clients go by */
+int frieda_encoded_shape(const frieda_encoded* enc, uint32_t* log_size_bound, uint32_t* log_domain);
 /* n_seeds proofs of the encoded blob: out_proofs[i] serialises to exactly the bytes of frieda_commit_and_generate_proof(data,
  * &seeds[i], cfg); repeated seeds are allowed (identical proofs), the order is the caller's.  seeds != NULL, 1 <= n_seeds <= 65535,
  * cfg.log_blowup_factor == the one the blob was encoded with, the ctx on the blob's device, and every argument rule of the batch
@@ -283,6 +287,59 @@ int frieda_verify_pairs_many(frieda_ctx* ctx, const frieda_proof* const* proofs,
 int frieda_reconstruct_from_proof_pairs(frieda_ctx* ctx, const frieda_proof* const* proofs, const uint64_t* seeds, uint32_t count,
                                         const uint8_t expected_commitment[32], size_t len, uint8_t* out_bytes, uint8_t* out_status,
                                         size_t* n_points);
+
+/* ---- authenticated cells: open, verify and rebuild from cells of the codeword ------------------------------------------------
+ * The FRIDA flow (/root/reference/README.md:56-69): proximity is checked ONCE per commitment — a client verifies one ordinary proof of
+ * the blob — and every further sample is a cell of the codeword opened against the same first-layer root.  A cell is what the
+ * reconstruction entry points below call a cell: cell c = entries c * 2^log_cell .. (c + 1) * 2^log_cell of every column of the
+ * bit-reversed codeword, c < 2^(log_domain - log_cell), 0 <= log_cell <= min(log_domain, FRIEDA_MAX_LOG_OPEN_CELL).  Layouts, all host
+ * arrays: values[n_cells][4][2^log_cell], cell-major (what frieda_reconstruct_points_device takes);
+ * paths[n_cells][log_domain - log_cell][32], bottom-up: entry s is the sibling of the node above the cell at tree layer log_domain -
+ * log_cell - s, and that node is the left child when bit s of the cell's index is 0.  With log_cell == log_domain the path is empty and the
+ * cell's subtree root must be the commitment itself.  Hashing is the prover's trees (stwo's hash_node): a leaf is the four column words of
+ * one position, a node its two children.  A cell with its path is a self-contained message: paths are per cell, not compacted across
+ * the cells of a call, and cells served to different peers share nothing.
+ * A cell is ACCEPTED when every word is a canonical M31 (< 2^31 - 1) and the subtree root over its 2^log_cell leaves, carried up its
+ * path, equals the commitment.  One status byte per cell; a cell's status never depends on the other cells of the call.
+ * What a cell shares with a proof: the encoded blob, the first-layer tree and its root.  What it does not: no transcript, no seed, no
+ * fold chain, no proof of work, no proximity claim — a cell alone says nothing about the degree of the codeword.
+ * Every call: cell_index in any order, repeats allowed; an index >= 2^(log_domain - log_cell) or a log_cell out of range gives
+ * FRIEDA_ERR_ARG before anything runs, outputs untouched; n_cells == 0 is a no-op. */
+#define FRIEDA_MAX_LOG_OPEN_CELL 10
+#define FRIEDA_CELL_REJECTED 0
+#define FRIEDA_CELL_ACCEPTED 1
+/* Provider: cells of an encoded blob, each with its own path to frieda_encoded_commitment.  Only reads the blob, as proving does: it may
+ * be in use by a frieda_prove_seeds job on another context.  Uses ctx's workspace and pinned staging (FRIEDA_ERR_ARG while a proof is in
+ * flight on ctx); ctx must sit where the blob does, else FRIEDA_ERR_ARG.  One upload of the indices, the launches, one download, one
+ * synchronisation.  log_domain here is the blob's (frieda_encoded_shape).  out_paths may be NULL when log_cell == log_domain.
+ * The call is NOT cut into passes: the workspace and the pinned block hold the whole answer, 16 * 2^log_cell + 32 * (log_domain -
+ * log_cell) + 4 bytes per cell, and a request they cannot hold fails with FRIEDA_ERR_NOMEM (the ctx stays usable): a provider serves
+ * large requests as several calls. */
+int frieda_open_cells(frieda_ctx* ctx, const frieda_encoded* enc, uint32_t log_cell, const uint32_t* cell_index, uint32_t n_cells,
+                      uint32_t* out_values, uint8_t* out_paths);
+/* Client, host verifier: no context, one core, the Blake2s of frieda_verify.  2^log_cell + log_domain - log_cell compressions per cell. */
+int frieda_verify_cells(const uint8_t commitment[32], uint32_t log_domain, uint32_t log_cell, const uint32_t* cell_index, uint32_t n_cells,
+                        const uint32_t* values, const uint8_t* paths, uint8_t* out_status);
+/* Client, thousands of cells in one call: the same status bytes from the GPU (cells.hip: a lane per leaf pair and an LDS reduction to
+ * every subtree root, then a lane per cell up its path).  Stages through the context's workspace in passes of bounded size, as
+ * frieda_verify_many does: FRIEDA_ERR_ARG while a proof is in flight on the context.  Measured on the 128 KiB fixture (a 2^19 codeword),
+ * 513 cells of 64 entries, one MI355X against one host core (profiles/r11_open_cells.txt): 0.15 ms for the
+ * call (staging, two launches, status download) against 3.54 ms for frieda_verify_cells on the same cells — the device verifier is the
+ * faster one there, about 24 times. */
+int frieda_verify_cells_many(frieda_ctx* ctx, const uint8_t commitment[32], uint32_t log_domain, uint32_t log_cell, const uint32_t* cell_index,
+                             uint32_t n_cells, const uint32_t* values, const uint8_t* paths, uint8_t* out_status);
+/* The client's whole flow for a blob of len bytes committed with log_blowup_factor (log_size_bound follows from len as in
+ * frieda_codec_shape, log_domain = log_size_bound + log_blowup_factor): verify all cells as frieda_verify_cells_many does, drop the
+ * rejected ones, de-duplicate by index, rebuild through frieda_reconstruct_points_device's route, pack, and require frieda_commit of the
+ * len rebuilt bytes to equal commitment.  That route needs 2^(log_size_bound - log_cell) + 1 distinct cells for log_cell >= 1 and
+ * 2^log_size_bound + 2 points for log_cell == 0.  *n_cells_used receives the number of distinct accepted cells.  Too few of them, or a
+ * result that does not commit to commitment (a wrong len): FRIEDA_ERR_ARG with out_bytes untouched and out_status[n_cells] valid.  A
+ * rejected cell is never used.  Per call: two allocations of the call's own beside the workspace (the pool of accepted cells, the
+ * rebuilt bytes), freed before it returns, and the final commitment check uploads the rebuilt bytes again; the measured time of the
+ * whole call includes all of that (0.63 ms from 513 cells to the checked bytes of the fixture, same record). */
+int frieda_reconstruct_from_opened_cells(frieda_ctx* ctx, const uint8_t commitment[32], uint32_t log_blowup_factor, size_t len, uint32_t log_cell,
+                                         const uint32_t* cell_index, uint32_t n_cells, const uint32_t* values, const uint8_t* paths,
+                                         uint8_t* out_bytes, uint8_t* out_status, size_t* n_cells_used);
 
 /* ---- batch policy: how a stream of equal-length blobs is cut into batched calls ("bytes in flight") -------------------------
  * Every kernel of a batched call covers all its blobs, so the launch / Fiat-Shamir latency chain is paid once per call: small
