@@ -139,6 +139,11 @@ extern "C" {
     pub fn frieda_verify_cells_many(ctx: *mut frieda_ctx, commitment: *const u8, log_domain: u32, log_cell: u32, cell_index: *const u32, n_cells: u32, values: *const u32, paths: *const u8, out_status: *mut u8) -> c_int;
     /// verify the cells, drop the rejected ones, rebuild the blob and check it against the commitment
     pub fn frieda_reconstruct_from_opened_cells(ctx: *mut frieda_ctx, commitment: *const u8, log_blowup_factor: u32, len: usize, log_cell: u32, cell_index: *const u32, n_cells: u32, values: *const u32, paths: *const u8, out_bytes: *mut u8, out_status: *mut u8, n_cells_used: *mut usize) -> c_int;
+    // the cells of a block: cell i is cell cell_index[i] of blob blob_index[i]; a stripe is cell j of every blob
+    pub fn frieda_open_cells_blobs(ctx: *mut frieda_ctx, encs: *const *const frieda_encoded, n_blobs: u32, log_cell: u32, blob_index: *const u32, cell_index: *const u32, n_cells: u32, out_values: *mut u32, out_paths: *mut u8) -> c_int;
+    pub fn frieda_verify_cells_blobs(commitments: *const u8, n_blobs: u32, log_domain: u32, log_cell: u32, blob_index: *const u32, cell_index: *const u32, n_cells: u32, values: *const u32, paths: *const u8, out_status: *mut u8) -> c_int;
+    pub fn frieda_verify_cells_blobs_many(ctx: *mut frieda_ctx, commitments: *const u8, n_blobs: u32, log_domain: u32, log_cell: u32, blob_index: *const u32, cell_index: *const u32, n_cells: u32, values: *const u32, paths: *const u8, out_status: *mut u8) -> c_int;
+    pub fn frieda_reconstruct_blobs_from_opened_stripes(ctx: *mut frieda_ctx, commitments: *const u8, n_blobs: u32, log_blowup_factor: u32, len: usize, log_cell: u32, stripe_index: *const u32, n_stripes: u32, values: *const u32, paths: *const u8, out_bytes: *mut u8, out_status: *mut u8, n_stripes_used: *mut usize) -> c_int;
 
     // struct Proof
     pub fn frieda_proof_free(p: *mut frieda_proof);

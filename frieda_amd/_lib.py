@@ -147,6 +147,10 @@ def lib():
         "frieda_verify_cells": (C.c_int, [vp, u32, u32, vp, u32, vp, vp, vp]),
         "frieda_verify_cells_many": (C.c_int, [vp, vp, u32, u32, vp, u32, vp, vp, vp]),
         "frieda_reconstruct_from_opened_cells": (C.c_int, [vp, vp, u32, sz, u32, vp, u32, vp, vp, vp, vp, C.POINTER(sz)]),
+        "frieda_open_cells_blobs": (C.c_int, [vp, vp, u32, u32, vp, vp, u32, vp, vp]),
+        "frieda_verify_cells_blobs": (C.c_int, [vp, u32, u32, u32, vp, vp, u32, vp, vp, vp]),
+        "frieda_verify_cells_blobs_many": (C.c_int, [vp, vp, u32, u32, u32, vp, vp, u32, vp, vp, vp]),
+        "frieda_reconstruct_blobs_from_opened_stripes": (C.c_int, [vp, vp, u32, u32, sz, u32, vp, u32, vp, vp, vp, vp, C.POINTER(sz)]),
         "frieda_proof_free": (None, [vp]),
         "frieda_proof_clone": (C.c_int, [vp, pp]),
         "frieda_proof_proof_of_work": (u64, [vp]),

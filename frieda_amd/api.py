@@ -564,6 +564,47 @@ class Context:
             raise
         return out[:n_bytes].tobytes(), status[:count], n.value
 
+    # ---- the cells of a block: many blobs of one shape in one call (cell i is cell cell_index[i] of blob blob_index[i]) ----
+    def verify_cells_blobs_many(self, commitments, log_domain, log_cell, blob_index, cell_index, values, paths):
+        """One status byte per (blob, cell) pair, verified on the device in one call; the bytes verify_cells_blobs() gives."""
+        com = _commitment_table(commitments)
+        bidx, idx, val, pth = _blob_cell_arrays(log_domain, log_cell, blob_index, cell_index, values, paths)
+        status = np.zeros(len(idx), dtype=np.uint8)
+        _check(
+            self._L.frieda_verify_cells_blobs_many(self._h, com.ctypes.data, len(com) // 32, log_domain, log_cell, bidx.ctypes.data, idx.ctypes.data, len(idx),
+                                                   val.ctypes.data, pth.ctypes.data, status.ctypes.data),
+            self._h,
+        )
+        return status
+
+    def reconstruct_blobs_from_opened_stripes(self, commitments, log_blowup_factor, n_bytes, log_cell, stripe_index, values, paths):
+        """A block sampled by stripes (stripe j = cell j of every blob): values [S, K, 4, 2^log_cell], paths [S, K, log_domain - log_cell, 32].
+        Verifies every cell, uses the stripes whose K cells are all accepted and rebuilds all K blobs in one reconstruction:
+        (list of K bytes, status uint8 [S, K], n_stripes_used).  Raises FriedaError (with .n_stripes_used and .cell_status set) when the
+        fully accepted stripes do not suffice or a blob does not commit to its commitment."""
+        com = _commitment_table(commitments)
+        K = len(com) // 32
+        log_domain = codec_log_size(n_bytes) + log_blowup_factor
+        stripes = np.ascontiguousarray(stripe_index, dtype=np.uint32).reshape(-1)
+        S = len(stripes)
+        _, val, pth = _cell_arrays(log_domain, log_cell, np.zeros(S * K, dtype=np.uint32), values, paths)
+        status = np.zeros(max(S * K, 1), dtype=np.uint8)
+        out = np.zeros(max(n_bytes * K, 1), dtype=np.uint8)
+        n = C.c_size_t(0)
+        try:
+            _check(
+                self._L.frieda_reconstruct_blobs_from_opened_stripes(
+                    self._h, com.ctypes.data, K, log_blowup_factor, n_bytes, log_cell, stripes.ctypes.data, S, val.ctypes.data, pth.ctypes.data,
+                    out.ctypes.data, status.ctypes.data, C.byref(n)
+                ),
+                self._h,
+            )
+        except FriedaError as e:
+            e.n_stripes_used = n.value
+            e.cell_status = status[: S * K].reshape(S, K)
+            raise
+        return [out[b * n_bytes : (b + 1) * n_bytes].tobytes() for b in range(K)], status[: S * K].reshape(S, K), n.value
+
 
 def codec_log_size(n_bytes):
     """log2 of the coefficients per column of a blob of n_bytes (frieda_codec_shape)."""
@@ -588,6 +629,23 @@ def _cell_arrays(log_domain, log_cell, cell_index, values, paths):
     if idx.size == 0:
         idx = np.zeros(0, dtype=np.uint32)
     return idx, val, pth
+
+
+def _commitment_table(commitments):
+    """[K][32] commitments -> one contiguous uint8 array of 32 K bytes"""
+    rows = [bytes(c) for c in commitments]
+    if not rows or any(len(r) != 32 for r in rows):
+        raise FriedaError(_lib.ERR_ARG, "commitments: need at least one, 32 bytes each")
+    return np.frombuffer(b"".join(rows), dtype=np.uint8).copy()
+
+
+def _blob_cell_arrays(log_domain, log_cell, blob_index, cell_index, values, paths):
+    """_cell_arrays plus the blob numbers: one per cell"""
+    idx, val, pth = _cell_arrays(log_domain, log_cell, cell_index, values, paths)
+    bidx = np.ascontiguousarray(blob_index, dtype=np.uint32).reshape(-1)
+    if len(bidx) != len(idx):
+        raise FriedaError(_lib.ERR_ARG, "blob_index / cell_index: one blob number per cell")
+    return bidx, idx, val, pth
 
 
 class Encoded:
@@ -1076,3 +1134,57 @@ def verify_cells_many(commitment, log_domain, log_cell, cell_index, values, path
 def reconstruct_from_opened_cells(commitment, log_blowup_factor, n_bytes, log_cell, cell_index, values, paths):
     """frieda_reconstruct_from_opened_cells on the default context: (bytes, status, n_cells_used)."""
     return default_context().reconstruct_from_opened_cells(commitment, log_blowup_factor, n_bytes, log_cell, cell_index, values, paths)
+
+
+def open_cells_blobs(ctx, encs, log_cell, blob_index, cell_index):
+    """Cells of many encoded blobs of one shape in ONE call (frieda_open_cells_blobs on `ctx`): pair i is cell cell_index[i] of
+    encs[blob_index[i]].  (values uint32 [n, 4, 2^log_cell], paths uint8 [n, log_domain - log_cell, 32])."""
+    encs = list(encs)
+    if not encs:
+        raise FriedaError(_lib.ERR_ARG, "open_cells_blobs: no blobs")
+    log_domain = encs[0].shape[1]
+    if not 0 <= log_cell <= log_domain:
+        raise FriedaError(_lib.ERR_ARG, "log_cell out of range")
+    bidx = np.ascontiguousarray(blob_index, dtype=np.uint32).reshape(-1)
+    idx = np.ascontiguousarray(cell_index, dtype=np.uint32).reshape(-1)
+    if len(bidx) != len(idx):
+        raise FriedaError(_lib.ERR_ARG, "blob_index / cell_index: one blob number per cell")
+    handles = (C.c_void_p * len(encs))(*[e._handle() for e in encs])
+    values = np.zeros((len(idx), 4, 1 << log_cell), dtype=np.uint32)
+    paths = np.zeros((len(idx), log_domain - log_cell, 32), dtype=np.uint8)
+    _check(
+        _lib.lib().frieda_open_cells_blobs(ctx._h, handles, len(encs), log_cell, bidx.ctypes.data, idx.ctypes.data, len(idx),
+                                           values.ctypes.data if values.size else None, paths.ctypes.data if paths.size else None),
+        ctx._h,
+    )
+    return values, paths
+
+
+def open_stripes(ctx, encs, log_cell, stripe_index):
+    """Stripe j of a block = cell j of each of its K blobs.  One open_cells_blobs call: (values uint32 [S, K, 4, 2^log_cell],
+    paths uint8 [S, K, log_domain - log_cell, 32]) — what Context.reconstruct_blobs_from_opened_stripes takes."""
+    encs = list(encs)
+    stripes = np.ascontiguousarray(stripe_index, dtype=np.uint32).reshape(-1)
+    S, K = len(stripes), len(encs)
+    values, paths = open_cells_blobs(ctx, encs, log_cell, np.tile(np.arange(K, dtype=np.uint32), S), np.repeat(stripes, K))
+    return values.reshape(S, K, 4, -1), paths.reshape(S, K, -1, 32)
+
+
+def verify_cells_blobs(commitments, log_domain, log_cell, blob_index, cell_index, values, paths):
+    """The host verifier over (blob, cell) pairs (frieda_verify_cells_blobs: no context): one status byte per pair (numpy uint8)."""
+    com = _commitment_table(commitments)
+    bidx, idx, val, pth = _blob_cell_arrays(log_domain, log_cell, blob_index, cell_index, values, paths)
+    status = np.zeros(len(idx), dtype=np.uint8)
+    _check(_lib.lib().frieda_verify_cells_blobs(com.ctypes.data, len(com) // 32, log_domain, log_cell, bidx.ctypes.data, idx.ctypes.data, len(idx),
+                                                val.ctypes.data, pth.ctypes.data, status.ctypes.data))
+    return status
+
+
+def verify_cells_blobs_many(commitments, log_domain, log_cell, blob_index, cell_index, values, paths):
+    """frieda_verify_cells_blobs_many on the default context."""
+    return default_context().verify_cells_blobs_many(commitments, log_domain, log_cell, blob_index, cell_index, values, paths)
+
+
+def reconstruct_blobs_from_opened_stripes(commitments, log_blowup_factor, n_bytes, log_cell, stripe_index, values, paths):
+    """frieda_reconstruct_blobs_from_opened_stripes on the default context: (list of bytes, status [S, K], n_stripes_used)."""
+    return default_context().reconstruct_blobs_from_opened_stripes(commitments, log_blowup_factor, n_bytes, log_cell, stripe_index, values, paths)

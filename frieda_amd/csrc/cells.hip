@@ -16,6 +16,10 @@
 //                   launch: the walk's lane hashes its one leaf itself.  (One fused launch would leave the walk with 2^(9 - c) busy lanes
 //                   of 256 per workgroup; the compressions are the plain form — neither launch fills the chip at a client's cell counts.)
 //   cells_gather    the accepted cells of a pass -> the pool the reconstruction reads (verify.hip's pairs_gather_kernel for cells).
+//   *_blobs         the same for cells of MANY blobs of one shape in one call: open reads eval / tree / skip_log from a per-blob table, the
+//                   walk compares with a table of commitments in device memory; cells_roots is shared as it is.
+//   cells_stripe_*  a stripe = cell j of every blob of a block.  accept: a wave per stripe ANDs its cells' status words; gather: the fully
+//                   accepted stripes -> the pool, which is the point reconstruction's layout at 4 * n_blobs columns.
 #include "kernels.h"
 #include "tree_dev.h"
 
@@ -31,7 +35,7 @@ __device__ __forceinline__ void leaf_at(const uint32_t* __restrict__ v, size_t c
 }
 
 // node `node` of level n - up (up = 0: a leaf hash, 1: the parent of two leaves, 2: of four) from the evaluation v[4][2^n]
-__device__ void node_from_eval(const uint32_t* __restrict__ v, uint32_t n, uint32_t up, size_t node, uint32_t (&h)[8]) {
+__device__ __forceinline__ void node_from_eval(const uint32_t* __restrict__ v, uint32_t n, uint32_t up, size_t node, uint32_t (&h)[8]) {
     const size_t cs = (size_t)1 << n;
     uint32_t l[4], r[4];
     if (up == 0) {
@@ -200,6 +204,105 @@ __global__ __launch_bounds__(CL_THREADS) void cells_gather_kernel(const uint32_t
     if (w == 0) pool_idx[dst] = idx[src];
 }
 
+// ---- the cells of many blobs of one shape in one call: cell i is cell idx[i] of blob bidx[i] ----
+// cells_open_values_kernel with eval taken from the cell's row of the blob table
+template <int VEC>
+__global__ __launch_bounds__(CL_THREADS) void cells_open_blobs_values_kernel(CellsOpenBlobsArgs a) {
+    const size_t e = (size_t)blockIdx.x * CL_THREADS + threadIdx.x;
+    const uint32_t c = a.log_cell, lu = c - (VEC == 4 ? 2 : 0);
+    if (e >= ((size_t)a.n_cells * 4) << lu) return;
+    const size_t run = e >> lu, cell = run >> 2;
+    const uint32_t col = (uint32_t)(run & 3), u = (uint32_t)(e & (((size_t)1 << lu) - 1));
+    const uint32_t* __restrict__ eval = a.table[a.bidx[cell]].eval;
+    const size_t src = ((size_t)col << a.n) + ((size_t)a.idx[cell] << c) + (size_t)u * VEC;
+    if constexpr (VEC == 4)
+        reinterpret_cast<uint4*>(a.out_values)[e] = *reinterpret_cast<const uint4*>(eval + src);
+    else
+        a.out_values[e] = eval[src];
+}
+
+// cells_open_paths_kernel with eval, tree and skip_log taken from the cell's row: the "stored" rule is evaluated per blob
+__global__ __launch_bounds__(CL_THREADS) void cells_open_blobs_paths_kernel(CellsOpenBlobsArgs a) {
+    const size_t e = (size_t)blockIdx.x * CL_THREADS + threadIdx.x;
+    const uint32_t depth = a.n - a.log_cell;
+    if (e >= (size_t)a.n_cells * depth) return;
+    const size_t cell = e / depth;
+    const uint32_t s = (uint32_t)(e - cell * depth), level = depth - s;
+    const size_t node = (size_t)(a.idx[cell] >> s) ^ 1;
+    const CellsBlobRow row = a.table[a.bidx[cell]];
+    uint4* o = a.out_paths + 2 * e;
+    const bool stored = level < a.n && !(a.n >= row.skip_log && level + 2 >= a.n);
+    if (stored) {
+        const uint4* p = reinterpret_cast<const uint4*>(row.tree + treedev::layer_off(a.n, level) + 32 * node);
+        const uint4 x = p[0], y = p[1];
+        o[0] = x, o[1] = y;
+    } else {
+        uint32_t h[8];
+        node_from_eval(row.eval, a.n, a.n - level, node, h);
+        o[0] = make_uint4(h[0], h[1], h[2], h[3]);
+        o[1] = make_uint4(h[4], h[5], h[6], h[7]);
+    }
+}
+
+// cells_walk_kernel against a table of commitments in device memory: lane `cell` compares with coms[bidx[cell]][8]
+template <bool LEAF>
+__global__ __launch_bounds__(CL_THREADS) void cells_walk_blobs_kernel(CellsVerifyArgs a, const uint32_t* __restrict__ bidx, const uint32_t* __restrict__ coms) {
+    const size_t cell = (size_t)blockIdx.x * CL_THREADS + threadIdx.x;
+    if (cell >= a.n_cells) return;
+    uint32_t h[8], bad;
+    if constexpr (LEAF) {
+        const uint4 v = reinterpret_cast<const uint4*>(a.values)[cell];
+        bad = (v.x >= P31) | (v.y >= P31) | (v.z >= P31) | (v.w >= P31);
+        treedev::leaf_hash<B2_LAT>(v.x, v.y, v.z, v.w, h);
+    } else {
+#pragma unroll
+        for (int w = 0; w < 8; w++) h[w] = a.roots[(size_t)w * a.n_cells + cell];
+        bad = a.bad[cell];
+    }
+    const uint32_t idx = a.idx[cell], depth = a.n - a.log_cell;
+#pragma unroll 1
+    for (uint32_t s = 0; s < depth; s++) {
+        const uint4* p = a.paths + 2 * ((size_t)s * a.n_cells + cell);
+        const uint4 x = p[0], y = p[1];
+        const uint32_t sib[8] = {x.x, x.y, x.z, x.w, y.x, y.y, y.z, y.w};
+        const bool right = (idx >> s) & 1;
+        uint32_t m[16];
+#pragma unroll
+        for (int w = 0; w < 8; w++) m[w] = right ? sib[w] : h[w], m[8 + w] = right ? h[w] : sib[w];
+        b2_merkle_block<B2_LAT>(m, h);
+    }
+    const uint4* want = reinterpret_cast<const uint4*>(coms + 8 * (size_t)bidx[cell]);
+    const uint4 x = want[0], y = want[1];
+    const uint32_t diff = bad | (h[0] ^ x.x) | (h[1] ^ x.y) | (h[2] ^ x.z) | (h[3] ^ x.w) | (h[4] ^ y.x) | (h[5] ^ y.y) | (h[6] ^ y.z) | (h[7] ^ y.w);
+    a.status[cell] = diff == 0 ? 1u : 0u;
+}
+
+// a wave per stripe: its lanes AND the status words of the stripe's n_blobs cells (any n_blobs: the lanes stride over them), one vote
+__global__ __launch_bounds__(CL_THREADS) void cells_stripe_accept_kernel(const uint32_t* __restrict__ status, uint32_t n_stripes, uint32_t n_blobs,
+                                                                         uint32_t* __restrict__ accept) {
+    const uint32_t lane = threadIdx.x & 63;
+    const size_t stripe = (size_t)blockIdx.x * (CL_THREADS / 64) + (threadIdx.x >> 6);
+    if (stripe >= n_stripes) return;  // (the whole wave leaves)
+    const uint32_t* st = status + stripe * n_blobs;
+    bool ok = true;
+    for (uint32_t b = lane; b < n_blobs; b += 64) ok = ok && st[b] == 1u;
+    const bool all_ok = __all(ok);
+    if (lane == 0) accept[stripe] = all_ok ? 1u : 0u;
+}
+
+// row r of the table: (stripe of the pass, entry of the pool); 16-byte copies (a cell is at least four words)
+__global__ __launch_bounds__(CL_THREADS) void cells_stripe_gather_kernel(const uint32_t* __restrict__ tab, uint32_t n_rows, const uint32_t* __restrict__ values,
+                                                                         const uint32_t* __restrict__ idx, uint32_t n_blobs, uint32_t log_cell,
+                                                                         uint32_t* __restrict__ pool_idx, uint32_t* __restrict__ pool_val) {
+    const size_t e = (size_t)blockIdx.x * CL_THREADS + threadIdx.x;
+    const size_t units = (size_t)n_blobs << log_cell;  // 16-byte units of a stripe
+    if (e >= (size_t)n_rows * units) return;
+    const size_t row = e / units, u = e - row * units;
+    const size_t src = tab[2 * row], dst = tab[2 * row + 1];
+    reinterpret_cast<uint4*>(pool_val)[dst * units + u] = reinterpret_cast<const uint4*>(values)[src * units + u];
+    if (u == 0) pool_idx[dst] = idx[src * n_blobs];
+}
+
 unsigned blocks_for(size_t units) { return (unsigned)((units + CL_THREADS - 1) / CL_THREADS); }
 
 }  // namespace
@@ -241,6 +344,52 @@ void cells_gather(const Launch& L, const uint32_t* d_tab, uint32_t n_rows, const
     Scope scope(L, "cells_gather", 0.0);
     cells_gather_kernel<<<blocks_for((size_t)n_rows << (log_cell + 2)), CL_THREADS, 0, L.stream>>>(d_tab, n_rows, d_values, d_idx, log_cell, d_pool_idx,
                                                                                                   d_pool_val);
+}
+
+void cells_open_blobs(const Launch& L, const CellsOpenBlobsArgs& a) {
+    if (!a.n_cells) return;
+    {
+        Scope scope(L, "cells_open_blobs_values", 32.0 * (double)(((size_t)a.n_cells) << a.log_cell));
+        if (a.log_cell >= 2)
+            cells_open_blobs_values_kernel<4><<<blocks_for(((size_t)a.n_cells * 4) << (a.log_cell - 2)), CL_THREADS, 0, L.stream>>>(a);
+        else
+            cells_open_blobs_values_kernel<1><<<blocks_for(((size_t)a.n_cells * 4) << a.log_cell), CL_THREADS, 0, L.stream>>>(a);
+    }
+    if (a.n > a.log_cell) {
+        Scope scope(L, "cells_open_blobs_paths", 64.0 * (double)a.n_cells * (a.n - a.log_cell));
+        cells_open_blobs_paths_kernel<<<blocks_for((size_t)a.n_cells * (a.n - a.log_cell)), CL_THREADS, 0, L.stream>>>(a);
+    }
+}
+
+void cells_verify_blobs(const Launch& L, const CellsVerifyArgs& a, const uint32_t* d_bidx, const uint32_t* d_commitments) {
+    if (!a.n_cells) return;
+    if (a.log_cell == 0) {
+        Scope scope(L, "cells_walk_blobs", 0.0);
+        cells_walk_blobs_kernel<true><<<blocks_for(a.n_cells), CL_THREADS, 0, L.stream>>>(a, d_bidx, d_commitments);
+        return;
+    }
+    {
+        Scope scope(L, "cells_roots", 0.0);  // (knows neither index nor commitment: the single-blob launch)
+        const uint32_t cpw = a.log_cell >= 10 ? 1u : 1u << (9 - a.log_cell);
+        cells_roots_kernel<<<(a.n_cells + cpw - 1) / cpw, CL_THREADS, 0, L.stream>>>(a);
+    }
+    Scope scope(L, "cells_walk_blobs", 0.0);
+    cells_walk_blobs_kernel<false><<<blocks_for(a.n_cells), CL_THREADS, 0, L.stream>>>(a, d_bidx, d_commitments);
+}
+
+void cells_stripe_accept(const Launch& L, const uint32_t* d_status, uint32_t n_stripes, uint32_t n_blobs, uint32_t* d_accept) {
+    if (!n_stripes) return;
+    Scope scope(L, "cells_stripe_accept", 0.0);
+    const uint32_t per = CL_THREADS / 64;
+    cells_stripe_accept_kernel<<<(n_stripes + per - 1) / per, CL_THREADS, 0, L.stream>>>(d_status, n_stripes, n_blobs, d_accept);
+}
+
+void cells_stripe_gather(const Launch& L, const uint32_t* d_tab, uint32_t n_rows, const uint32_t* d_values, const uint32_t* d_idx, uint32_t n_blobs,
+                         uint32_t log_cell, uint32_t* d_pool_idx, uint32_t* d_pool_val) {
+    if (!n_rows) return;
+    Scope scope(L, "cells_stripe_gather", 0.0);
+    cells_stripe_gather_kernel<<<blocks_for((size_t)n_rows * ((size_t)n_blobs << log_cell)), CL_THREADS, 0, L.stream>>>(d_tab, n_rows, d_values, d_idx, n_blobs,
+                                                                                                                      log_cell, d_pool_idx, d_pool_val);
 }
 
 }  // namespace k

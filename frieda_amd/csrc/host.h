@@ -292,6 +292,23 @@ int verify_cells_device(Ctx* ctx, const uint8_t commitment[32], uint32_t log_dom
                         const uint32_t* values, const uint8_t* paths, uint8_t* out_status, CellPool* pool);
 // cells of an encoded blob with their paths: one upload of the indices, the launches, one download, one synchronisation
 int open_cells(Ctx* ctx, const Encoded& enc, uint32_t log_cell, const uint32_t* cell_index, uint32_t n_cells, uint32_t* out_values, uint8_t* out_paths);
+// ---- the cells of many blobs of one shape in one call: cell i is cell cell_index[i] of blob blob_index[i] (arguments already checked) ----
+// host verifier: commitments[n_blobs][32]
+void verify_cells_blobs_host(const uint8_t* commitments, uint32_t log_domain, uint32_t log_cell, const uint32_t* blob_index, const uint32_t* cell_index,
+                             uint32_t n_cells, const uint32_t* values, const uint8_t* paths, uint8_t* out_status);
+// device verifier, staged in passes as verify_cells_device; the commitments are uploaded once.  stripes (optional): the cells are
+// [n_cells / n_blobs][n_blobs] — stripe t is cell cell_index[t] of every blob, blob_index is not read — the passes are cut at stripe
+// boundaries and the stripes whose cells are ALL accepted are gathered into it: entry e: d_idx()[e], d_val()[e][n_blobs][4][2^log_cell].
+int verify_cells_blobs_device(Ctx* ctx, const uint8_t* commitments, uint32_t n_blobs, uint32_t log_domain, uint32_t log_cell, const uint32_t* blob_index,
+                              const uint32_t* cell_index, uint32_t n_cells, const uint32_t* values, const uint8_t* paths, uint8_t* out_status,
+                              CellPool* stripes);
+// provider: one upload (indices, blob numbers, a table row per blob), the launches, one download, one synchronisation; skip_log is per blob
+int open_cells_blobs(Ctx* ctx, const Encoded* const* encs, uint32_t n_blobs, uint32_t log_cell, const uint32_t* blob_index, const uint32_t* cell_index,
+                     uint32_t n_cells, uint32_t* out_values, uint8_t* out_paths);
+// n_blobs blobs from a pool of stripes (d_cells[n_stripes][n_blobs][4][2^log_cell] next to d_index[n_stripes], outside the arena): ONE point
+// reconstruction over 4 * n_blobs columns — one locator for all of them — then blob b packed to d_out_bytes + b * out_stride.
+int reconstruct_stripes_pooled(frieda_ctx* ctx, const uint32_t* d_cells, const uint32_t* d_index, uint32_t n_stripes, uint32_t n_blobs, uint32_t log_cell,
+                               uint32_t log_coef, uint32_t log_domain, size_t len, uint8_t* d_out_bytes, size_t out_stride, uint32_t* n_distinct);
 
 // transcript pieces shared by prover and verifier (transcript.cpp)
 void channel_mix_felts(Channel& ch, const std::vector<QM31>& felts);

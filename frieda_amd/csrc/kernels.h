@@ -406,6 +406,31 @@ void cells_verify(const Launch& L, const CellsVerifyArgs& a);
 // cells of a pass -> the call's pool.  d_tab[n_rows][2]: slot of the pass, entry of the pool; d_pool_idx[entry], d_pool_val[entry][4][2^log_cell]
 void cells_gather(const Launch& L, const uint32_t* d_tab, uint32_t n_rows, const uint32_t* d_values, const uint32_t* d_idx, uint32_t log_cell,
                   uint32_t* d_pool_idx, uint32_t* d_pool_val);
+// The same for the cells of many blobs of one shape in one call (frieda_open_cells_blobs, frieda_verify_cells_blobs_many,
+// frieda_reconstruct_blobs_from_opened_stripes): cell i is cell idx[i] of blob bidx[i].
+struct CellsBlobRow {      // one encoded blob of the call
+    const uint32_t* eval;  // as CellsOpenArgs::eval
+    const uint8_t* tree;   // as CellsOpenArgs::tree
+    uint32_t skip_log;     // the threshold THIS blob's tree was built with
+    uint32_t pad;
+};
+struct CellsOpenBlobsArgs {
+    const CellsBlobRow* table;  // n_blobs rows, all of domain 2^n
+    const uint32_t* bidx;       // n_cells blob numbers, each < n_blobs (checked by the caller)
+    const uint32_t* idx;        // n_cells cell indices, each < 2^(n - log_cell) (checked by the caller)
+    uint32_t n, log_cell, n_cells;
+    uint32_t* out_values;  // [n_cells][4][2^log_cell], 16-byte aligned
+    uint4* out_paths;      // [n_cells][n - log_cell] hashes
+};
+void cells_open_blobs(const Launch& L, const CellsOpenBlobsArgs& a);
+// cells_verify with lane `cell` compared against d_commitments[d_bidx[cell]] (8 words per blob, in device memory); a.commitment is not read
+void cells_verify_blobs(const Launch& L, const CellsVerifyArgs& a, const uint32_t* d_bidx, const uint32_t* d_commitments);
+// Stripes: the cells of a pass are [n_stripes][n_blobs].  d_accept[s] = 1 iff all n_blobs status words of stripe s are 1, else 0.
+void cells_stripe_accept(const Launch& L, const uint32_t* d_status, uint32_t n_stripes, uint32_t n_blobs, uint32_t* d_accept);
+// stripes of a pass -> the call's pool.  d_tab[n_rows][2]: stripe of the pass, entry of the pool; d_pool_idx[entry] = the stripe's cell index
+// (d_idx of its first cell), d_pool_val[entry][n_blobs][4][2^log_cell]: the d_cells layout of the point reconstruction at 4 * n_blobs columns
+void cells_stripe_gather(const Launch& L, const uint32_t* d_tab, uint32_t n_rows, const uint32_t* d_values, const uint32_t* d_idx, uint32_t n_blobs,
+                         uint32_t log_cell, uint32_t* d_pool_idx, uint32_t* d_pool_val);
 
 // ---- opening.hip: Level B openings (frieda_dev_gather*, frieda_merkle_decommit*) ----
 constexpr uint32_t OPEN_BAD_WORD = 0xFFFFFFFFu;   // gathered word of an out-of-range index (device forms only; not a canonical M31)

@@ -481,6 +481,24 @@ int reconstruct_cells_pooled(frieda_ctx* ctx, const uint32_t* d_cells, const uin
     return FRIEDA_OK;
 }
 
+int reconstruct_stripes_pooled(frieda_ctx* ctx, const uint32_t* d_cells, const uint32_t* d_index, uint32_t n_stripes, uint32_t n_blobs, uint32_t log_cell,
+                               uint32_t log_coef, uint32_t log_domain, size_t len, uint8_t* d_out_bytes, size_t out_stride, uint32_t* n_distinct) {
+    if (!ctx || !d_cells || !d_index || !n_distinct || (len && !d_out_bytes) || n_stripes == 0 || n_blobs == 0 || n_blobs > 256 ||
+        log_coef > FRIEDA_MAX_LOG_DOMAIN)
+        return FRIEDA_ERR_ARG;
+    const size_t n_felts = (size_t)4 << log_coef;
+    if ((8 * len + 29) / 30 > n_felts) return ctx->c.fail(FRIEDA_ERR_ARG, "len does not fit the polynomial");
+    FR_HIP(&ctx->c, hipSetDevice(ctx->c.device));
+    const size_t coef_bytes = (sizeof(uint32_t) * n_felts * n_blobs + 255) & ~(size_t)255;
+    int rc = interpolate_points(ctx, d_cells, nullptr, n_stripes, 4 * n_blobs, log_cell, log_coef, log_domain, nullptr, coef_bytes, d_index, n_distinct);
+    if (rc) return rc;
+    // blob b's four coefficient columns are columns 4 b .. 4 b + 3: n_felts consecutive words
+    for (uint32_t b = 0; b < n_blobs; b++)
+        k::pack30(ctx->c.launch(), reinterpret_cast<const uint32_t*>(ctx->c.arena) + (size_t)b * n_felts, n_felts, d_out_bytes + (size_t)b * out_stride, len);
+    FR_HIP(&ctx->c, hipGetLastError());
+    return FRIEDA_OK;
+}
+
 // the de-duplication of interpolate_points alone
 int count_distinct_points(frieda_ctx* ctx, const uint32_t* d_index, uint32_t n_points, uint32_t log_domain, uint32_t* n_distinct) {
     if (!ctx || !n_distinct || (n_points && !d_index) || log_domain > FRIEDA_MAX_LOG_DOMAIN) return FRIEDA_ERR_ARG;

@@ -375,6 +375,62 @@ class Context {
         out.resize(len);
         return out;
     }
+    // ---- the cells of a block: many blobs of one shape in one call (frieda_open_cells_blobs, frieda_verify_cells_blobs*,
+    // frieda_reconstruct_blobs_from_opened_stripes).  Cell i of a call is cell cell_index[i] of blob blob_index[i].
+    static std::vector<uint8_t> flat_commitments(const std::vector<Commitment>& commitments) {
+        std::vector<uint8_t> flat(32 * commitments.size());
+        for (size_t b = 0; b < commitments.size(); b++) std::copy(commitments[b].begin(), commitments[b].end(), flat.begin() + 32 * b);
+        return flat;
+    }
+    OpenedCells open_cells_blobs(const std::vector<const Encoded*>& encs, uint32_t log_cell, const std::vector<uint32_t>& blob_index,
+                                 const std::vector<uint32_t>& cell_index) {
+        if (encs.empty() || blob_index.size() != cell_index.size()) throw Error(FRIEDA_ERR_ARG, "open_cells_blobs: one blob number per cell, at least one blob");
+        std::vector<const frieda_encoded*> handles;
+        for (const Encoded* e : encs) handles.push_back(e ? e->handle() : nullptr);
+        if (!encs[0]) throw Error(FRIEDA_ERR_ARG, "open_cells_blobs: null blob");
+        const uint32_t n = encs[0]->shape().second;
+        if (log_cell > n) throw Error(FRIEDA_ERR_ARG, "open_cells_blobs: log_cell beyond log_domain");
+        OpenedCells out{std::vector<uint32_t>((cell_index.size() * 4) << log_cell), std::vector<uint8_t>(cell_index.size() * 32 * (n - log_cell))};
+        check(frieda_open_cells_blobs(h_, handles.data(), (uint32_t)handles.size(), log_cell, blob_index.data(), cell_index.data(), (uint32_t)cell_index.size(),
+                                      out.values.data(), out.paths.data()),
+              h_);
+        return out;
+    }
+    std::vector<uint8_t> verify_cells_blobs_many(const std::vector<Commitment>& commitments, uint32_t log_domain, uint32_t log_cell,
+                                                 const std::vector<uint32_t>& blob_index, const std::vector<uint32_t>& cell_index,
+                                                 const std::vector<uint32_t>& values, const std::vector<uint8_t>& paths) {
+        if (blob_index.size() != cell_index.size()) throw Error(FRIEDA_ERR_ARG, "verify_cells_blobs_many: one blob number per cell");
+        check_cell_shapes("verify_cells_blobs_many", log_domain, log_cell, cell_index.size(), values.size(), paths.size());
+        const std::vector<uint8_t> flat = flat_commitments(commitments);
+        std::vector<uint8_t> status(cell_index.size());
+        check(frieda_verify_cells_blobs_many(h_, flat.data(), (uint32_t)commitments.size(), log_domain, log_cell, blob_index.data(), cell_index.data(),
+                                             (uint32_t)cell_index.size(), values.data(), paths.data(), status.data()),
+              h_);
+        return status;
+    }
+    // values[n_stripes][n_blobs][4][2^log_cell], paths[n_stripes][n_blobs][log_domain - log_cell][32] -> blob b's bytes at [b]
+    std::vector<std::vector<uint8_t>> reconstruct_blobs_from_opened_stripes(const std::vector<Commitment>& commitments, uint32_t log_blowup_factor, size_t len,
+                                                                            uint32_t log_cell, const std::vector<uint32_t>& stripe_index,
+                                                                            const std::vector<uint32_t>& values, const std::vector<uint8_t>& paths,
+                                                                            std::vector<uint8_t>* out_status = nullptr, size_t* n_stripes_used = nullptr) {
+        size_t n_felts = 0, n_padded = 0;
+        uint32_t log_size = 0;
+        check(frieda_codec_shape(len, &n_felts, &n_padded, &log_size));
+        const size_t K = commitments.size(), cells = stripe_index.size() * K;
+        check_cell_shapes("reconstruct_blobs_from_opened_stripes", log_size + log_blowup_factor, log_cell, cells, values.size(), paths.size());
+        const std::vector<uint8_t> flat = flat_commitments(commitments);
+        std::vector<uint8_t> status(cells + 1), out(len * K + 1);
+        size_t used = 0;
+        const int rc = frieda_reconstruct_blobs_from_opened_stripes(h_, flat.data(), (uint32_t)K, log_blowup_factor, len, log_cell, stripe_index.data(),
+                                                                    (uint32_t)stripe_index.size(), values.data(), paths.data(), out.data(), status.data(), &used);
+        status.resize(cells);
+        if (out_status) *out_status = status;
+        if (n_stripes_used) *n_stripes_used = used;
+        check(rc, h_);
+        std::vector<std::vector<uint8_t>> blobs(K);
+        for (size_t b = 0; b < K; b++) blobs[b].assign(out.begin() + b * len, out.begin() + (b + 1) * len);
+        return blobs;
+    }
     // Level B openings over caller device buffers (frieda_dev_gather, frieda_dev_gather_hashes, frieda_merkle_decommit)
     // rows[i * ncols + c] = column c at idx[i]
     std::vector<uint32_t> dev_gather(const uint32_t* d_cols, size_t stride, uint32_t ncols, const std::vector<uint64_t>& idx) {
@@ -532,6 +588,18 @@ inline std::vector<uint8_t> verify_cells(const Commitment& commitment, uint32_t 
     Context::check_cell_shapes("verify_cells", log_domain, log_cell, cell_index.size(), values.size(), paths.size());
     std::vector<uint8_t> status(cell_index.size());
     check(frieda_verify_cells(commitment.data(), log_domain, log_cell, cell_index.data(), (uint32_t)cell_index.size(), values.data(), paths.data(), status.data()));
+    return status;
+}
+// host verifier of the cells of many blobs (frieda_verify_cells_blobs): cell i is cell cell_index[i] of blob blob_index[i]
+inline std::vector<uint8_t> verify_cells_blobs(const std::vector<Commitment>& commitments, uint32_t log_domain, uint32_t log_cell,
+                                               const std::vector<uint32_t>& blob_index, const std::vector<uint32_t>& cell_index,
+                                               const std::vector<uint32_t>& values, const std::vector<uint8_t>& paths) {
+    if (blob_index.size() != cell_index.size()) throw Error(FRIEDA_ERR_ARG, "verify_cells_blobs: one blob number per cell");
+    Context::check_cell_shapes("verify_cells_blobs", log_domain, log_cell, cell_index.size(), values.size(), paths.size());
+    const std::vector<uint8_t> flat = Context::flat_commitments(commitments);
+    std::vector<uint8_t> status(cell_index.size());
+    check(frieda_verify_cells_blobs(flat.data(), (uint32_t)commitments.size(), log_domain, log_cell, blob_index.data(), cell_index.data(),
+                                    (uint32_t)cell_index.size(), values.data(), paths.data(), status.data()));
     return status;
 }
 }  // namespace api
