@@ -64,6 +64,7 @@ extern "C" {
     pub fn frieda_ctx_test_set_grind_first_log(ctx: *mut frieda_ctx, log_first: u32) -> c_int;
     pub fn frieda_ctx_test_set_arena_limit(ctx: *mut frieda_ctx, bytes: u64) -> c_int;
     pub fn frieda_ctx_test_set_verify_pass_bytes(ctx: *mut frieda_ctx, bytes: u64) -> c_int;
+    pub fn frieda_ctx_test_poison(ctx: *mut frieda_ctx, word: u32, sticky: c_int, out_bytes: *mut u64) -> c_int;
     pub fn frieda_test_near_cpus(sysfs_root: *const c_char, pci_bus_id: *const c_char, out_cpus: *mut c_int, cap: usize, n: *mut usize) -> c_int;
     pub fn frieda_test_parse_cpulist(text: *const c_char, out_cpus: *mut c_int, cap: usize, n: *mut usize) -> c_int;
     /// batch policy: device workspace one blob adds to a batched call; the cut of `count` equal-length blobs into calls

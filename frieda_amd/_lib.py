@@ -88,6 +88,7 @@ def lib():
         "frieda_ctx_test_set_grind_first_log": (C.c_int, [vp, u32]),
         "frieda_ctx_test_set_arena_limit": (C.c_int, [vp, u64]),
         "frieda_ctx_test_set_verify_pass_bytes": (C.c_int, [vp, u64]),
+        "frieda_ctx_test_poison": (C.c_int, [vp, u32, C.c_int, u64p]),
         "frieda_workspace_bytes": (sz, [sz, u32, u32, C.c_int]),
         "frieda_batch_plan": (C.c_int, [vp, sz, u32, u32, C.c_int, u32, u32, C.POINTER(u32), sz, C.POINTER(u32)]),
         "frieda_ctx_set_kernel_timing": (C.c_int, [vp, C.c_int]),

@@ -198,6 +198,38 @@ int frieda_ctx_test_set_arena_limit(frieda_ctx* ctx, uint64_t bytes) {
     return FRIEDA_OK;
 }
 
+int frieda_ctx_test_poison(frieda_ctx* ctx, uint32_t word, int sticky, uint64_t out_bytes[4]) {
+    if (!ctx) return FRIEDA_ERR_ARG;
+    FR_NO_JOB(&ctx->c);
+    FR_GUARD_BEGIN
+    Ctx& c = ctx->c;
+    FR_HIP(&c, hipSetDevice(c.device));
+    uint64_t filled[4] = {0, 0, 0, 0};  // arena, pinned, pinned_in, twiddle scratch
+    FR_HIP(&c, c.poison_device(c.arena, c.arena_bytes, word));
+    filled[0] = c.arena ? c.arena_bytes : 0;
+    for (auto& kv : c.twiddles) {
+        const TwiddleSet& ts = kv.second;
+        FR_HIP(&c, c.poison_device(ts.d_scratch, 8192, word));
+        filled[3] += ts.d_scratch ? 8192 : 0;
+        if (!c.cache_twiddles) {  // regenerated by every call: the tables are scratch too
+            const size_t tb = sizeof(uint32_t) << (kv.first - 1);
+            FR_HIP(&c, c.poison_device(ts.d_tw, tb, word));
+            FR_HIP(&c, c.poison_device(ts.d_itw, tb, word));
+            filled[3] += 2 * tb;
+        }
+    }
+    FR_HIP(&c, c.poison_pinned(c.pinned, c.pinned_bytes, word));
+    filled[1] = c.pinned ? c.pinned_bytes : 0;
+    FR_HIP(&c, c.poison_pinned(c.pinned_in, SMALL_HOST_IN_BYTES, word));
+    filled[2] = c.pinned_in ? SMALL_HOST_IN_BYTES : 0;
+    c.tuning.test_poison = sticky != 0;
+    c.tuning.test_poison_word = word;
+    if (out_bytes)
+        for (int i = 0; i < 4; i++) out_bytes[i] = filled[i];
+    return FRIEDA_OK;
+    FR_GUARD_END(ctx)
+}
+
 int frieda_ctx_test_set_verify_pass_bytes(frieda_ctx* ctx, uint64_t bytes) {
     if (!ctx) return FRIEDA_ERR_ARG;
     ctx->c.tuning.test_verify_pass_bytes = bytes;
@@ -544,6 +576,10 @@ int frieda_reconstruct_from_opened_cells(frieda_ctx* ctx, const uint8_t commitme
         ctx->c.err = std::string("hipMalloc: ") + hipGetErrorString(e);
         return FRIEDA_ERR_NOMEM;
     }
+    if (const hipError_t pe = ctx->c.poison_fresh(d_out, len ? len : 1); pe != hipSuccess) {
+        (void)hipFree(d_out);
+        return ctx->c.hip_fail(pe, "poison(rebuilt bytes)");
+    }
     std::vector<uint8_t> bytes(len);
     rc = reconstruct_cells_pooled(ctx, pool.d_val(), pool.d_idx(), (uint32_t)pool.n, log_cell, L, n, len, d_out, &nd);
     *n_cells_used = nd;
@@ -656,6 +692,10 @@ int frieda_reconstruct_blobs_from_opened_stripes(frieda_ctx* ctx, const uint8_t*
         (void)hipGetLastError();
         ctx->c.err = std::string("hipMalloc: ") + hipGetErrorString(e);
         return FRIEDA_ERR_NOMEM;
+    }
+    if (const hipError_t pe = ctx->c.poison_fresh(d_out, stride * n_blobs); pe != hipSuccess) {
+        (void)hipFree(d_out);
+        return ctx->c.hip_fail(pe, "poison(rebuilt bytes)");
     }
     std::vector<uint8_t> roots(32 * (size_t)n_blobs), bytes(len * n_blobs);
     rc = reconstruct_stripes_pooled(ctx, pool.d_val(), pool.d_idx(), (uint32_t)pool.n, n_blobs, log_cell, L, n, len, static_cast<uint8_t*>(d_out), stride, &nd);

@@ -103,6 +103,7 @@ int verify_cells_device(Ctx* ctx, const uint8_t commitment[32], uint32_t log_dom
             return FRIEDA_ERR_NOMEM;
         }
         pool->d = static_cast<uint8_t*>(d);
+        FR_HIP(ctx, ctx->poison_fresh(d, ((4 * pool->cap + 255) & ~(size_t)255) + vb * pool->cap));
     }
     const size_t pass_bytes = ctx->tuning.test_verify_pass_bytes ? (size_t)ctx->tuning.test_verify_pass_bytes : PASS_BYTES;
     const size_t per_pass = std::max<size_t>(1, pass_bytes / (4 + vb + pb));
@@ -227,6 +228,7 @@ int verify_cells_blobs_device(Ctx* ctx, const uint8_t* commitments, uint32_t n_b
             return FRIEDA_ERR_NOMEM;
         }
         stripes->d = static_cast<uint8_t*>(d);
+        FR_HIP(ctx, ctx->poison_fresh(d, ((4 * stripes->cap + 255) & ~(size_t)255) + vb * n_cells));
     }
     const size_t pass_bytes = ctx->tuning.test_verify_pass_bytes ? (size_t)ctx->tuning.test_verify_pass_bytes : PASS_BYTES;
     // (a stripe's cells never straddle two passes, and one stripe is always admitted)

@@ -288,7 +288,25 @@ int Ctx::ensure_arena(size_t bytes) {
         return FRIEDA_ERR_NOMEM;
     }
     arena_bytes = want;
+    FR_HIP(this, poison_fresh(arena, arena_bytes));
     return FRIEDA_OK;
+}
+
+hipError_t Ctx::poison_device(void* d, size_t bytes, uint32_t word) {
+    if (!d || !bytes) return hipSuccess;
+    hipError_t e = hipSuccess;
+    if (bytes / 4) e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d), (int)word, bytes / 4, stream);
+    if (e == hipSuccess && bytes % 4)  // an allocation of the caller's length: its last bytes take the word's low byte
+        e = hipMemsetAsync(static_cast<uint8_t*>(d) + (bytes & ~(size_t)3), (int)(word & 0xffu), bytes % 4, stream);
+    return e;
+}
+
+hipError_t Ctx::poison_pinned(void* p, size_t bytes, uint32_t word) {
+    if (!p || !bytes) return hipSuccess;
+    const hipError_t e = hipStreamSynchronize(stream);
+    if (e != hipSuccess) return e;
+    for (size_t i = 0; i < bytes; i++) static_cast<uint8_t*>(p)[i] = (uint8_t)(word >> (8 * (i & 3)));
+    return hipSuccess;
 }
 
 void Ctx::drop_twiddles() {
@@ -321,6 +339,10 @@ int Ctx::get_twiddles(uint32_t n, TwiddleSet& out) {
             return FRIEDA_ERR_NOMEM;
         }
         twiddles[n] = ts;  // owned by the cache from here on, whatever happens below
+        hipError_t pe = poison_fresh(ts.d_tw, bytes);
+        if (pe == hipSuccess) pe = poison_fresh(ts.d_itw, bytes);
+        if (pe == hipSuccess) pe = poison_fresh(ts.d_scratch, 8192);
+        if (pe != hipSuccess) return hip_fail(pe, "poison(twiddles)");
     }
     // seeds: initial point of half_odds(n-1) and the step multiples the kernel combines
     Coset h = Coset::half_odds(n - 1);

@@ -113,6 +113,13 @@ struct Ctx {
     int fail(int code, const std::string& what);
     int hip_fail(hipError_t e, const char* what);
     int ensure_arena(size_t bytes);
+    // test hook (frieda_ctx_test_poison): fill `bytes` of device memory with `word` on the ctx stream; a page-locked host block is
+    // filled by the host once the stream has drained (nothing of the context is in flight on it: FR_NO_JOB)
+    hipError_t poison_device(void* d, size_t bytes, uint32_t word);
+    hipError_t poison_pinned(void* p, size_t bytes, uint32_t word);
+    // the sticky mode's sites: a no-op unless tuning.test_poison; `d` is an allocation the context has just made for itself
+    hipError_t poison_fresh(void* d, size_t bytes) { return tuning.test_poison ? poison_device(d, bytes, tuning.test_poison_word) : hipSuccess; }
+    hipError_t poison_fresh_pinned(void* p, size_t bytes) { return tuning.test_poison ? poison_pinned(p, bytes, tuning.test_poison_word) : hipSuccess; }
     int get_twiddles(uint32_t n, TwiddleSet& out);
     void drop_twiddles();
     ~Ctx();
@@ -143,6 +150,8 @@ struct ArenaPlan {
     }
 };
 
+// the size of Ctx::pinned_in (prover.cpp)
+constexpr size_t SMALL_HOST_IN_BYTES = 7680;  // 15 << 9: up to 32 workgroups read the block over PCIe; larger small blobs are copied to the device first
 // the pinned staging block (Ctx::pinned) of at least `bytes` (reallocated when smaller; callers hold no job: FR_NO_JOB)
 int ensure_pinned(Ctx* ctx, size_t bytes);
 

@@ -71,6 +71,8 @@ struct Tuning {
                                          // four-columns-side-by-side fold2 kernel (ntt.hip), also against a later set_option
     uint64_t test_arena_limit = 0;       // test hook (frieda_ctx_test_set_arena_limit): ensure_arena refuses more than this many bytes (0 = off)
     uint64_t test_verify_pass_bytes = 0; // test hook (frieda_ctx_test_set_verify_pass_bytes): staging budget of one verify pass (0 = the default, 32 MB)
+    bool test_poison = false;            // test hook (frieda_ctx_test_poison, sticky): every allocation the context makes for itself is filled with
+    uint32_t test_poison_word = 0;       // this word on the ctx stream before its first use (host side only: no kernel reads either field)
 };
 // trees of a proof with at least 2^(this) leaves are built without the two levels above their leaves (tree.hip TreeArgs::skip_bc,
 // decommit.hip node_from_values, prover.cpp's host-planner fallback): ONE rule for the three places, by the blobs of the call

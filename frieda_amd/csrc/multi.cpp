@@ -439,6 +439,8 @@ static void device_worker(frieda_multi* m, uint32_t d, const uint8_t* const* blo
     pin_this_thread(m->near_cpus[d]);
     frieda_ctx* cx[2] = {m->ctx[2 * d], m->ctx[2 * d + 1]};
     cx[1]->c.tuning.test_arena_limit = cx[0]->c.tuning.test_arena_limit;  // (test hook set through frieda_multi_ctx: the slot's both contexts)
+    cx[1]->c.tuning.test_poison = cx[0]->c.tuning.test_poison;
+    cx[1]->c.tuning.test_poison_word = cx[0]->c.tuning.test_poison_word;
     const bool pf = m->prefetch;
     struct DrainUploads {  // no upload may still be reading the caller's blobs when the worker returns
         frieda_multi* m;

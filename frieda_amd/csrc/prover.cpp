@@ -39,6 +39,7 @@ int ensure_pinned(Ctx* ctx, size_t bytes) {
     ctx->pinned_bytes = 0;
     FR_HIP(ctx, hipHostMalloc(&ctx->pinned, bytes, hipHostMallocDefault));
     ctx->pinned_bytes = bytes;
+    FR_HIP(ctx, ctx->poison_fresh_pinned(ctx->pinned, bytes));
     return FRIEDA_OK;
 }
 
@@ -46,10 +47,10 @@ namespace {
 
 // Small host blobs (the fused small-domain kernel, tree.hip) are not copied to the device at all: they are placed in a page-locked
 // block that the kernel reads directly (one PCIe read per workgroup instead of a copy command in front of the first launch).
-constexpr size_t SMALL_HOST_IN_BYTES = 7680;  // 15 << 9: up to 32 workgroups read the block over PCIe; larger small blobs are copied to the device first
 int ensure_pinned_in(Ctx* ctx) {
     if (ctx->pinned_in) return FRIEDA_OK;
     FR_HIP(ctx, hipHostMalloc(&ctx->pinned_in, SMALL_HOST_IN_BYTES, hipHostMallocDefault));
+    FR_HIP(ctx, ctx->poison_fresh_pinned(ctx->pinned_in, SMALL_HOST_IN_BYTES));
     return FRIEDA_OK;
 }
 
@@ -973,6 +974,7 @@ int prove_finish_batch(Ctx* ctx, uint8_t* out_commitments, std::vector<ProofData
                 (void)hipGetLastError();
                 return ctx->fail(FRIEDA_ERR_NOMEM, "no device memory for the complete first-layer tree of the host decommitment");
             }
+            FR_HIP(ctx, ctx->poison_fresh(first_full.d, k::merkle_layer_offset(n, 0) + 32));
             const uint32_t* c0 = J.enc->eval();
             k::merkle_tree4(ctx->launch(), c0, c0 + N, c0 + 2 * N, c0 + 3 * N, n, first_full.d);
             first_tree_alt = first_full.d;
@@ -1163,6 +1165,7 @@ int encode_blob(Ctx* ctx, const uint8_t* data, size_t len, bool data_on_device, 
         e->d = nullptr;
         return ctx->fail(FRIEDA_ERR_NOMEM, "hipMalloc(encoded blob " + std::to_string(e->bytes) + " B) failed");
     }
+    FR_HIP(ctx, ctx->poison_fresh(e->d, e->bytes));
     hipStream_t s = ctx->stream;
     uint8_t* A = ctx->arena;
     const uint8_t* d_data = data;

@@ -131,6 +131,7 @@ int pool_alloc(Ctx* ctx, PairPool& pool) {
         return FRIEDA_ERR_NOMEM;
     }
     pool.d = static_cast<uint8_t*>(d);
+    FR_HIP(ctx, ctx->poison_fresh(d, ((4 * pool.cap + 255) & ~(size_t)255) + 16 * pool.cap));
     return FRIEDA_OK;
 }
 
@@ -382,6 +383,13 @@ int frieda_reconstruct_from_proofs(frieda_ctx* ctx, const frieda_proof* const* p
         ctx->c.err = std::string("hipMalloc: ") + hipGetErrorString(e);
         return FRIEDA_ERR_NOMEM;
     }
+    e = ctx->c.poison_fresh(d_cells, 4 * cells.size());
+    if (e == hipSuccess) e = ctx->c.poison_fresh(d_out, len ? len : 1);
+    if (e != hipSuccess) {
+        (void)hipFree(d_cells);
+        (void)hipFree(d_out);
+        return ctx->c.hip_fail(e, "poison(rebuilt bytes)");
+    }
     std::vector<uint8_t> bytes(len);
     rc = frieda_dev_upload(ctx, d_cells, cells.data(), 4 * cells.size());
     if (rc == FRIEDA_OK)
@@ -476,6 +484,10 @@ int frieda_reconstruct_from_proof_pairs(frieda_ctx* ctx, const frieda_proof* con
     if (e != hipSuccess) {
         ctx->c.err = std::string("hipMalloc: ") + hipGetErrorString(e);
         return FRIEDA_ERR_NOMEM;
+    }
+    if (const hipError_t pe = ctx->c.poison_fresh(d_out, len ? len : 1); pe != hipSuccess) {
+        (void)hipFree(d_out);
+        return ctx->c.hip_fail(pe, "poison(rebuilt bytes)");
     }
     std::vector<uint8_t> bytes(len);
     rc = reconstruct_points_pooled(ctx, pool.d_val(), pool.d_pos(), (uint32_t)pool.n, L, L + B, len, d_out, &nd);
