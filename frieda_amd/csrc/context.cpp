@@ -130,6 +130,7 @@ const KnobDesc KNOBS[] = {
     {"FRIEDA_NTT_REP", 0, 2, [](Tuning& t, long v) { t.ntt_rep = (uint32_t)v; return true; }},
     {"FRIEDA_NTT_NO_CP", 0, 1, [](Tuning& t, long v) { t.ntt_no_cp = v != 0; return true; }},
     {"FRIEDA_NTT_NO_PAD8", 0, 1, [](Tuning& t, long v) { t.ntt_no_pad8 = v != 0; return true; }},
+    {"FRIEDA_NTT_PACKED_SRC", 0, 1, [](Tuning& t, long v) { t.ntt_packed_src = v != 0; return true; }},
     {"FRIEDA_NTT_TREE_REG_ONLY", 0, 1, [](Tuning& t, long v) { t.ntt_tree_reg_only = v != 0; return true; }},
     {"FRIEDA_NO_ENCODE_TREE_FUSION", 0, 1, [](Tuning& t, long v) { t.no_encode_tree_fusion = v != 0; return true; }},
     {"FRIEDA_ENCODE_TREE_FUSION_PROVE", 0, 1, [](Tuning& t, long v) { t.encode_tree_fusion_prove = v != 0; return true; }},

@@ -37,6 +37,7 @@ struct Tuning {
     uint32_t ntt_cpw_small = 1;  // FRIEDA_NTT_CPW_SMALL: columns per workgroup of fast-kernel launches below 512 tiles
     uint32_t ntt_rep = 2;        // FRIEDA_NTT_REP: the first strided pass as ntt_tile12_rep_kernel: 0 never, 1 wherever the shape allows, 2 from 1024 workgroups on
     bool ntt_no_pad8 = false;    // FRIEDA_NTT_NO_PAD8: no padded / 4-layer fast passes
+    bool ntt_packed_src = true;  // FRIEDA_NTT_PACKED_SRC: ntt_tile12_rep_kernel unpacks the blob itself (no unpack30 launch before it); 0 = A/B
     bool ntt_no_cp = false;      // FRIEDA_NTT_NO_CP: small fold2 launches as one 256-thread workgroup per tile (not four columns side by side)
     bool ntt_tree_reg_only = false;      // FRIEDA_NTT_TREE_REG_ONLY: the fused encode + leaf launch stops after its five register levels
     bool no_encode_tree_fusion = false;  // FRIEDA_NO_ENCODE_TREE_FUSION: last transform pass and leaf launch as two kernels (commitments too)
@@ -169,8 +170,19 @@ struct EncodeFoldSink {
 };
 bool circle_evaluate_fold2(const Launch& L_, const uint32_t* d_coef, size_t coef_stride, uint32_t L, uint32_t n, const uint32_t* d_tw,
                            DomainScalars ds, uint32_t* d_out, size_t out_stride, const EncodeFoldSink& fs, hipError_t* err);
+// `blob` non-null: d_coef is not filled yet — it is the unpacked form of this blob (codec.hip; column c = felts [c * coef_stride,
+// (c + 1) * coef_stride)).  When the plan's first pass is ntt_tile12_rep_kernel and the blob's pointer and batch stride are dword
+// aligned, that pass reads the packed bytes itself and d_coef stays untouched; every other shape, alignment or FRIEDA_NTT_PACKED_SRC = 0
+// runs unpack30 into d_coef first, as a caller without `blob` does itself.
+struct BlobSource {
+    const uint8_t* bytes;  // blob 0 of the batch; blob b at bytes + b * bstride
+    size_t len;
+    size_t bstride;
+    size_t n_padded;  // felts of d_coef (unpack30's n_out)
+};
 uint32_t circle_evaluate_into_tree(const Launch& L_, const uint32_t* d_coef, size_t coef_stride, uint32_t ncols, uint32_t L, uint32_t n,
-                               const uint32_t* d_tw, DomainScalars ds, uint32_t* d_out, size_t out_stride, const EncodeTreeSink* sink);
+                               const uint32_t* d_tw, DomainScalars ds, uint32_t* d_out, size_t out_stride, const EncodeTreeSink* sink,
+                               const BlobSource* blob = nullptr);
 
 // ---- intt.hip (reconstruction side) ----
 // block `block` (2^L consecutive bit-reversed evaluations per column) -> the 2^L coefficients per column
@@ -297,7 +309,7 @@ void small_encode_and_first_tree(const Launch& L, const uint8_t* d_data, size_t 
                                  uint8_t* d_scratch, uint8_t* d_root, DevTranscript* tr, const DevTranscript* tr_init, size_t tr_init_pitch);
 void encode_and_first_tree(const Launch& L, const uint32_t* d_coef, size_t coef_stride, uint32_t Lc, uint32_t n, const uint32_t* d_tw,
                            DomainScalars ds, uint32_t* d_eval, size_t eval_stride, uint8_t* d_layers, uint8_t* d_scratch, uint8_t* d_root,
-                           DevTranscript* tr, const DevTranscript* tr_init = nullptr, size_t tr_init_pitch = 0);
+                           DevTranscript* tr, const DevTranscript* tr_init = nullptr, size_t tr_init_pitch = 0, const BlobSource* blob = nullptr);
 // fold the layer `src` (log size src_log; circle evaluation or line layer) with the alpha in tr into dst_vals and build the
 // tree of the folded layer in the same launches (leaf hashes not written, as above); finishes with the channel step
 // shared_src (prove_seeds: the blobs of the launch are the seeds of ONE encoded blob): `src` is the same for every blob (stride 0) while

@@ -240,6 +240,11 @@ struct NttArgs {
     uint32_t n_stages;    // <= 3
     uint32_t stage_r[3];  // layers per stage, top stage first
     size_t bstride_w;     // batch: words between consecutive blobs' buffers (both in and out); blob = blockIdx.z
+    // the packed source form (ntt_tile12_rep_kernel<COLS, true>): the first pass reads the blob itself instead of `in`
+    const uint8_t* pk;    // dword-aligned blob of blob 0; blob z at pk + z * pk_bstride
+    size_t pk_len;        // its bytes; everything at or beyond reads as zero
+    size_t pk_bstride;    // a multiple of 4
+    size_t pk_col_felts;  // column c starts at felt c * pk_col_felts
     uint32_t rep_log;     // ntt_tile12_rep_kernel: a workgroup produces the tiles of 2^rep_log consecutive high blocks from one read of its source tile
 };
 
@@ -500,9 +505,45 @@ __global__ __launch_bounds__(NTT_THREADS) void ntt_tile12_kernel(NttArgs a) {
 // twiddles only.  With one workgroup per high block every coefficient was fetched once per block (208 MB from the memory side for
 // 16.8 MB of coefficients at n = 24, profiles/r02_prove24_traffic.json).  Here a workgroup reads its source tile of COLS columns
 // once into registers (16 words per thread and column) and loops over 2^rep_log high blocks: twiddles of the block, then per
-// column registers -> LDS -> two radix-16 stages -> store.  Twiddles are still shared by the workgroup's columns.
+// column two radix-16 stages -> store.  Twiddles are still shared by the workgroup's columns.
+//
+// The source registers are held in STAGE 0's OWN LAYOUT: word r of a thread is tile element stage_group_base(g, 8) | r << 8, i.e. the
+// x[r] its first radix-16 stage works on.  Stage 0 of every high block and column therefore starts from a register copy: no LDS fill,
+// no read-back and no barrier in front of it — per column three workgroup barriers instead of four and 64 + 16 LDS instructions per
+// thread instead of 96 + 16.  In that layout sixteen consecutive lanes hold sixteen consecutive coefficients, a 64-byte run of the
+// coefficient buffer — or (PACKED) a 60-byte run of the packed blob itself: the kernel then unpacks its words (two dwords, a funnel
+// shift, a mask) once per workgroup and the encode needs no unpack30 launch and no coefficient buffer round trip.  Measured in
+// profiles/r13_encode_stage0.txt; the same first-stage-from-registers change in ntt_tile12_kernel, whose source changes with every
+// column and has to be prefetched, was measured there too and did not pay.
 // ------------------------------------------------------------------------------------------------
-template <int COLS>
+// Felt f of a packed blob: bits [30 f, 30 f + 30) of the LSB-first byte stream (bytes_to_felt_le), zero-extended beyond `len`
+// (polynomial_from_bytes).  `p` is dword aligned.  Only the blob's FULL dwords are ever loaded (a dword index at or beyond them is
+// clamped to dword 0 and its value dropped), so the loads carry no branch and all of a thread's words are in flight together; the
+// ragged last dword (len % 4 bytes) is one value per blob, assembled from its bytes by packed_blob, and everything behind it is zero.
+struct PackedBlob {
+    const uint8_t* p;
+    uint32_t full;  // dwords that lie wholly inside the blob
+    uint32_t tail;  // dword `full`: the blob's last len % 4 bytes, zero-extended
+};
+__device__ __forceinline__ PackedBlob packed_blob(const uint8_t* __restrict__ p, size_t len) {
+    PackedBlob b{p, (uint32_t)(len >> 2), 0u};
+    for (size_t i = 4 * (size_t)b.full; i < len; i++) b.tail |= (uint32_t)p[i] << (8 * (i & 3));
+    return b;
+}
+// (32-bit arithmetic: the plan takes this form for at most 2^28 felts, so 15 f and every byte offset stay below 2^32 and a load is the
+// blob's uniform base plus one offset register)
+__device__ __forceinline__ uint32_t packed_dword(const PackedBlob& b, uint32_t d) {
+    const bool in = d < b.full;
+    const uint32_t v = *reinterpret_cast<const uint32_t*>(b.p + ((in ? d : 0u) << 2));  // (only called with full >= 1)
+    return in ? v : (d == b.full ? b.tail : 0u);
+}
+__device__ __forceinline__ uint32_t packed_felt(const PackedBlob& b, uint32_t f) {
+    const uint32_t d = (15u * f) >> 4, sh = (30u * f) & 31u;  // bit 30 f = dword d, shift sh
+    const uint64_t pair = ((uint64_t)packed_dword(b, d + 1) << 32) | packed_dword(b, d);
+    return (uint32_t)(pair >> sh) & 0x3fffffffu;
+}
+
+template <int COLS, bool PACKED>
 __global__ __launch_bounds__(NTT_THREADS) void ntt_tile12_rep_kernel(NttArgs a) {
     ntt_enter();
     constexpr int NS = 2;
@@ -514,20 +555,36 @@ __global__ __launch_bounds__(NTT_THREADS) void ntt_tile12_rep_kernel(NttArgs a) 
     const uint32_t hblk0 = (blockIdx.x >> nwb_log) << a.rep_log;
     constexpr uint32_t wmask = (1u << LOG_W) - 1;
     const size_t col0 = (size_t)blockIdx.y * COLS;
-    const uint32_t* in = a.in + col0 * a.in_stride + blockIdx.z * a.bstride_w;
     uint32_t* out = a.out + col0 * a.out_stride + blockIdx.z * a.bstride_w;
 
     auto piece_e = [&](int kk) { return 4u * g + 1024u * (uint32_t)kk; };
     // tile element e -> index below the high block (the source index is this, masked: independent of the high block)
     auto low_of = [&](uint32_t e) { return (wblk << LOG_W) | ((e >> LOG_W) << a.i_lo) | (e & wmask); };
 
-    uint4 src[COLS][4];
+    // The source tiles, in stage 0's layout: src[c][r] = tile element stage_group_base(g, 8) | r << 8 of column c.  Indices at or beyond
+    // in_limit are the zero padding of the coefficient vector.
+    const uint32_t e0 = stage_group_base(g, 8);
+    uint32_t src[COLS][16];
+    if constexpr (PACKED) {
+        const PackedBlob blob = packed_blob(a.pk + blockIdx.z * a.pk_bstride, a.pk_len);
 #pragma unroll
-    for (int c = 0; c < COLS; c++) {
+        for (int c = 0; c < COLS; c++) {
 #pragma unroll
-        for (int kk = 0; kk < 4; kk++) {
-            const uint32_t idx = low_of(piece_e(kk)) & a.in_mask;
-            src[c][kk] = idx < a.in_limit ? *reinterpret_cast<const uint4*>(in + (size_t)c * a.in_stride + idx) : make_uint4(0u, 0u, 0u, 0u);
+            for (int r = 0; r < 16; r++) {
+                const uint32_t idx = low_of(e0 | ((uint32_t)r << 8)) & a.in_mask;
+                const bool ok = idx < a.in_limit;  // (else: the zero padding of the coefficient vector; felt 0 is loaded and dropped)
+                const uint32_t v = packed_felt(blob, ok ? (uint32_t)((col0 + c) * a.pk_col_felts) + idx : 0u);
+                src[c][r] = ok ? v : 0u;
+            }
+        }
+    } else {
+#pragma unroll
+        for (int c = 0; c < COLS; c++) {
+#pragma unroll
+            for (int r = 0; r < 16; r++) {
+                const uint32_t idx = low_of(e0 | ((uint32_t)r << 8)) & a.in_mask;
+                src[c][r] = idx < a.in_limit ? (a.in + col0 * a.in_stride + blockIdx.z * a.bstride_w)[(size_t)c * a.in_stride + idx] : 0u;
+            }
         }
     }
     uint32_t pbase[NS];
@@ -562,22 +619,18 @@ __global__ __launch_bounds__(NTT_THREADS) void ntt_tile12_rep_kernel(NttArgs a) 
         }
 #pragma unroll
         for (int c = 0; c < COLS; c++) {
-#pragma unroll
-            for (int kk = 0; kk < 4; kk++) {
-                const uint32_t p = pad(piece_e(kk));
-                lds[p] = src[c][kk].x;
-                lds[p + 1] = src[c][kk].y;
-                lds[p + 2] = src[c][kk].z;
-                lds[p + 3] = src[c][kk].w;
-            }
-            __syncthreads();
+            // one tile: three barriers per column (after each stage's write, and behind the store's reads)
             uint32_t x[16];
+#pragma unroll
+            for (int r = 0; r < 16; r++) x[r] = src[c][r];
 #pragma unroll
             for (int s = 0; s < NS; s++) {
                 const uint32_t lo = 8 - 4 * s;
                 uint32_t* col = lds + pbase[s];
+                if (s > 0) {
 #pragma unroll
-                for (int r = 0; r < 16; r++) x[r] = col[pad((uint32_t)r << lo)];
+                    for (int r = 0; r < 16; r++) x[r] = col[pad((uint32_t)r << lo)];
+                }
                 radix16_stage(x, twd[s]);
 #pragma unroll
                 for (int r = 0; r < 16; r++) col[pad((uint32_t)r << lo)] = x[r];
@@ -589,7 +642,7 @@ __global__ __launch_bounds__(NTT_THREADS) void ntt_tile12_rep_kernel(NttArgs a) 
                 const uint32_t e = piece_e(kk), p = pad(e);
                 *reinterpret_cast<uint4*>(dst + low_of(e)) = make_uint4(lds[p], lds[p + 1], lds[p + 2], lds[p + 3]);
             }
-            __syncthreads();  // the next tile overwrites the LDS buffer
+            __syncthreads();  // the next tile's stage 0 overwrites the LDS buffer
         }
     }
 }
@@ -1029,7 +1082,7 @@ FR_CLOCK_READER(frieda_debug_clock_ntt_last_tree, g_clock_ntt_last_tree)
 namespace {
 uint32_t evaluate_plan(const Launch& L_, const uint32_t* d_coef, size_t coef_stride, uint32_t ncols, uint32_t L, uint32_t n, uint32_t out_log,
                        const uint32_t* d_tw, DomainScalars ds, uint32_t* d_out, size_t out_stride, const EncodeTreeSink* sink,
-                       const EncodeFoldSink* fsink = nullptr);
+                       const EncodeFoldSink* fsink = nullptr, const BlobSource* blob = nullptr);
 }
 
 void circle_evaluate(const Launch& L_, const uint32_t* d_coef, size_t coef_stride, uint32_t ncols, uint32_t L, uint32_t n,
@@ -1043,8 +1096,9 @@ void circle_evaluate_prefix(const Launch& L_, const uint32_t* d_coef, size_t coe
 }
 
 uint32_t circle_evaluate_into_tree(const Launch& L_, const uint32_t* d_coef, size_t coef_stride, uint32_t ncols, uint32_t L, uint32_t n,
-                               const uint32_t* d_tw, DomainScalars ds, uint32_t* d_out, size_t out_stride, const EncodeTreeSink* sink) {
-    return evaluate_plan(L_, d_coef, coef_stride, ncols, L, n, n, d_tw, ds, d_out, out_stride, sink);
+                               const uint32_t* d_tw, DomainScalars ds, uint32_t* d_out, size_t out_stride, const EncodeTreeSink* sink,
+                               const BlobSource* blob) {
+    return evaluate_plan(L_, d_coef, coef_stride, ncols, L, n, n, d_tw, ds, d_out, out_stride, sink, nullptr, blob);
 }
 
 hipError_t ntt_opt_in_dynamic_lds() {
@@ -1081,13 +1135,21 @@ namespace {
 // `fsink`: the last pass also folds (ntt_last_fold_kernel) when the shape allows; the return value is then 1, else 0.
 uint32_t evaluate_plan(const Launch& L_, const uint32_t* d_coef, size_t coef_stride, uint32_t ncols, uint32_t L, uint32_t n, uint32_t out_log,
                        const uint32_t* d_tw, DomainScalars ds, uint32_t* d_out, size_t out_stride, const EncodeTreeSink* sink,
-                       const EncodeFoldSink* fsink) {
+                       const EncodeFoldSink* fsink, const BlobSource* blob) {
     const size_t N = (size_t)1 << out_log;
     hipStream_t s = L_.stream;
+    // `blob`: the coefficients are still packed (kernels.h BlobSource).  The first pass decides: ntt_tile12_rep_kernel reads the blob,
+    // anything else gets the unpack30 launch it always had.
+    bool blob_pending = blob != nullptr;
+    auto unpack_now = [&]() {
+        unpack30(L_, blob->bytes, blob->len, const_cast<uint32_t*>(d_coef), blob->n_padded, blob->bstride);
+        blob_pending = false;
+    };
     // algorithmic bytes of the encode: read 2^L, write 2^n words per column (16N(1 + 2^-B) for 4 columns),
     // split evenly over the passes
     const double enc_bytes = 4.0 * ncols * ((double)N + (double)((size_t)1 << L));
     if (L == 0) {
+        if (blob_pending) unpack_now();
         Scope scope(L_, "ntt_broadcast", enc_bytes);
         dim3 grid((unsigned)((N + 255) / 256), ncols, L_.batch);
         ntt_broadcast_kernel<<<grid, 256, 0, s>>>(d_coef, coef_stride, d_out, out_stride, N, L_.bstride / 4);
@@ -1130,6 +1192,28 @@ uint32_t evaluate_plan(const Launch& L_, const uint32_t* d_coef, size_t coef_str
     auto launch_pass = [&](uint32_t t, const char* name) {
         const bool aligned = ((a.in_stride | a.out_stride) & 3) == 0 && (a.in_mask & 3u) == 3u &&
                              ((reinterpret_cast<uintptr_t>(a.in) | reinterpret_cast<uintptr_t>(a.out) | L_.bstride) & 15) == 0;
+        // ntt_tile12_rep_kernel: one workgroup per source tile looping over the high blocks.  It cuts the pass's fetches from the memory
+        // side to the unique coefficients; the pass is bound by its butterflies and LDS round trips, so that bought nothing in round 3
+        // (142 vs 140 us at 2^24, profiles/r03_ntt_mid_rep_ab.txt) and costs a launch that no longer fills the chip its width
+        // (a lone 2^22 blob: 256 workgroups, 33 vs 26 us).  With the round-5 kernels it is ahead where it still fills the chip:
+        // 102 vs 106 us at 2^24 and the pass AFTER it 144 vs 150 (profiles/r05_prio_product_ab.txt, last block); streams of 2^22 / 2^20
+        // blobs equal.  FRIEDA_NTT_REP: 0 = never, 1 = wherever the shape allows, 2 (default) = from 1024 workgroups on.
+        const uint32_t hb_log = n - 1 - a.i_hi;  // high blocks = 2^hb_log
+        const uint64_t rep_wgs = (uint64_t)((N >> TILE_LOG) >> (hb_log < 3 ? hb_log : 3)) * (ncols / 2) * L_.batch;
+        const bool use_rep = L_.tune->ntt_rep == 1 || (L_.tune->ntt_rep == 2 && rep_wgs >= 1024);
+        // this pass reads the (replicated) coefficient vector: every high block has the same source tile
+        const bool rep = use_rep && out_log == n && aligned && t == 8 && a.log_w == MID_LOG_W && hb_log >= 1 && ((uint64_t)a.in_mask >> (a.i_hi + 1)) == 0 && ncols % 2 == 0;
+        bool packed = false;
+        if (blob_pending) {  // (the first pass of the plan: a.in is still the coefficient buffer)
+            // the packed form: dword-aligned blobs of at least one dword, sizes its 32-bit index arithmetic holds (packed_felt)
+            packed = rep && L_.tune->ntt_packed_src && blob->len >= 4 && blob->len <= ((size_t)1 << 30) &&
+                     (uint64_t)ncols * coef_stride <= ((uint64_t)1 << 28) && (reinterpret_cast<uintptr_t>(blob->bytes) & 3) == 0 &&
+                     (L_.batch == 1 || (blob->bstride & 3) == 0);
+            if (packed)
+                blob_pending = false;
+            else
+                unpack_now();
+        }
         if (sink && aligned && a.log_w == 0 && t == 12 && ncols == 4 && n >= TILE_LOG && out_log == n) {
             // the contiguous last pass of 12 layers over the 4 coordinate columns: fused with leaf hashing + 6 tree levels
             NttTreeArgs ta{};
@@ -1195,21 +1279,19 @@ uint32_t evaluate_plan(const Launch& L_, const uint32_t* d_coef, size_t coef_str
             return;
         }
         Scope scope(L_, name, enc_bytes / ((n_mid_fast ? n_mid_fast : n_mid_generic) + 1));
-        // ntt_tile12_rep_kernel: one workgroup per source tile looping over the high blocks.  It cuts the pass's fetches from the memory
-        // side to the unique coefficients; the pass is bound by its butterflies and LDS round trips, so that bought nothing in round 3
-        // (142 vs 140 us at 2^24, profiles/r03_ntt_mid_rep_ab.txt) and costs a launch that no longer fills the chip its width
-        // (a lone 2^22 blob: 256 workgroups, 33 vs 26 us).  With the round-5 kernels it is ahead where it still fills the chip:
-        // 102 vs 106 us at 2^24 and the pass AFTER it 144 vs 150 (profiles/r05_prio_product_ab.txt, last block); streams of 2^22 / 2^20
-        // blobs equal.  FRIEDA_NTT_REP: 0 = never, 1 = wherever the shape allows, 2 (default) = from 1024 workgroups on.
-        const uint32_t hb_log = n - 1 - a.i_hi;  // high blocks = 2^hb_log
-        const uint64_t rep_wgs = (uint64_t)((N >> TILE_LOG) >> (hb_log < 3 ? hb_log : 3)) * (ncols / 2) * L_.batch;
-        const bool use_rep = L_.tune->ntt_rep == 1 || (L_.tune->ntt_rep == 2 && rep_wgs >= 1024);
-        if (use_rep && out_log == n && aligned && t == 8 && a.log_w == MID_LOG_W && hb_log >= 1 && ((uint64_t)a.in_mask >> (a.i_hi + 1)) == 0 && ncols % 2 == 0) {
-            // this pass reads the (replicated) coefficient vector: every high block has the same source tile
+        if (rep) {
             a.rep_log = hb_log < 3 ? hb_log : 3;
             a.ncols = 2;
             dim3 grid((unsigned)((N >> TILE_LOG) >> a.rep_log), ncols / 2, L_.batch);
-            ntt_tile12_rep_kernel<2><<<grid, NTT_THREADS, 0, s>>>(a);
+            if (packed) {
+                a.pk = blob->bytes;
+                a.pk_len = blob->len;
+                a.pk_bstride = L_.batch > 1 ? blob->bstride : 0;
+                a.pk_col_felts = coef_stride;
+                ntt_tile12_rep_kernel<2, true><<<grid, NTT_THREADS, 0, s>>>(a);
+            } else {
+                ntt_tile12_rep_kernel<2, false><<<grid, NTT_THREADS, 0, s>>>(a);
+            }
             a.rep_log = 0;
         } else if (aligned && t + a.log_w == TILE_LOG && (t == 12 || t == 8 || t == 4)) {
             a.ncols = cpw4;

@@ -145,9 +145,10 @@ int commit_device(Ctx* ctx, const uint8_t* d_data, size_t len, uint32_t log_blow
         k::small_encode_and_first_tree(ctx->launch(), d_data, len, 0, sh.L, sh.n, tw.d_tw, tw.ds, nullptr, 0, nullptr, ctx->arena + o_scr, d_root,
                                        nullptr, nullptr, 0);
     } else {
-        k::unpack30(ctx->launch(), d_data, len, coef, sh.cs.n_padded);
+        // (the encode unpacks: in its first pass where that pass takes the blob, else by the unpack30 launch — kernels.h BlobSource)
+        const k::BlobSource blob{d_data, len, 0, sh.cs.n_padded};
         k::encode_and_first_tree(ctx->launch(), coef, (size_t)1 << sh.L, sh.L, sh.n, tw.d_tw, tw.ds, eval, sh.N, nullptr, ctx->arena + o_scr, d_root,
-                                 nullptr);
+                                 nullptr, nullptr, 0, &blob);
     }
     FR_HIP(ctx, hipGetLastError());
     return FRIEDA_OK;
@@ -254,8 +255,8 @@ int commit_batch_begin(Ctx* ctx, const uint8_t* data, size_t data_stride, size_t
         k::small_encode_and_first_tree(LN, d_data, len, d_stride, sh.L, sh.n, tw.d_tw, tw.ds, nullptr, 0, nullptr, A + o_scr, A + o_root, nullptr,
                                        nullptr, 0);
     } else {
-        k::unpack30(LN, d_data, len, coef, sh.cs.n_padded, d_stride);
-        k::encode_and_first_tree(LN, coef, (size_t)1 << sh.L, sh.L, sh.n, tw.d_tw, tw.ds, eval, sh.N, nullptr, A + o_scr, A + o_root, nullptr);
+        const k::BlobSource blob{d_data, len, d_stride, sh.cs.n_padded};
+        k::encode_and_first_tree(LN, coef, (size_t)1 << sh.L, sh.L, sh.n, tw.d_tw, tw.ds, eval, sh.N, nullptr, A + o_scr, A + o_root, nullptr, nullptr, 0, &blob);
     }
     FR_HIP(ctx, hipMemcpy2DAsync(ctx->pinned, 32, A + o_root, bstride, 32, count, hipMemcpyDeviceToHost, s));
     FR_HIP(ctx, hipGetLastError());
@@ -684,7 +685,9 @@ static int prove_begin_impl(Ctx* ctx, const uint8_t* data, size_t data_stride, s
     uint32_t* coef = reinterpret_cast<uint32_t*>(A + o_coef);
     // the first layer's columns: in the workspace, or (prove_seeds) the encoded blob's, only ever read
     uint32_t* eval = enc ? const_cast<uint32_t*>(enc->eval()) : reinterpret_cast<uint32_t*>(A + first.o_vals);
-    if (!small && !enc) k::unpack30(LN, d_data, len, coef, sh.cs.n_padded, d_data_stride);
+    // the device-channel path hands the blob to the encode (kernels.h BlobSource); the host-channel path's plain transform wants coefficients
+    const k::BlobSource blob{d_data, len, d_data_stride, sh.cs.n_padded};
+    if (!small && !enc && !dev_channel) k::unpack30(LN, d_data, len, coef, sh.cs.n_padded, d_data_stride);
     ctx->phase_ms[5] = ms_since(t_entry);  // set-up before the first launch (workspace plan, twiddle lookup, ...) + that launch call
 
     for (uint32_t b = 0; b < count; b++) {
@@ -722,7 +725,7 @@ static int prove_begin_impl(Ctx* ctx, const uint8_t* data, size_t data_stride, s
                                            reinterpret_cast<const DevTranscript*>(ctx->pinned), tr_host_pitch);
         else
             k::encode_and_first_tree(LN, coef, (size_t)1 << sh.L, sh.L, n, tw.d_tw, tw.ds, eval, N, A + first.o_tree, nullptr, nullptr, d_tr,
-                                     reinterpret_cast<const DevTranscript*>(ctx->pinned), tr_host_pitch);
+                                     reinterpret_cast<const DevTranscript*>(ctx->pinned), tr_host_pitch, &blob);
         // FriProver::commit_inner_layers: layers above 2^11 points, one fused fold + tree each
         const FriLayerDev* cur = &first;
         bool circle = true;
@@ -1180,8 +1183,8 @@ int encode_blob(Ctx* ctx, const uint8_t* data, size_t len, bool data_on_device, 
                                        nullptr, 0);
     } else {
         uint32_t* coef = reinterpret_cast<uint32_t*>(A + o_coef);
-        k::unpack30(LN, d_data, len, coef, sh.cs.n_padded);
-        k::encode_and_first_tree(LN, coef, (size_t)1 << sh.L, sh.L, sh.n, tw.d_tw, tw.ds, eval, sh.N, e->d + e->o_tree, nullptr, e->d + e->o_root, nullptr);
+        const k::BlobSource blob{d_data, len, 0, sh.cs.n_padded};
+        k::encode_and_first_tree(LN, coef, (size_t)1 << sh.L, sh.L, sh.n, tw.d_tw, tw.ds, eval, sh.N, e->d + e->o_tree, nullptr, e->d + e->o_root, nullptr, nullptr, 0, &blob);
     }
     FR_HIP(ctx, hipMemcpyAsync(ctx->pinned, e->d + e->o_root, 32, hipMemcpyDeviceToHost, s));
     FR_HIP(ctx, hipStreamSynchronize(s));
