@@ -1,6 +1,7 @@
 // capi.cpp — the extern "C" shell of libfrieda_hip.so (declarations and reference citations: include/frieda_hip.h).
 // No exception leaves this file: every entry point catches and maps to a status code (FR_GUARD_*, host.h).  The reconstruction entry
-// points (frieda_circle_interpolate_cells / _cells_any / _points, frieda_reconstruct_cells_device / _points_device) live in reconstruct.cpp.
+// points (frieda_circle_interpolate_cells / _cells_any / _points, frieda_reconstruct_cells_device / _points_device) live in reconstruct.cpp,
+// the many-proof verifiers in verify_many.cpp, the authenticated cells in cells_host.cpp.
 #include <string.h>
 
 #include <algorithm>
@@ -508,211 +509,6 @@ int frieda_encoded_shape(const frieda_encoded* enc, uint32_t* log_size_bound, ui
     *log_size_bound = enc->e.L;
     *log_domain = enc->e.n;
     return FRIEDA_OK;
-}
-
-// ---- authenticated cells (cells_host.cpp) ----
-int frieda_open_cells(frieda_ctx* ctx, const frieda_encoded* enc, uint32_t log_cell, const uint32_t* cell_index, uint32_t n_cells,
-                      uint32_t* out_values, uint8_t* out_paths) {
-    if (!ctx || !enc) return FRIEDA_ERR_ARG;
-    if (n_cells == 0) return FRIEDA_OK;
-    if (!cell_index || !out_values || (!out_paths && log_cell != enc->e.n)) return FRIEDA_ERR_ARG;
-    if (const char* bad = cells_args_error(enc->e.n, log_cell, cell_index, n_cells)) return ctx->c.fail(FRIEDA_ERR_ARG, std::string("open_cells: ") + bad);
-    FR_GUARD_BEGIN
-    return open_cells(&ctx->c, enc->e, log_cell, cell_index, n_cells, out_values, out_paths);
-    FR_GUARD_END(ctx)
-}
-
-int frieda_verify_cells(const uint8_t commitment[32], uint32_t log_domain, uint32_t log_cell, const uint32_t* cell_index, uint32_t n_cells,
-                        const uint32_t* values, const uint8_t* paths, uint8_t* out_status) {
-    if (n_cells == 0) return FRIEDA_OK;
-    if (!commitment || !cell_index || !values || !out_status) return FRIEDA_ERR_ARG;
-    if (cells_args_error(log_domain, log_cell, cell_index, n_cells) || (!paths && log_cell != log_domain)) return FRIEDA_ERR_ARG;
-    try {
-        verify_cells_host(commitment, log_domain, log_cell, cell_index, n_cells, values, paths, out_status);
-    } catch (const std::bad_alloc&) {
-        return FRIEDA_ERR_NOMEM;
-    }
-    return FRIEDA_OK;
-}
-
-int frieda_verify_cells_many(frieda_ctx* ctx, const uint8_t commitment[32], uint32_t log_domain, uint32_t log_cell, const uint32_t* cell_index,
-                             uint32_t n_cells, const uint32_t* values, const uint8_t* paths, uint8_t* out_status) {
-    if (!ctx) return FRIEDA_ERR_ARG;
-    if (n_cells == 0) return FRIEDA_OK;
-    if (!commitment || !cell_index || !values || !out_status || (!paths && log_cell != log_domain)) return FRIEDA_ERR_ARG;
-    if (const char* bad = cells_args_error(log_domain, log_cell, cell_index, n_cells)) return ctx->c.fail(FRIEDA_ERR_ARG, std::string("verify_cells_many: ") + bad);
-    FR_NO_JOB(&ctx->c);
-    FR_GUARD_BEGIN
-    return verify_cells_device(&ctx->c, commitment, log_domain, log_cell, cell_index, n_cells, values, paths, out_status, nullptr);
-    FR_GUARD_END(ctx)
-}
-
-int frieda_reconstruct_from_opened_cells(frieda_ctx* ctx, const uint8_t commitment[32], uint32_t log_blowup_factor, size_t len, uint32_t log_cell,
-                                         const uint32_t* cell_index, uint32_t n_cells, const uint32_t* values, const uint8_t* paths,
-                                         uint8_t* out_bytes, uint8_t* out_status, size_t* n_cells_used) {
-    if (!ctx || !commitment || !n_cells_used || (len && !out_bytes) || (n_cells && (!cell_index || !values || !out_status))) return FRIEDA_ERR_ARG;
-    *n_cells_used = 0;
-    if (log_blowup_factor > FRIEDA_MAX_LOG_DOMAIN || len > ((size_t)1 << 40)) return ctx->c.fail(FRIEDA_ERR_ARG, "reconstruct_from_opened_cells: shape out of range");
-    const uint32_t L = codec_shape(len).log_size, n = L + log_blowup_factor;
-    if (L < 1 || n < 2 || n + 1 > FRIEDA_MAX_LOG_DOMAIN) return ctx->c.fail(FRIEDA_ERR_ARG, "reconstruct_from_opened_cells: shape out of range");
-    if (const char* bad = cells_args_error(n, log_cell, cell_index, n_cells)) return ctx->c.fail(FRIEDA_ERR_ARG, std::string("reconstruct_from_opened_cells: ") + bad);
-    if (n_cells && !paths && log_cell != n) return FRIEDA_ERR_ARG;
-    FR_NO_JOB(&ctx->c);
-    FR_GUARD_BEGIN
-    const size_t need = log_cell ? (((size_t)1 << L) >> log_cell) + 1 : ((size_t)1 << L) + 2;
-    uint32_t nd = 0;
-    auto too_few = [&]() {
-        return ctx->c.fail(FRIEDA_ERR_ARG, std::to_string(nd) + " distinct accepted cells, " + std::to_string(need) + " needed");
-    };
-    if (n_cells == 0) return too_few();
-    CellPool pool;
-    int rc = verify_cells_device(&ctx->c, commitment, n, log_cell, cell_index, n_cells, values, paths, out_status, &pool);
-    if (rc != FRIEDA_OK) return rc;
-    if (pool.n == 0) return too_few();
-    void* d_out = nullptr;
-    const hipError_t e = hipMalloc(&d_out, len ? len : 1);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        ctx->c.err = std::string("hipMalloc: ") + hipGetErrorString(e);
-        return FRIEDA_ERR_NOMEM;
-    }
-    if (const hipError_t pe = ctx->c.poison_fresh(d_out, len ? len : 1); pe != hipSuccess) {
-        (void)hipFree(d_out);
-        return ctx->c.hip_fail(pe, "poison(rebuilt bytes)");
-    }
-    std::vector<uint8_t> bytes(len);
-    rc = reconstruct_cells_pooled(ctx, pool.d_val(), pool.d_idx(), (uint32_t)pool.n, log_cell, L, n, len, d_out, &nd);
-    *n_cells_used = nd;
-    if (rc == FRIEDA_OK) rc = frieda_dev_download(ctx, bytes.data(), d_out, len);
-    (void)hipStreamSynchronize(ctx->c.stream);
-    (void)hipFree(d_out);
-    if (rc == FRIEDA_ERR_ARG && nd < need) return too_few();
-    if (rc != FRIEDA_OK) return rc;
-    uint8_t root[32];
-    rc = commit_host(&ctx->c, bytes.data(), len, log_blowup_factor, root);
-    if (rc != FRIEDA_OK) return rc;
-    if (memcmp(root, commitment, 32) != 0) return ctx->c.fail(FRIEDA_ERR_ARG, "the rebuilt blob does not commit to the commitment (wrong len?)");
-    if (len) memcpy(out_bytes, bytes.data(), len);
-    return FRIEDA_OK;
-    FR_GUARD_END(ctx)
-}
-
-// ---- the cells of many blobs of one shape in one call ----
-namespace {
-constexpr uint32_t CELLS_MAX_BLOBS = 65536, STRIPES_MAX_BLOBS = 256;  // (the point reconstruction takes at most 1024 columns)
-// the argument rule the three (blob, cell) pair calls share; null when it holds
-const char* cells_blobs_args_error(uint32_t n_blobs, uint32_t log_domain, uint32_t log_cell, const uint32_t* blob_index, const uint32_t* cell_index,
-                                   uint32_t n_cells) {
-    if (n_blobs == 0 || n_blobs > CELLS_MAX_BLOBS) return "n_blobs out of range";
-    for (uint32_t i = 0; i < n_cells; i++)
-        if (blob_index[i] >= n_blobs) return "blob index out of range";
-    return cells_args_error(log_domain, log_cell, cell_index, n_cells);
-}
-}  // namespace
-
-int frieda_open_cells_blobs(frieda_ctx* ctx, const frieda_encoded* const* encs, uint32_t n_blobs, uint32_t log_cell, const uint32_t* blob_index,
-                            const uint32_t* cell_index, uint32_t n_cells, uint32_t* out_values, uint8_t* out_paths) {
-    if (!ctx || !encs || n_blobs == 0 || n_blobs > CELLS_MAX_BLOBS) return FRIEDA_ERR_ARG;
-    for (uint32_t b = 0; b < n_blobs; b++)
-        if (!encs[b]) return FRIEDA_ERR_ARG;
-    FR_GUARD_BEGIN
-    const uint32_t n = encs[0]->e.n;
-    std::vector<const Encoded*> blobs(n_blobs);
-    for (uint32_t b = 0; b < n_blobs; b++) {
-        if (encs[b]->e.n != n) return ctx->c.fail(FRIEDA_ERR_ARG, "open_cells_blobs: the blobs of a call must have one log_domain");
-        if (encs[b]->e.device != ctx->c.device) return ctx->c.fail(FRIEDA_ERR_ARG, "open_cells_blobs: the context is not on the encoded blobs' device");
-        blobs[b] = &encs[b]->e;
-    }
-    if (n_cells == 0) return FRIEDA_OK;
-    if (!blob_index || !cell_index || !out_values || (!out_paths && log_cell != n)) return FRIEDA_ERR_ARG;
-    if (const char* bad = cells_blobs_args_error(n_blobs, n, log_cell, blob_index, cell_index, n_cells))
-        return ctx->c.fail(FRIEDA_ERR_ARG, std::string("open_cells_blobs: ") + bad);
-    return open_cells_blobs(&ctx->c, blobs.data(), n_blobs, log_cell, blob_index, cell_index, n_cells, out_values, out_paths);
-    FR_GUARD_END(ctx)
-}
-
-int frieda_verify_cells_blobs(const uint8_t* commitments, uint32_t n_blobs, uint32_t log_domain, uint32_t log_cell, const uint32_t* blob_index,
-                              const uint32_t* cell_index, uint32_t n_cells, const uint32_t* values, const uint8_t* paths, uint8_t* out_status) {
-    if (n_cells == 0) return FRIEDA_OK;
-    if (!commitments || !blob_index || !cell_index || !values || !out_status) return FRIEDA_ERR_ARG;
-    if (cells_blobs_args_error(n_blobs, log_domain, log_cell, blob_index, cell_index, n_cells) || (!paths && log_cell != log_domain)) return FRIEDA_ERR_ARG;
-    try {
-        verify_cells_blobs_host(commitments, log_domain, log_cell, blob_index, cell_index, n_cells, values, paths, out_status);
-    } catch (const std::bad_alloc&) {
-        return FRIEDA_ERR_NOMEM;
-    }
-    return FRIEDA_OK;
-}
-
-int frieda_verify_cells_blobs_many(frieda_ctx* ctx, const uint8_t* commitments, uint32_t n_blobs, uint32_t log_domain, uint32_t log_cell,
-                                   const uint32_t* blob_index, const uint32_t* cell_index, uint32_t n_cells, const uint32_t* values, const uint8_t* paths,
-                                   uint8_t* out_status) {
-    if (!ctx) return FRIEDA_ERR_ARG;
-    if (n_cells == 0) return FRIEDA_OK;
-    if (!commitments || !blob_index || !cell_index || !values || !out_status || (!paths && log_cell != log_domain)) return FRIEDA_ERR_ARG;
-    if (const char* bad = cells_blobs_args_error(n_blobs, log_domain, log_cell, blob_index, cell_index, n_cells))
-        return ctx->c.fail(FRIEDA_ERR_ARG, std::string("verify_cells_blobs_many: ") + bad);
-    FR_NO_JOB(&ctx->c);
-    FR_GUARD_BEGIN
-    return verify_cells_blobs_device(&ctx->c, commitments, n_blobs, log_domain, log_cell, blob_index, cell_index, n_cells, values, paths, out_status, nullptr);
-    FR_GUARD_END(ctx)
-}
-
-int frieda_reconstruct_blobs_from_opened_stripes(frieda_ctx* ctx, const uint8_t* commitments, uint32_t n_blobs, uint32_t log_blowup_factor, size_t len,
-                                                 uint32_t log_cell, const uint32_t* stripe_index, uint32_t n_stripes, const uint32_t* values,
-                                                 const uint8_t* paths, uint8_t* out_bytes, uint8_t* out_status, size_t* n_stripes_used) {
-    if (!ctx || !commitments || !n_stripes_used || (len && !out_bytes) || (n_stripes && (!stripe_index || !values || !out_status))) return FRIEDA_ERR_ARG;
-    *n_stripes_used = 0;
-    const char* const fn = "reconstruct_blobs_from_opened_stripes: ";
-    if (n_blobs == 0 || n_blobs > STRIPES_MAX_BLOBS) return ctx->c.fail(FRIEDA_ERR_ARG, std::string(fn) + "n_blobs out of range (1 .. 256)");
-    if (log_blowup_factor > FRIEDA_MAX_LOG_DOMAIN || len > ((size_t)1 << 40)) return ctx->c.fail(FRIEDA_ERR_ARG, std::string(fn) + "shape out of range");
-    const uint32_t L = codec_shape(len).log_size, n = L + log_blowup_factor;
-    if (L < 1 || n < 2 || n + 1 > FRIEDA_MAX_LOG_DOMAIN) return ctx->c.fail(FRIEDA_ERR_ARG, std::string(fn) + "shape out of range");
-    if (const char* bad = cells_args_error(n, log_cell, stripe_index, n_stripes)) return ctx->c.fail(FRIEDA_ERR_ARG, std::string(fn) + bad);
-    if (n_stripes && !paths && log_cell != n) return FRIEDA_ERR_ARG;
-    // the staged values are the point reconstruction's sample buffer: at most 2^32 words (its positions are 32-bit)
-    if ((uint64_t)n_stripes * n_blobs > (0x100000000ull >> (log_cell + 2))) return ctx->c.fail(FRIEDA_ERR_ARG, std::string(fn) + "more than 2^32 value words");
-    FR_NO_JOB(&ctx->c);
-    FR_GUARD_BEGIN
-    const size_t need = log_cell ? (((size_t)1 << L) >> log_cell) + 1 : ((size_t)1 << L) + 2;
-    uint32_t nd = 0;
-    auto too_few = [&]() {
-        return ctx->c.fail(FRIEDA_ERR_ARG, std::to_string(nd) + " distinct fully accepted stripes, " + std::to_string(need) + " needed");
-    };
-    if (n_stripes == 0) return too_few();
-    CellPool pool;
-    int rc = verify_cells_blobs_device(&ctx->c, commitments, n_blobs, n, log_cell, nullptr, stripe_index, n_stripes * n_blobs, values, paths, out_status, &pool);
-    if (rc != FRIEDA_OK) return rc;
-    if (pool.n == 0) return too_few();
-    // the rebuilt bytes stay on the device for the commitment check: blob b at b * stride
-    const size_t stride = std::max<size_t>(256, (len + 255) & ~(size_t)255);
-    void* d_out = nullptr;
-    const hipError_t e = hipMalloc(&d_out, stride * n_blobs);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        ctx->c.err = std::string("hipMalloc: ") + hipGetErrorString(e);
-        return FRIEDA_ERR_NOMEM;
-    }
-    if (const hipError_t pe = ctx->c.poison_fresh(d_out, stride * n_blobs); pe != hipSuccess) {
-        (void)hipFree(d_out);
-        return ctx->c.hip_fail(pe, "poison(rebuilt bytes)");
-    }
-    std::vector<uint8_t> roots(32 * (size_t)n_blobs), bytes(len * n_blobs);
-    rc = reconstruct_stripes_pooled(ctx, pool.d_val(), pool.d_idx(), (uint32_t)pool.n, n_blobs, log_cell, L, n, len, static_cast<uint8_t*>(d_out), stride, &nd);
-    *n_stripes_used = nd;
-    if (rc == FRIEDA_OK) rc = commit_batch(&ctx->c, static_cast<const uint8_t*>(d_out), stride, len, n_blobs, true, log_blowup_factor, roots.data());
-    if (rc == FRIEDA_OK && len && hipMemcpy2D(bytes.data(), len, d_out, stride, len, n_blobs, hipMemcpyDeviceToHost) != hipSuccess)
-        rc = ctx->c.hip_fail(hipGetLastError(), "hipMemcpy2D(rebuilt bytes)");
-    (void)hipStreamSynchronize(ctx->c.stream);
-    (void)hipFree(d_out);
-    if (rc == FRIEDA_ERR_ARG && nd < need) return too_few();
-    if (rc != FRIEDA_OK) return rc;
-    for (uint32_t b = 0; b < n_blobs; b++)
-        if (memcmp(&roots[32 * (size_t)b], commitments + 32 * (size_t)b, 32) != 0)
-            return ctx->c.fail(FRIEDA_ERR_ARG, "the rebuilt blob " + std::to_string(b) + " does not commit to its commitment (wrong len?)");
-    if (len) memcpy(out_bytes, bytes.data(), len * n_blobs);
-    return FRIEDA_OK;
-    FR_GUARD_END(ctx)
 }
 
 int frieda_prove_seeds_begin(frieda_ctx* ctx, const frieda_encoded* enc, const uint64_t* seeds, uint32_t n_seeds, frieda_pcs_config cfg) {

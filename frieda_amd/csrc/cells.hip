@@ -16,10 +16,12 @@
 //                   launch: the walk's lane hashes its one leaf itself.  (One fused launch would leave the walk with 2^(9 - c) busy lanes
 //                   of 256 per workgroup; the compressions are the plain form — neither launch fills the chip at a client's cell counts.)
 //   cells_gather    the accepted cells of a pass -> the pool the reconstruction reads (verify.hip's pairs_gather_kernel for cells).
-//   *_blobs         the same for cells of MANY blobs of one shape in one call: open reads eval / tree / skip_log from a per-blob table, the
-//                   walk compares with a table of commitments in device memory; cells_roots is shared as it is.
+//   *_blobs         the same kernels instantiated for cells of MANY blobs of one shape: open takes eval / tree / skip_log from the cell's row
+//                   of a per-blob table, the walk its commitment from a table in device memory; cells_roots knows neither.
 //   cells_stripe_*  a stripe = cell j of every blob of a block.  accept: a wave per stripe ANDs its cells' status words; gather: the fully
 //                   accepted stripes -> the pool, which is the point reconstruction's layout at 4 * n_blobs columns.
+#include <type_traits>
+
 #include "kernels.h"
 #include "tree_dev.h"
 
@@ -63,41 +65,57 @@ __device__ __forceinline__ void node_from_eval(const uint32_t* __restrict__ v, u
     b2_merkle_block<B2_LAT>(m, h);
 }
 
+// The blob cell `cell` is opened from: the one of the call, or row bidx[cell] of the call's table (cell i is cell idx[i] of blob bidx[i]).
+// The single-blob form reads the kernel arguments and nothing else.
+struct BlobSource {
+    const uint32_t* __restrict__ eval;
+    const uint8_t* __restrict__ tree;
+    uint32_t skip_log;
+};
+__device__ __forceinline__ BlobSource blob_of(const CellsOpenArgs& a, size_t) { return {a.eval, a.tree, a.skip_log}; }
+__device__ __forceinline__ BlobSource blob_of(const CellsOpenBlobsArgs& a, size_t cell) {
+    const CellsBlobRow& row = a.table[a.bidx[cell]];
+    return {row.eval, row.tree, row.skip_log};
+}
+
 // out_values[cell][col][2^c]: VEC = 4 copies 16 bytes per thread (c >= 2: every run starts on a 16-byte boundary), VEC = 1 one word
-template <int VEC>
-__global__ __launch_bounds__(CL_THREADS) void cells_open_values_kernel(CellsOpenArgs a) {
+template <int VEC, class Args>
+__global__ __launch_bounds__(CL_THREADS) void cells_open_values_kernel(Args a) {
     const size_t e = (size_t)blockIdx.x * CL_THREADS + threadIdx.x;  // unit of VEC words of the output
     const uint32_t c = a.log_cell, lu = c - (VEC == 4 ? 2 : 0);      // log2 of the units of one run
     if (e >= ((size_t)a.n_cells * 4) << lu) return;
     const size_t run = e >> lu, cell = run >> 2;
     const uint32_t col = (uint32_t)(run & 3), u = (uint32_t)(e & (((size_t)1 << lu) - 1));
+    const uint32_t* __restrict__ eval = blob_of(a, cell).eval;
     const size_t src = ((size_t)col << a.n) + ((size_t)a.idx[cell] << c) + (size_t)u * VEC;
     if constexpr (VEC == 4)
-        reinterpret_cast<uint4*>(a.out_values)[e] = *reinterpret_cast<const uint4*>(a.eval + src);
+        reinterpret_cast<uint4*>(a.out_values)[e] = *reinterpret_cast<const uint4*>(eval + src);
     else
-        a.out_values[e] = a.eval[src];
+        a.out_values[e] = eval[src];
 }
 
-// out_paths[cell][s]: the sibling of the node above the cell at level n - c - s
-__global__ __launch_bounds__(CL_THREADS) void cells_open_paths_kernel(CellsOpenArgs a) {
+// out_paths[cell][s]: the sibling of the node above the cell at level n - c - s; the "stored" rule is evaluated for the cell's blob
+template <class Args>
+__global__ __launch_bounds__(CL_THREADS) void cells_open_paths_kernel(Args a) {
     const size_t e = (size_t)blockIdx.x * CL_THREADS + threadIdx.x;
     const uint32_t depth = a.n - a.log_cell;
     if (e >= (size_t)a.n_cells * depth) return;
     const size_t cell = e / depth;
     const uint32_t s = (uint32_t)(e - cell * depth), level = depth - s;
     const size_t node = (size_t)(a.idx[cell] >> s) ^ 1;
+    const BlobSource b = blob_of(a, cell);
     uint4* o = a.out_paths + 2 * e;
     // Deliberately conservative: decommit.hip's rule, by the threshold alone.  A route that wrote levels n - 1, n - 2 although n >= skip_log
     // (the fused small-domain launch never skips them) is re-hashed all the same — the words are equal, and no route is ever read where
     // it did not write.
-    const bool stored = level < a.n && !(a.n >= a.skip_log && level + 2 >= a.n);
+    const bool stored = level < a.n && !(a.n >= b.skip_log && level + 2 >= a.n);
     if (stored) {
-        const uint4* p = reinterpret_cast<const uint4*>(a.tree + treedev::layer_off(a.n, level) + 32 * node);
+        const uint4* p = reinterpret_cast<const uint4*>(b.tree + treedev::layer_off(a.n, level) + 32 * node);
         const uint4 x = p[0], y = p[1];
         o[0] = x, o[1] = y;
     } else {
         uint32_t h[8];
-        node_from_eval(a.eval, a.n, a.n - level, node, h);
+        node_from_eval(b.eval, a.n, a.n - level, node, h);
         o[0] = make_uint4(h[0], h[1], h[2], h[3]);
         o[1] = make_uint4(h[4], h[5], h[6], h[7]);
     }
@@ -158,9 +176,10 @@ __global__ __launch_bounds__(CL_THREADS) void cells_roots_kernel(CellsVerifyArgs
     }
 }
 
-// LEAF (c = 0): the lane hashes its cell's one leaf; else it takes the subtree root the first launch left
-template <bool LEAF>
-__global__ __launch_bounds__(CL_THREADS) void cells_walk_kernel(CellsVerifyArgs a) {
+// LEAF (c = 0): the lane hashes its cell's one leaf; else it takes the subtree root the first launch left.
+// TABLE: lane `cell` compares with coms[bidx[cell]][8] in device memory; else with a.commitment, and bidx / coms are not read
+template <bool LEAF, bool TABLE>
+__global__ __launch_bounds__(CL_THREADS) void cells_walk_kernel(CellsVerifyArgs a, const uint32_t* __restrict__ bidx, const uint32_t* __restrict__ coms) {
     const size_t cell = (size_t)blockIdx.x * CL_THREADS + threadIdx.x;
     if (cell >= a.n_cells) return;
     uint32_t h[8], bad;
@@ -186,8 +205,14 @@ __global__ __launch_bounds__(CL_THREADS) void cells_walk_kernel(CellsVerifyArgs 
         b2_merkle_block<B2_LAT>(m, h);
     }
     uint32_t diff = bad;
+    if constexpr (TABLE) {
+        const uint4* want = reinterpret_cast<const uint4*>(coms + 8 * (size_t)bidx[cell]);
+        const uint4 x = want[0], y = want[1];
+        diff |= (h[0] ^ x.x) | (h[1] ^ x.y) | (h[2] ^ x.z) | (h[3] ^ x.w) | (h[4] ^ y.x) | (h[5] ^ y.y) | (h[6] ^ y.z) | (h[7] ^ y.w);
+    } else {
 #pragma unroll
-    for (int w = 0; w < 8; w++) diff |= h[w] ^ a.commitment[w];
+        for (int w = 0; w < 8; w++) diff |= h[w] ^ a.commitment[w];
+    }
     a.status[cell] = diff == 0 ? 1u : 0u;
 }
 
@@ -202,79 +227,6 @@ __global__ __launch_bounds__(CL_THREADS) void cells_gather_kernel(const uint32_t
     const size_t src = tab[2 * row], dst = tab[2 * row + 1];
     pool_val[(dst << lw) + w] = values[(src << lw) + w];
     if (w == 0) pool_idx[dst] = idx[src];
-}
-
-// ---- the cells of many blobs of one shape in one call: cell i is cell idx[i] of blob bidx[i] ----
-// cells_open_values_kernel with eval taken from the cell's row of the blob table
-template <int VEC>
-__global__ __launch_bounds__(CL_THREADS) void cells_open_blobs_values_kernel(CellsOpenBlobsArgs a) {
-    const size_t e = (size_t)blockIdx.x * CL_THREADS + threadIdx.x;
-    const uint32_t c = a.log_cell, lu = c - (VEC == 4 ? 2 : 0);
-    if (e >= ((size_t)a.n_cells * 4) << lu) return;
-    const size_t run = e >> lu, cell = run >> 2;
-    const uint32_t col = (uint32_t)(run & 3), u = (uint32_t)(e & (((size_t)1 << lu) - 1));
-    const uint32_t* __restrict__ eval = a.table[a.bidx[cell]].eval;
-    const size_t src = ((size_t)col << a.n) + ((size_t)a.idx[cell] << c) + (size_t)u * VEC;
-    if constexpr (VEC == 4)
-        reinterpret_cast<uint4*>(a.out_values)[e] = *reinterpret_cast<const uint4*>(eval + src);
-    else
-        a.out_values[e] = eval[src];
-}
-
-// cells_open_paths_kernel with eval, tree and skip_log taken from the cell's row: the "stored" rule is evaluated per blob
-__global__ __launch_bounds__(CL_THREADS) void cells_open_blobs_paths_kernel(CellsOpenBlobsArgs a) {
-    const size_t e = (size_t)blockIdx.x * CL_THREADS + threadIdx.x;
-    const uint32_t depth = a.n - a.log_cell;
-    if (e >= (size_t)a.n_cells * depth) return;
-    const size_t cell = e / depth;
-    const uint32_t s = (uint32_t)(e - cell * depth), level = depth - s;
-    const size_t node = (size_t)(a.idx[cell] >> s) ^ 1;
-    const CellsBlobRow row = a.table[a.bidx[cell]];
-    uint4* o = a.out_paths + 2 * e;
-    const bool stored = level < a.n && !(a.n >= row.skip_log && level + 2 >= a.n);
-    if (stored) {
-        const uint4* p = reinterpret_cast<const uint4*>(row.tree + treedev::layer_off(a.n, level) + 32 * node);
-        const uint4 x = p[0], y = p[1];
-        o[0] = x, o[1] = y;
-    } else {
-        uint32_t h[8];
-        node_from_eval(row.eval, a.n, a.n - level, node, h);
-        o[0] = make_uint4(h[0], h[1], h[2], h[3]);
-        o[1] = make_uint4(h[4], h[5], h[6], h[7]);
-    }
-}
-
-// cells_walk_kernel against a table of commitments in device memory: lane `cell` compares with coms[bidx[cell]][8]
-template <bool LEAF>
-__global__ __launch_bounds__(CL_THREADS) void cells_walk_blobs_kernel(CellsVerifyArgs a, const uint32_t* __restrict__ bidx, const uint32_t* __restrict__ coms) {
-    const size_t cell = (size_t)blockIdx.x * CL_THREADS + threadIdx.x;
-    if (cell >= a.n_cells) return;
-    uint32_t h[8], bad;
-    if constexpr (LEAF) {
-        const uint4 v = reinterpret_cast<const uint4*>(a.values)[cell];
-        bad = (v.x >= P31) | (v.y >= P31) | (v.z >= P31) | (v.w >= P31);
-        treedev::leaf_hash<B2_LAT>(v.x, v.y, v.z, v.w, h);
-    } else {
-#pragma unroll
-        for (int w = 0; w < 8; w++) h[w] = a.roots[(size_t)w * a.n_cells + cell];
-        bad = a.bad[cell];
-    }
-    const uint32_t idx = a.idx[cell], depth = a.n - a.log_cell;
-#pragma unroll 1
-    for (uint32_t s = 0; s < depth; s++) {
-        const uint4* p = a.paths + 2 * ((size_t)s * a.n_cells + cell);
-        const uint4 x = p[0], y = p[1];
-        const uint32_t sib[8] = {x.x, x.y, x.z, x.w, y.x, y.y, y.z, y.w};
-        const bool right = (idx >> s) & 1;
-        uint32_t m[16];
-#pragma unroll
-        for (int w = 0; w < 8; w++) m[w] = right ? sib[w] : h[w], m[8 + w] = right ? h[w] : sib[w];
-        b2_merkle_block<B2_LAT>(m, h);
-    }
-    const uint4* want = reinterpret_cast<const uint4*>(coms + 8 * (size_t)bidx[cell]);
-    const uint4 x = want[0], y = want[1];
-    const uint32_t diff = bad | (h[0] ^ x.x) | (h[1] ^ x.y) | (h[2] ^ x.z) | (h[3] ^ x.w) | (h[4] ^ y.x) | (h[5] ^ y.y) | (h[6] ^ y.z) | (h[7] ^ y.w);
-    a.status[cell] = diff == 0 ? 1u : 0u;
 }
 
 // a wave per stripe: its lanes AND the status words of the stripe's n_blobs cells (any n_blobs: the lanes stride over them), one vote
@@ -305,37 +257,48 @@ __global__ __launch_bounds__(CL_THREADS) void cells_stripe_gather_kernel(const u
 
 unsigned blocks_for(size_t units) { return (unsigned)((units + CL_THREADS - 1) / CL_THREADS); }
 
-}  // namespace
-
-void cells_open(const Launch& L, const CellsOpenArgs& a) {
+template <class Args>
+void open_launch(const Launch& L, const Args& a) {
+    constexpr bool TABLE = std::is_same<Args, CellsOpenBlobsArgs>::value;
     if (!a.n_cells) return;
     {
-        Scope scope(L, "cells_open_values", 32.0 * (double)(((size_t)a.n_cells) << a.log_cell));
+        Scope scope(L, TABLE ? "cells_open_blobs_values" : "cells_open_values", 32.0 * (double)(((size_t)a.n_cells) << a.log_cell));
         if (a.log_cell >= 2)
             cells_open_values_kernel<4><<<blocks_for(((size_t)a.n_cells * 4) << (a.log_cell - 2)), CL_THREADS, 0, L.stream>>>(a);
         else
             cells_open_values_kernel<1><<<blocks_for(((size_t)a.n_cells * 4) << a.log_cell), CL_THREADS, 0, L.stream>>>(a);
     }
     if (a.n > a.log_cell) {
-        Scope scope(L, "cells_open_paths", 64.0 * (double)a.n_cells * (a.n - a.log_cell));
+        Scope scope(L, TABLE ? "cells_open_blobs_paths" : "cells_open_paths", 64.0 * (double)a.n_cells * (a.n - a.log_cell));
         cells_open_paths_kernel<<<blocks_for((size_t)a.n_cells * (a.n - a.log_cell)), CL_THREADS, 0, L.stream>>>(a);
     }
 }
 
-void cells_verify(const Launch& L, const CellsVerifyArgs& a) {
+template <bool TABLE>
+void verify_launch(const Launch& L, const CellsVerifyArgs& a, const uint32_t* d_bidx, const uint32_t* d_commitments) {
     if (!a.n_cells) return;
     if (a.log_cell == 0) {
-        Scope scope(L, "cells_walk", 0.0);
-        cells_walk_kernel<true><<<blocks_for(a.n_cells), CL_THREADS, 0, L.stream>>>(a);
+        Scope scope(L, TABLE ? "cells_walk_blobs" : "cells_walk", 0.0);
+        cells_walk_kernel<true, TABLE><<<blocks_for(a.n_cells), CL_THREADS, 0, L.stream>>>(a, d_bidx, d_commitments);
         return;
     }
     {
-        Scope scope(L, "cells_roots", 0.0);
+        Scope scope(L, "cells_roots", 0.0);  // (knows neither index nor commitment)
         const uint32_t cpw = a.log_cell >= 10 ? 1u : 1u << (9 - a.log_cell);
         cells_roots_kernel<<<(a.n_cells + cpw - 1) / cpw, CL_THREADS, 0, L.stream>>>(a);
     }
-    Scope scope(L, "cells_walk", 0.0);
-    cells_walk_kernel<false><<<blocks_for(a.n_cells), CL_THREADS, 0, L.stream>>>(a);
+    Scope scope(L, TABLE ? "cells_walk_blobs" : "cells_walk", 0.0);
+    cells_walk_kernel<false, TABLE><<<blocks_for(a.n_cells), CL_THREADS, 0, L.stream>>>(a, d_bidx, d_commitments);
+}
+
+}  // namespace
+
+void cells_open(const Launch& L, const CellsOpenArgs& a) { open_launch(L, a); }
+void cells_open_blobs(const Launch& L, const CellsOpenBlobsArgs& a) { open_launch(L, a); }
+
+void cells_verify(const Launch& L, const CellsVerifyArgs& a) { verify_launch<false>(L, a, nullptr, nullptr); }
+void cells_verify_blobs(const Launch& L, const CellsVerifyArgs& a, const uint32_t* d_bidx, const uint32_t* d_commitments) {
+    verify_launch<true>(L, a, d_bidx, d_commitments);
 }
 
 void cells_gather(const Launch& L, const uint32_t* d_tab, uint32_t n_rows, const uint32_t* d_values, const uint32_t* d_idx, uint32_t log_cell,
@@ -344,37 +307,6 @@ void cells_gather(const Launch& L, const uint32_t* d_tab, uint32_t n_rows, const
     Scope scope(L, "cells_gather", 0.0);
     cells_gather_kernel<<<blocks_for((size_t)n_rows << (log_cell + 2)), CL_THREADS, 0, L.stream>>>(d_tab, n_rows, d_values, d_idx, log_cell, d_pool_idx,
                                                                                                   d_pool_val);
-}
-
-void cells_open_blobs(const Launch& L, const CellsOpenBlobsArgs& a) {
-    if (!a.n_cells) return;
-    {
-        Scope scope(L, "cells_open_blobs_values", 32.0 * (double)(((size_t)a.n_cells) << a.log_cell));
-        if (a.log_cell >= 2)
-            cells_open_blobs_values_kernel<4><<<blocks_for(((size_t)a.n_cells * 4) << (a.log_cell - 2)), CL_THREADS, 0, L.stream>>>(a);
-        else
-            cells_open_blobs_values_kernel<1><<<blocks_for(((size_t)a.n_cells * 4) << a.log_cell), CL_THREADS, 0, L.stream>>>(a);
-    }
-    if (a.n > a.log_cell) {
-        Scope scope(L, "cells_open_blobs_paths", 64.0 * (double)a.n_cells * (a.n - a.log_cell));
-        cells_open_blobs_paths_kernel<<<blocks_for((size_t)a.n_cells * (a.n - a.log_cell)), CL_THREADS, 0, L.stream>>>(a);
-    }
-}
-
-void cells_verify_blobs(const Launch& L, const CellsVerifyArgs& a, const uint32_t* d_bidx, const uint32_t* d_commitments) {
-    if (!a.n_cells) return;
-    if (a.log_cell == 0) {
-        Scope scope(L, "cells_walk_blobs", 0.0);
-        cells_walk_blobs_kernel<true><<<blocks_for(a.n_cells), CL_THREADS, 0, L.stream>>>(a, d_bidx, d_commitments);
-        return;
-    }
-    {
-        Scope scope(L, "cells_roots", 0.0);  // (knows neither index nor commitment: the single-blob launch)
-        const uint32_t cpw = a.log_cell >= 10 ? 1u : 1u << (9 - a.log_cell);
-        cells_roots_kernel<<<(a.n_cells + cpw - 1) / cpw, CL_THREADS, 0, L.stream>>>(a);
-    }
-    Scope scope(L, "cells_walk_blobs", 0.0);
-    cells_walk_blobs_kernel<false><<<blocks_for(a.n_cells), CL_THREADS, 0, L.stream>>>(a, d_bidx, d_commitments);
 }
 
 void cells_stripe_accept(const Launch& L, const uint32_t* d_status, uint32_t n_stripes, uint32_t n_blobs, uint32_t* d_accept) {

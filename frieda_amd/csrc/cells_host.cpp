@@ -1,31 +1,25 @@
-// cells_host.cpp — authenticated cells: the host side of cells.hip (frieda_open_cells, frieda_verify_cells, frieda_verify_cells_many,
-// frieda_reconstruct_from_opened_cells, and their forms over the blobs of a block: frieda_open_cells_blobs, frieda_verify_cells_blobs,
-// frieda_verify_cells_blobs_many, frieda_reconstruct_blobs_from_opened_stripes; the exports are in capi.cpp).
+// cells_host.cpp — authenticated cells: the host side of cells.hip and its exports (frieda_open_cells, frieda_verify_cells,
+// frieda_verify_cells_many, frieda_reconstruct_from_opened_cells, and their forms over the blobs of a block: frieda_open_cells_blobs,
+// frieda_verify_cells_blobs, frieda_verify_cells_blobs_many, frieda_reconstruct_blobs_from_opened_stripes).
 //
 // A cell with its path is a self-contained message (values, index, path): every cell carries its own n - log_cell siblings, nothing is
 // shared between the cells of a call, and a cell's status never depends on the others.  The host verifier and the kernels hash the
 // same way (blake2s.h): a leaf is the four column words of one position, a node its two children.
 //
-// The device verifier stages a call through the context's pinned block and arena in passes of bounded size (PASS_BYTES, or the test
-// hook Tuning::test_verify_pass_bytes, as verify_many.cpp): indices, values as given (cell-major), and the paths transposed to
-// level-major so that the path walk's lanes read neighbouring hashes.  With a pool, the accepted cells of a pass are copied from the
-// staged values into the call's CellPool by a gather launch before the next pass overwrites them.
-//
-// Blobs of a block: cell i of a call is cell cell_index[i] of blob blob_index[i]; the blob numbers are staged beside the indices, the
-// commitments go to the device once per call, and the provider uploads a table row per blob (evaluation, tree, skip threshold) with the
-// indices.  A stripe is cell j of every blob: the stripe call cuts its passes at stripe boundaries, and a stripe whose cells are all
-// accepted is gathered whole into the pool — the reconstruction's cell layout at 4 * n_blobs columns.
+// One opener, one host verifier and one pass driver serve both forms.  Blobs of a block: cell i of a call is cell cell_index[i] of blob
+// blob_index[i]; the single-blob calls are the same code without blob numbers, and launch the single-blob kernels.  The driver
+// (verify_cells_passes) stages a call through the pinned block and the arena in passes cut by cells_pass.h; with a pool, what a pass
+// accepted — cells, or whole stripes (cell j of every blob) — is gathered into it before the next pass overwrites the staged values.
 #include <string.h>
 
 #include <algorithm>
 
+#include "cells_pass.h"
 #include "host.h"
 
 namespace frieda {
 
 namespace {
-
-constexpr size_t PASS_BYTES = (size_t)32 << 20;
 
 // compress(0, left || right) / compress(0, leaf words || 0 x 12) on words, as the kernels do
 void node_words(const uint32_t* l, const uint32_t* r, uint32_t* out) {
@@ -61,222 +55,64 @@ bool host_cell_ok(const uint32_t want[8], uint32_t n, uint32_t c, uint32_t index
     return memcmp(h, want, 32) == 0;
 }
 
-}  // namespace
-
-CellPool::~CellPool() {
-    if (d) (void)hipFree(d);
-}
-
-const char* cells_args_error(uint32_t log_domain, uint32_t log_cell, const uint32_t* cell_index, uint32_t n_cells) {
-    if (log_domain > FRIEDA_MAX_LOG_DOMAIN) return "log_domain out of range";
-    if (log_cell > log_domain || log_cell > FRIEDA_MAX_LOG_OPEN_CELL) return "log_cell out of range";
-    const uint32_t bits = log_domain - log_cell;
-    for (uint32_t i = 0; i < n_cells; i++)
-        if (((uint64_t)cell_index[i] >> bits) != 0) return "cell index out of range";
-    return nullptr;
-}
-
-void verify_cells_host(const uint8_t commitment[32], uint32_t log_domain, uint32_t log_cell, const uint32_t* cell_index, uint32_t n_cells,
-                       const uint32_t* values, const uint8_t* paths, uint8_t* out_status) {
-    uint32_t want[8];
-    memcpy(want, commitment, 32);
-    const size_t vw = (size_t)4 << log_cell, pb = 32 * (size_t)(log_domain - log_cell);
-    std::vector<uint32_t> lvl;
-    for (uint32_t i = 0; i < n_cells; i++)
-        out_status[i] = host_cell_ok(want, log_domain, log_cell, cell_index[i], values + i * vw, paths + i * pb, lvl) ? FRIEDA_CELL_ACCEPTED : FRIEDA_CELL_REJECTED;
-}
-
-int verify_cells_device(Ctx* ctx, const uint8_t commitment[32], uint32_t log_domain, uint32_t log_cell, const uint32_t* cell_index, uint32_t n_cells,
-                        const uint32_t* values, const uint8_t* paths, uint8_t* out_status, CellPool* pool) {
-    const uint32_t depth = log_domain - log_cell;
-    const size_t vb = (size_t)16 << log_cell, pb = 32 * (size_t)depth;  // bytes of a cell's values / path
-    FR_HIP(ctx, hipSetDevice(ctx->device));
-    if (pool) {
-        pool->n = 0;
-        pool->cap = n_cells;
-        pool->log_cell = log_cell;
-        void* d = nullptr;
-        const hipError_t e = hipMalloc(&d, ((4 * pool->cap + 255) & ~(size_t)255) + vb * pool->cap);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            ctx->err = std::string("hipMalloc: ") + hipGetErrorString(e);
-            return FRIEDA_ERR_NOMEM;
-        }
-        pool->d = static_cast<uint8_t*>(d);
-        FR_HIP(ctx, ctx->poison_fresh(d, ((4 * pool->cap + 255) & ~(size_t)255) + vb * pool->cap));
-    }
-    const size_t pass_bytes = ctx->tuning.test_verify_pass_bytes ? (size_t)ctx->tuning.test_verify_pass_bytes : PASS_BYTES;
-    const size_t per_pass = std::max<size_t>(1, pass_bytes / (4 + vb + pb));
-    hipStream_t s = ctx->stream;
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    for (size_t first = 0; first < n_cells; first += per_pass) {
-        const size_t np = std::min(per_pass, (size_t)n_cells - first);
-        // staged image: indices | values (cell-major, as given) | paths (level-major); then the status words and the gather table
-        const size_t i_idx = 0, i_val = al(4 * np), i_path = i_val + al(vb * np), in_bytes = i_path + al(pb * np);
-        ArenaPlan ap;
-        const size_t a_in = ap.take(in_bytes), a_roots = ap.take(32 * np), a_bad = ap.take(4 * np), a_status = ap.take(4 * np), a_tab = ap.take(8 * np);
-        int rc = ctx->ensure_arena(ap.off);
-        if (rc) return rc;
-        rc = ensure_pinned(ctx, in_bytes + al(4 * np) + 8 * np);
-        if (rc) return rc;
-        uint8_t* pin = static_cast<uint8_t*>(ctx->pinned);
-        memcpy(pin + i_idx, cell_index + first, 4 * np);
-        memcpy(pin + i_val, reinterpret_cast<const uint8_t*>(values) + vb * first, vb * np);
-        for (size_t j = 0; j < np; j++)
-            for (uint32_t lv = 0; lv < depth; lv++) memcpy(pin + i_path + 32 * (lv * np + j), paths + pb * (first + j) + 32 * (size_t)lv, 32);
-        FR_HIP(ctx, hipMemcpyAsync(ctx->arena + a_in, pin, in_bytes, hipMemcpyHostToDevice, s));
-        k::CellsVerifyArgs va;
-        va.values = reinterpret_cast<const uint32_t*>(ctx->arena + a_in + i_val);
-        va.paths = reinterpret_cast<const uint4*>(ctx->arena + a_in + i_path);
-        va.idx = reinterpret_cast<const uint32_t*>(ctx->arena + a_in + i_idx);
-        va.roots = reinterpret_cast<uint32_t*>(ctx->arena + a_roots);
-        va.bad = reinterpret_cast<uint32_t*>(ctx->arena + a_bad);
-        va.status = reinterpret_cast<uint32_t*>(ctx->arena + a_status);
-        va.n = log_domain;
-        va.log_cell = log_cell;
-        va.n_cells = (uint32_t)np;
-        memcpy(va.commitment, commitment, 32);
-        FR_HIP(ctx, hipMemsetAsync(ctx->arena + a_status, 0xFF, 4 * np, s));  // (a word the kernel did not write is neither 0 nor 1)
-        k::cells_verify(ctx->launch(), va);
-        FR_HIP(ctx, hipGetLastError());
-        uint32_t* res = reinterpret_cast<uint32_t*>(pin + in_bytes);
-        FR_HIP(ctx, hipMemcpyAsync(res, ctx->arena + a_status, 4 * np, hipMemcpyDeviceToHost, s));
-        FR_HIP(ctx, hipStreamSynchronize(s));
-        uint32_t* tab = reinterpret_cast<uint32_t*>(pin + in_bytes + al(4 * np));
-        uint32_t n_rows = 0;
-        for (size_t j = 0; j < np; j++) {
-            if (res[j] > 1) return ctx->fail(FRIEDA_ERR_INVARIANT, "verify_cells: the kernel left no status");
-            out_status[first + j] = res[j] ? FRIEDA_CELL_ACCEPTED : FRIEDA_CELL_REJECTED;
-            if (pool && res[j]) {
-                tab[2 * n_rows] = (uint32_t)j, tab[2 * n_rows + 1] = (uint32_t)pool->n++;
-                n_rows++;
-            }
-        }
-        if (n_rows) {
-            // (the table sits in the pinned block the next pass overwrites: wait for the copy)
-            FR_HIP(ctx, hipMemcpyAsync(ctx->arena + a_tab, tab, 8 * (size_t)n_rows, hipMemcpyHostToDevice, s));
-            k::cells_gather(ctx->launch(), reinterpret_cast<const uint32_t*>(ctx->arena + a_tab), n_rows, va.values, va.idx, log_cell, pool->d_idx(), pool->d_val());
-            FR_HIP(ctx, hipGetLastError());
-            FR_HIP(ctx, hipStreamSynchronize(s));
-        }
-    }
-    return FRIEDA_OK;
-}
-
-int open_cells(Ctx* ctx, const Encoded& enc, uint32_t log_cell, const uint32_t* cell_index, uint32_t n_cells, uint32_t* out_values, uint8_t* out_paths) {
-    FR_NO_JOB(ctx);
-    if (ctx->device != enc.device) return ctx->fail(FRIEDA_ERR_ARG, "open_cells: the context is not on the encoded blob's device");
-    FR_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t ib = 4 * (size_t)n_cells, vb = ((size_t)16 << log_cell) * n_cells, pb = 32 * (size_t)(enc.n - log_cell) * n_cells;
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    ArenaPlan ap;
-    const size_t a_idx = ap.take(ib), a_out = ap.take(al(vb) + pb);  // values | paths: one download
-    int rc = ctx->ensure_arena(ap.off);
-    if (rc) return rc;
-    rc = ensure_pinned(ctx, al(ib) + al(vb) + pb);
-    if (rc) return rc;
-    hipStream_t s = ctx->stream;
-    uint8_t* pin = static_cast<uint8_t*>(ctx->pinned);
-    memcpy(pin, cell_index, ib);
-    FR_HIP(ctx, hipMemcpyAsync(ctx->arena + a_idx, pin, ib, hipMemcpyHostToDevice, s));
-    k::CellsOpenArgs oa;
-    oa.eval = enc.eval();
-    oa.tree = enc.tree();
-    oa.n = enc.n;
-    oa.log_cell = log_cell;
-    oa.skip_log = enc.skip_log;
-    oa.n_cells = n_cells;
-    oa.idx = reinterpret_cast<const uint32_t*>(ctx->arena + a_idx);
-    oa.out_values = reinterpret_cast<uint32_t*>(ctx->arena + a_out);
-    oa.out_paths = reinterpret_cast<uint4*>(ctx->arena + a_out + al(vb));
-    k::cells_open(ctx->launch(), oa);
-    FR_HIP(ctx, hipGetLastError());
-    FR_HIP(ctx, hipMemcpyAsync(pin + al(ib), ctx->arena + a_out, al(vb) + pb, hipMemcpyDeviceToHost, s));
-    FR_HIP(ctx, hipStreamSynchronize(s));
-    memcpy(out_values, pin + al(ib), vb);
-    if (pb) memcpy(out_paths, pin + al(ib) + al(vb), pb);
-    return FRIEDA_OK;
-}
-
-void verify_cells_blobs_host(const uint8_t* commitments, uint32_t log_domain, uint32_t log_cell, const uint32_t* blob_index, const uint32_t* cell_index,
-                             uint32_t n_cells, const uint32_t* values, const uint8_t* paths, uint8_t* out_status) {
+// cell i's commitment: the call's one (blob_index null), or commitments[blob_index[i]]
+void verify_cells_host(const uint8_t* commitments, uint32_t log_domain, uint32_t log_cell, const uint32_t* blob_index, const uint32_t* cell_index,
+                       uint32_t n_cells, const uint32_t* values, const uint8_t* paths, uint8_t* out_status) {
     const size_t vw = (size_t)4 << log_cell, pb = 32 * (size_t)(log_domain - log_cell);
     std::vector<uint32_t> lvl;
     for (uint32_t i = 0; i < n_cells; i++) {
         uint32_t want[8];
-        memcpy(want, commitments + 32 * (size_t)blob_index[i], 32);
+        memcpy(want, commitments + (blob_index ? 32 * (size_t)blob_index[i] : 0), 32);
         out_status[i] = host_cell_ok(want, log_domain, log_cell, cell_index[i], values + i * vw, paths + i * pb, lvl) ? FRIEDA_CELL_ACCEPTED : FRIEDA_CELL_REJECTED;
     }
 }
 
-int verify_cells_blobs_device(Ctx* ctx, const uint8_t* commitments, uint32_t n_blobs, uint32_t log_domain, uint32_t log_cell, const uint32_t* blob_index,
-                              const uint32_t* cell_index, uint32_t n_cells, const uint32_t* values, const uint8_t* paths, uint8_t* out_status,
-                              CellPool* stripes) {
-    const uint32_t depth = log_domain - log_cell;
-    const size_t vb = (size_t)16 << log_cell, pb = 32 * (size_t)depth;  // bytes of a cell's values / path
-    const size_t group = stripes ? n_blobs : 1;                          // cells that stay in one pass
+// One status byte per cell from the kernels, staged in passes (cells_pass.h).  Uses the arena and the pinned block (callers: FR_NO_JOB).
+//   n_blobs 0        one commitment, in the kernel arguments (blob_index is not read)
+//   n_blobs >= 1     commitments[n_blobs][32], uploaded once; cell i belongs to blob blob_index[i]
+//   ... and a pool   stripes: the cells are [n_cells / n_blobs][n_blobs], stripe t is cell cell_index[t] of every blob (blob_index is not read)
+// pool (optional): receives, in the caller's order, the accepted cells (one commitment) or the stripes whose cells are ALL accepted.
+int verify_cells_passes(Ctx* ctx, const uint8_t* commitments, uint32_t n_blobs, uint32_t log_domain, uint32_t log_cell, const uint32_t* blob_index,
+                        const uint32_t* cell_index, uint32_t n_cells, const uint32_t* values, const uint8_t* paths, uint8_t* out_status, CellPool* pool) {
+    const CellsPassShape shape{log_cell, log_domain - log_cell, n_blobs, n_blobs && pool};
+    const size_t vb = shape.value_bytes(), pb = shape.path_bytes();
+    const std::string fn = n_blobs ? "verify_cells_blobs" : "verify_cells";
     FR_HIP(ctx, hipSetDevice(ctx->device));
-    if (stripes) {
-        stripes->n = 0;
-        stripes->cap = n_cells / n_blobs;
-        stripes->log_cell = log_cell;
-        void* d = nullptr;
-        const hipError_t e = hipMalloc(&d, ((4 * stripes->cap + 255) & ~(size_t)255) + vb * n_cells);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            ctx->err = std::string("hipMalloc: ") + hipGetErrorString(e);
-            return FRIEDA_ERR_NOMEM;
-        }
-        stripes->d = static_cast<uint8_t*>(d);
-        FR_HIP(ctx, ctx->poison_fresh(d, ((4 * stripes->cap + 255) & ~(size_t)255) + vb * n_cells));
+    if (pool) {
+        pool->n = 0;
+        const int rc = pool->alloc(ctx, n_cells / shape.group(), vb * shape.group(), "poison(cell pool)");
+        if (rc) return rc;
     }
-    const size_t pass_bytes = ctx->tuning.test_verify_pass_bytes ? (size_t)ctx->tuning.test_verify_pass_bytes : PASS_BYTES;
-    // (a stripe's cells never straddle two passes, and one stripe is always admitted)
-    const size_t per_pass = std::min<size_t>(n_cells, std::max<size_t>(1, pass_bytes / (group * (8 + vb + pb))) * group);
+    const size_t per_pass = cells_per_pass(shape, n_cells, ctx->tuning.test_verify_pass_bytes ? (size_t)ctx->tuning.test_verify_pass_bytes : CELLS_PASS_BYTES);
     hipStream_t s = ctx->stream;
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    // One plan for the call, sized by its largest pass (the first): the commitments sit in front of it and are uploaded once.
-    // staged image of a pass: indices | blob numbers | values (cell-major, as given) | paths (level-major); then the status words, the
-    // accept words of its stripes and the gather table
-    struct Plan {
-        size_t i_idx, i_bidx, i_val, i_path, in_bytes, ns, res_bytes, a_com, a_in, a_roots, a_bad, a_res, a_tab, arena;
-    };
-    auto plan_for = [&](size_t np) {
-        Plan p;
-        p.ns = stripes ? np / n_blobs : 0;
-        p.i_idx = 0, p.i_bidx = al(4 * np), p.i_val = p.i_bidx + al(4 * np), p.i_path = p.i_val + al(vb * np), p.in_bytes = p.i_path + al(pb * np);
-        p.res_bytes = al(4 * np) + 4 * p.ns;
-        ArenaPlan ap;
-        p.a_com = ap.take(32 * (size_t)n_blobs), p.a_in = ap.take(p.in_bytes), p.a_roots = ap.take(32 * np), p.a_bad = ap.take(4 * np);
-        p.a_res = ap.take(p.res_bytes), p.a_tab = ap.take(8 * p.ns);
-        p.arena = ap.off;
-        return p;
-    };
     {
-        const Plan p = plan_for(per_pass);
+        // one plan for the call, sized by its largest pass (the first)
+        const CellsPassPlan p = cells_pass_plan(shape, per_pass);
         int rc = ctx->ensure_arena(p.arena);
         if (rc) return rc;
-        rc = ensure_pinned(ctx, std::max(al(32 * (size_t)n_blobs), p.in_bytes + al(p.res_bytes) + 8 * p.ns));
+        rc = ensure_pinned(ctx, p.pinned);
         if (rc) return rc;
-        memcpy(ctx->pinned, commitments, 32 * (size_t)n_blobs);
-        FR_HIP(ctx, hipMemcpyAsync(ctx->arena + p.a_com, ctx->pinned, 32 * (size_t)n_blobs, hipMemcpyHostToDevice, s));
-        FR_HIP(ctx, hipStreamSynchronize(s));  // (the first pass stages over the pinned block)
+        if (n_blobs) {
+            memcpy(ctx->pinned, commitments, 32 * (size_t)n_blobs);
+            FR_HIP(ctx, hipMemcpyAsync(ctx->arena + p.a_com, ctx->pinned, 32 * (size_t)n_blobs, hipMemcpyHostToDevice, s));
+            FR_HIP(ctx, hipStreamSynchronize(s));  // (the first pass stages over the pinned block)
+        }
     }
+    uint8_t* pin = static_cast<uint8_t*>(ctx->pinned);
     for (size_t first = 0; first < n_cells; first += per_pass) {
         const size_t np = std::min(per_pass, (size_t)n_cells - first);
-        const Plan p = plan_for(np);
-        uint8_t* pin = static_cast<uint8_t*>(ctx->pinned);
+        const CellsPassPlan p = cells_pass_plan(shape, np);
         uint32_t* pin_idx = reinterpret_cast<uint32_t*>(pin + p.i_idx);
         uint32_t* pin_bidx = reinterpret_cast<uint32_t*>(pin + p.i_bidx);
-        if (stripes) {
+        if (shape.stripes) {
             for (size_t j = 0; j < np; j++) pin_idx[j] = cell_index[(first + j) / n_blobs], pin_bidx[j] = (uint32_t)((first + j) % n_blobs);
         } else {
             memcpy(pin_idx, cell_index + first, 4 * np);
-            memcpy(pin_bidx, blob_index + first, 4 * np);
+            if (n_blobs) memcpy(pin_bidx, blob_index + first, 4 * np);
         }
         memcpy(pin + p.i_val, reinterpret_cast<const uint8_t*>(values) + vb * first, vb * np);
-        for (size_t j = 0; j < np; j++)
-            for (uint32_t lv = 0; lv < depth; lv++) memcpy(pin + p.i_path + 32 * (lv * np + j), paths + pb * (first + j) + 32 * (size_t)lv, 32);
+        for (size_t j = 0; j < np; j++)  // the paths transposed to level-major: the walk's lanes read neighbouring hashes
+            for (uint32_t lv = 0; lv < shape.depth; lv++) memcpy(pin + p.i_path + 32 * (lv * np + j), paths + pb * (first + j) + 32 * (size_t)lv, 32);
         FR_HIP(ctx, hipMemcpyAsync(ctx->arena + p.a_in, pin, p.in_bytes, hipMemcpyHostToDevice, s));
         k::CellsVerifyArgs va;
         va.values = reinterpret_cast<const uint32_t*>(ctx->arena + p.a_in + p.i_val);
@@ -288,82 +124,281 @@ int verify_cells_blobs_device(Ctx* ctx, const uint8_t* commitments, uint32_t n_b
         va.n = log_domain;
         va.log_cell = log_cell;
         va.n_cells = (uint32_t)np;
-        memset(va.commitment, 0, 32);  // (not read: the walk takes the cell's commitment from the table)
-        uint32_t* d_accept = reinterpret_cast<uint32_t*>(ctx->arena + p.a_res + al(4 * np));
         FR_HIP(ctx, hipMemsetAsync(ctx->arena + p.a_res, 0xFF, p.res_bytes, s));  // (a word the kernels did not write is neither 0 nor 1)
-        k::cells_verify_blobs(ctx->launch(), va, reinterpret_cast<const uint32_t*>(ctx->arena + p.a_in + p.i_bidx),
-                              reinterpret_cast<const uint32_t*>(ctx->arena + p.a_com));
-        if (stripes) k::cells_stripe_accept(ctx->launch(), va.status, (uint32_t)p.ns, n_blobs, d_accept);
+        if (n_blobs) {
+            memset(va.commitment, 0, 32);  // (not read: the walk takes the cell's commitment from the table)
+            k::cells_verify_blobs(ctx->launch(), va, reinterpret_cast<const uint32_t*>(ctx->arena + p.a_in + p.i_bidx),
+                                  reinterpret_cast<const uint32_t*>(ctx->arena + p.a_com));
+        } else {
+            memcpy(va.commitment, commitments, 32);
+            k::cells_verify(ctx->launch(), va);
+        }
+        if (shape.stripes) k::cells_stripe_accept(ctx->launch(), va.status, (uint32_t)p.n_stripes, n_blobs, va.status + cells_al(4 * np) / 4);
         FR_HIP(ctx, hipGetLastError());
-        uint32_t* res = reinterpret_cast<uint32_t*>(pin + p.in_bytes);
-        FR_HIP(ctx, hipMemcpyAsync(res, ctx->arena + p.a_res, p.res_bytes, hipMemcpyDeviceToHost, s));
+        const uint32_t* res = reinterpret_cast<const uint32_t*>(pin + p.p_res);
+        FR_HIP(ctx, hipMemcpyAsync(pin + p.p_res, ctx->arena + p.a_res, p.res_bytes, hipMemcpyDeviceToHost, s));
         FR_HIP(ctx, hipStreamSynchronize(s));
         for (size_t j = 0; j < np; j++) {
-            if (res[j] > 1) return ctx->fail(FRIEDA_ERR_INVARIANT, "verify_cells_blobs: the kernel left no status");
+            if (res[j] > 1) return ctx->fail(FRIEDA_ERR_INVARIANT, fn + ": the kernel left no status");
             out_status[first + j] = res[j] ? FRIEDA_CELL_ACCEPTED : FRIEDA_CELL_REJECTED;
         }
-        if (!stripes) continue;
-        // the host keeps the accept words only: they number the pool entries
-        const uint32_t* acc = res + al(4 * np) / 4;
-        uint32_t* tab = reinterpret_cast<uint32_t*>(pin + p.in_bytes + al(p.res_bytes));
+        if (!pool) continue;
+        // what numbers the pool entries: the status words, or the accept words of the stripes
+        const uint32_t* mark = shape.stripes ? res + cells_al(4 * np) / 4 : res;
+        uint32_t* tab = reinterpret_cast<uint32_t*>(pin + p.p_tab);
         uint32_t n_rows = 0;
-        for (size_t t = 0; t < p.ns; t++) {
-            if (acc[t] > 1) return ctx->fail(FRIEDA_ERR_INVARIANT, "verify_cells_blobs: the kernel left no stripe status");
-            if (acc[t]) {
-                tab[2 * n_rows] = (uint32_t)t, tab[2 * n_rows + 1] = (uint32_t)stripes->n++;
+        for (size_t t = 0; t < p.n_rows; t++) {
+            if (mark[t] > 1) return ctx->fail(FRIEDA_ERR_INVARIANT, fn + ": the kernel left no stripe status");
+            if (mark[t]) {
+                tab[2 * n_rows] = (uint32_t)t, tab[2 * n_rows + 1] = (uint32_t)pool->n++;
                 n_rows++;
             }
         }
         if (n_rows) {
-            // (the table sits in the pinned block the next pass overwrites: wait for the copy)
+            const uint32_t* d_tab = reinterpret_cast<const uint32_t*>(ctx->arena + p.a_tab);
             FR_HIP(ctx, hipMemcpyAsync(ctx->arena + p.a_tab, tab, 8 * (size_t)n_rows, hipMemcpyHostToDevice, s));
-            k::cells_stripe_gather(ctx->launch(), reinterpret_cast<const uint32_t*>(ctx->arena + p.a_tab), n_rows, va.values, va.idx, n_blobs, log_cell,
-                                   stripes->d_idx(), stripes->d_val());
+            if (shape.stripes)
+                k::cells_stripe_gather(ctx->launch(), d_tab, n_rows, va.values, va.idx, n_blobs, log_cell, pool->d_idx(), pool->d_val());
+            else
+                k::cells_gather(ctx->launch(), d_tab, n_rows, va.values, va.idx, log_cell, pool->d_idx(), pool->d_val());
             FR_HIP(ctx, hipGetLastError());
-            FR_HIP(ctx, hipStreamSynchronize(s));
+            FR_HIP(ctx, hipStreamSynchronize(s));  // (the table sits in the pinned block the next pass overwrites: wait for the copy)
         }
     }
     return FRIEDA_OK;
 }
 
-int open_cells_blobs(Ctx* ctx, const Encoded* const* encs, uint32_t n_blobs, uint32_t log_cell, const uint32_t* blob_index, const uint32_t* cell_index,
-                     uint32_t n_cells, uint32_t* out_values, uint8_t* out_paths) {
-    FR_NO_JOB(ctx);
+// Provider: cell i is cell cell_index[i] of encs[blob_index[i]] — or, blob_index null, of encs[0]: then the indices alone are staged and
+// the single-blob kernels run.  One upload (indices, and with blob numbers those and a table row per blob: evaluation, tree, skip
+// threshold), the launches, one download (values | paths), one synchronisation.
+int open_cells(Ctx* ctx, const Encoded* const* encs, uint32_t n_blobs, uint32_t log_cell, const uint32_t* blob_index, const uint32_t* cell_index,
+               uint32_t n_cells, uint32_t* out_values, uint8_t* out_paths) {
     const uint32_t n = encs[0]->n;
     FR_HIP(ctx, hipSetDevice(ctx->device));
     const size_t ib = 4 * (size_t)n_cells, tb = sizeof(k::CellsBlobRow) * (size_t)n_blobs;
     const size_t vb = ((size_t)16 << log_cell) * n_cells, pb = 32 * (size_t)(n - log_cell) * n_cells;
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t i_bidx = al(ib), i_tab = i_bidx + al(ib), in_bytes = i_tab + al(tb);  // indices | blob numbers | table: one upload
+    const size_t i_bidx = cells_al(ib), i_tab = i_bidx + cells_al(ib), in_bytes = blob_index ? i_tab + cells_al(tb) : cells_al(ib);
     ArenaPlan ap;
-    const size_t a_in = ap.take(in_bytes), a_out = ap.take(al(vb) + pb);  // values | paths: one download
+    const size_t a_in = ap.take(in_bytes), a_out = ap.take(cells_al(vb) + pb);
     int rc = ctx->ensure_arena(ap.off);
     if (rc) return rc;
-    rc = ensure_pinned(ctx, in_bytes + al(vb) + pb);
+    rc = ensure_pinned(ctx, in_bytes + cells_al(vb) + pb);
     if (rc) return rc;
     hipStream_t s = ctx->stream;
     uint8_t* pin = static_cast<uint8_t*>(ctx->pinned);
     memcpy(pin, cell_index, ib);
-    memcpy(pin + i_bidx, blob_index, ib);
-    k::CellsBlobRow* rows = reinterpret_cast<k::CellsBlobRow*>(pin + i_tab);
-    for (uint32_t b = 0; b < n_blobs; b++) rows[b] = k::CellsBlobRow{encs[b]->eval(), encs[b]->tree(), encs[b]->skip_log, 0};
-    FR_HIP(ctx, hipMemcpyAsync(ctx->arena + a_in, pin, in_bytes, hipMemcpyHostToDevice, s));
-    k::CellsOpenBlobsArgs oa;
-    oa.table = reinterpret_cast<const k::CellsBlobRow*>(ctx->arena + a_in + i_tab);
-    oa.bidx = reinterpret_cast<const uint32_t*>(ctx->arena + a_in + i_bidx);
-    oa.idx = reinterpret_cast<const uint32_t*>(ctx->arena + a_in);
-    oa.n = n;
-    oa.log_cell = log_cell;
-    oa.n_cells = n_cells;
-    oa.out_values = reinterpret_cast<uint32_t*>(ctx->arena + a_out);
-    oa.out_paths = reinterpret_cast<uint4*>(ctx->arena + a_out + al(vb));
-    k::cells_open_blobs(ctx->launch(), oa);
+    uint32_t* d_out = reinterpret_cast<uint32_t*>(ctx->arena + a_out);
+    uint4* d_paths = reinterpret_cast<uint4*>(ctx->arena + a_out + cells_al(vb));
+    const uint32_t* d_idx = reinterpret_cast<const uint32_t*>(ctx->arena + a_in);
+    if (blob_index) {
+        memcpy(pin + i_bidx, blob_index, ib);
+        k::CellsBlobRow* rows = reinterpret_cast<k::CellsBlobRow*>(pin + i_tab);
+        for (uint32_t b = 0; b < n_blobs; b++) rows[b] = k::CellsBlobRow{encs[b]->eval(), encs[b]->tree(), encs[b]->skip_log, 0};
+        FR_HIP(ctx, hipMemcpyAsync(ctx->arena + a_in, pin, in_bytes, hipMemcpyHostToDevice, s));
+        k::cells_open_blobs(ctx->launch(), k::CellsOpenBlobsArgs{reinterpret_cast<const k::CellsBlobRow*>(ctx->arena + a_in + i_tab),
+                                                                 reinterpret_cast<const uint32_t*>(ctx->arena + a_in + i_bidx), d_idx, n, log_cell, n_cells,
+                                                                 d_out, d_paths});
+    } else {
+        FR_HIP(ctx, hipMemcpyAsync(ctx->arena + a_in, pin, ib, hipMemcpyHostToDevice, s));
+        k::cells_open(ctx->launch(), k::CellsOpenArgs{encs[0]->eval(), encs[0]->tree(), n, log_cell, encs[0]->skip_log, n_cells, d_idx, d_out, d_paths});
+    }
     FR_HIP(ctx, hipGetLastError());
-    FR_HIP(ctx, hipMemcpyAsync(pin + in_bytes, ctx->arena + a_out, al(vb) + pb, hipMemcpyDeviceToHost, s));
+    FR_HIP(ctx, hipMemcpyAsync(pin + in_bytes, ctx->arena + a_out, cells_al(vb) + pb, hipMemcpyDeviceToHost, s));
     FR_HIP(ctx, hipStreamSynchronize(s));
     memcpy(out_values, pin + in_bytes, vb);
-    if (pb) memcpy(out_paths, pin + in_bytes + al(vb), pb);
+    if (pb) memcpy(out_paths, pin + in_bytes + cells_al(vb), pb);
     return FRIEDA_OK;
 }
 
+constexpr uint32_t CELLS_MAX_BLOBS = 65536, STRIPES_MAX_BLOBS = 256;  // (the point reconstruction takes at most 1024 columns)
+// the argument rule the three (blob, cell) pair calls share; null when it holds
+const char* cells_blobs_args_error(uint32_t n_blobs, uint32_t log_domain, uint32_t log_cell, const uint32_t* blob_index, const uint32_t* cell_index,
+                                   uint32_t n_cells) {
+    if (n_blobs == 0 || n_blobs > CELLS_MAX_BLOBS) return "n_blobs out of range";
+    for (uint32_t i = 0; i < n_cells; i++)
+        if (blob_index[i] >= n_blobs) return "blob index out of range";
+    return cells_args_error(log_domain, log_cell, cell_index, n_cells);
+}
+
+}  // namespace
+
+const char* cells_args_error(uint32_t log_domain, uint32_t log_cell, const uint32_t* cell_index, uint32_t n_cells) {
+    if (log_domain > FRIEDA_MAX_LOG_DOMAIN) return "log_domain out of range";
+    if (log_cell > log_domain || log_cell > FRIEDA_MAX_LOG_OPEN_CELL) return "log_cell out of range";
+    const uint32_t bits = log_domain - log_cell;
+    for (uint32_t i = 0; i < n_cells; i++)
+        if (((uint64_t)cell_index[i] >> bits) != 0) return "cell index out of range";
+    return nullptr;
+}
+
 }  // namespace frieda
+
+using namespace frieda;
+
+extern "C" {
+int frieda_open_cells(frieda_ctx* ctx, const frieda_encoded* enc, uint32_t log_cell, const uint32_t* cell_index, uint32_t n_cells,
+                      uint32_t* out_values, uint8_t* out_paths) {
+    if (!ctx || !enc) return FRIEDA_ERR_ARG;
+    if (n_cells == 0) return FRIEDA_OK;
+    if (!cell_index || !out_values || (!out_paths && log_cell != enc->e.n)) return FRIEDA_ERR_ARG;
+    if (const char* bad = cells_args_error(enc->e.n, log_cell, cell_index, n_cells)) return ctx->c.fail(FRIEDA_ERR_ARG, std::string("open_cells: ") + bad);
+    FR_GUARD_BEGIN
+    FR_NO_JOB(&ctx->c);
+    if (ctx->c.device != enc->e.device) return ctx->c.fail(FRIEDA_ERR_ARG, "open_cells: the context is not on the encoded blob's device");
+    const Encoded* const one = &enc->e;
+    return open_cells(&ctx->c, &one, 1, log_cell, nullptr, cell_index, n_cells, out_values, out_paths);
+    FR_GUARD_END(ctx)
+}
+
+int frieda_verify_cells(const uint8_t commitment[32], uint32_t log_domain, uint32_t log_cell, const uint32_t* cell_index, uint32_t n_cells,
+                        const uint32_t* values, const uint8_t* paths, uint8_t* out_status) {
+    if (n_cells == 0) return FRIEDA_OK;
+    if (!commitment || !cell_index || !values || !out_status) return FRIEDA_ERR_ARG;
+    if (cells_args_error(log_domain, log_cell, cell_index, n_cells) || (!paths && log_cell != log_domain)) return FRIEDA_ERR_ARG;
+    try {
+        verify_cells_host(commitment, log_domain, log_cell, nullptr, cell_index, n_cells, values, paths, out_status);
+    } catch (const std::bad_alloc&) {
+        return FRIEDA_ERR_NOMEM;
+    }
+    return FRIEDA_OK;
+}
+
+int frieda_verify_cells_many(frieda_ctx* ctx, const uint8_t commitment[32], uint32_t log_domain, uint32_t log_cell, const uint32_t* cell_index,
+                             uint32_t n_cells, const uint32_t* values, const uint8_t* paths, uint8_t* out_status) {
+    if (!ctx) return FRIEDA_ERR_ARG;
+    if (n_cells == 0) return FRIEDA_OK;
+    if (!commitment || !cell_index || !values || !out_status || (!paths && log_cell != log_domain)) return FRIEDA_ERR_ARG;
+    if (const char* bad = cells_args_error(log_domain, log_cell, cell_index, n_cells)) return ctx->c.fail(FRIEDA_ERR_ARG, std::string("verify_cells_many: ") + bad);
+    FR_NO_JOB(&ctx->c);
+    FR_GUARD_BEGIN
+    return verify_cells_passes(&ctx->c, commitment, 0, log_domain, log_cell, nullptr, cell_index, n_cells, values, paths, out_status, nullptr);
+    FR_GUARD_END(ctx)
+}
+
+int frieda_reconstruct_from_opened_cells(frieda_ctx* ctx, const uint8_t commitment[32], uint32_t log_blowup_factor, size_t len, uint32_t log_cell,
+                                         const uint32_t* cell_index, uint32_t n_cells, const uint32_t* values, const uint8_t* paths,
+                                         uint8_t* out_bytes, uint8_t* out_status, size_t* n_cells_used) {
+    if (!ctx || !commitment || !n_cells_used || (len && !out_bytes) || (n_cells && (!cell_index || !values || !out_status))) return FRIEDA_ERR_ARG;
+    *n_cells_used = 0;
+    if (log_blowup_factor > FRIEDA_MAX_LOG_DOMAIN || len > ((size_t)1 << 40)) return ctx->c.fail(FRIEDA_ERR_ARG, "reconstruct_from_opened_cells: shape out of range");
+    const uint32_t L = codec_shape(len).log_size, n = L + log_blowup_factor;
+    if (L < 1 || n < 2 || n + 1 > FRIEDA_MAX_LOG_DOMAIN) return ctx->c.fail(FRIEDA_ERR_ARG, "reconstruct_from_opened_cells: shape out of range");
+    if (const char* bad = cells_args_error(n, log_cell, cell_index, n_cells)) return ctx->c.fail(FRIEDA_ERR_ARG, std::string("reconstruct_from_opened_cells: ") + bad);
+    if (n_cells && !paths && log_cell != n) return FRIEDA_ERR_ARG;
+    FR_NO_JOB(&ctx->c);
+    FR_GUARD_BEGIN
+    const size_t need = log_cell ? (((size_t)1 << L) >> log_cell) + 1 : ((size_t)1 << L) + 2;
+    uint32_t nd = 0;
+    auto too_few = [&]() {
+        return ctx->c.fail(FRIEDA_ERR_ARG, std::to_string(nd) + " distinct accepted cells, " + std::to_string(need) + " needed");
+    };
+    if (n_cells == 0) return too_few();
+    CellPool pool;
+    int rc = verify_cells_passes(&ctx->c, commitment, 0, n, log_cell, nullptr, cell_index, n_cells, values, paths, out_status, &pool);
+    if (rc != FRIEDA_OK) return rc;
+    if (pool.n == 0) return too_few();
+    return rebuild_blob(ctx, len, log_blowup_factor, commitment, "the rebuilt blob does not commit to the commitment (wrong len?)", out_bytes, [&](uint8_t* d_out) {
+        rc = reconstruct_pooled(ctx, pool.d_val(), pool.d_idx(), (uint32_t)pool.n, 1, log_cell, L, n, len, d_out, 0, &nd);
+        *n_cells_used = nd;
+        return rc == FRIEDA_ERR_ARG && nd < need ? too_few() : rc;
+    });
+    FR_GUARD_END(ctx)
+}
+
+// ---- the cells of many blobs of one shape in one call ----
+int frieda_open_cells_blobs(frieda_ctx* ctx, const frieda_encoded* const* encs, uint32_t n_blobs, uint32_t log_cell, const uint32_t* blob_index,
+                            const uint32_t* cell_index, uint32_t n_cells, uint32_t* out_values, uint8_t* out_paths) {
+    if (!ctx || !encs || n_blobs == 0 || n_blobs > CELLS_MAX_BLOBS) return FRIEDA_ERR_ARG;
+    for (uint32_t b = 0; b < n_blobs; b++)
+        if (!encs[b]) return FRIEDA_ERR_ARG;
+    FR_GUARD_BEGIN
+    const uint32_t n = encs[0]->e.n;
+    std::vector<const Encoded*> blobs(n_blobs);
+    for (uint32_t b = 0; b < n_blobs; b++) {
+        if (encs[b]->e.n != n) return ctx->c.fail(FRIEDA_ERR_ARG, "open_cells_blobs: the blobs of a call must have one log_domain");
+        if (encs[b]->e.device != ctx->c.device) return ctx->c.fail(FRIEDA_ERR_ARG, "open_cells_blobs: the context is not on the encoded blobs' device");
+        blobs[b] = &encs[b]->e;
+    }
+    if (n_cells == 0) return FRIEDA_OK;
+    if (!blob_index || !cell_index || !out_values || (!out_paths && log_cell != n)) return FRIEDA_ERR_ARG;
+    if (const char* bad = cells_blobs_args_error(n_blobs, n, log_cell, blob_index, cell_index, n_cells))
+        return ctx->c.fail(FRIEDA_ERR_ARG, std::string("open_cells_blobs: ") + bad);
+    FR_NO_JOB(&ctx->c);
+    return open_cells(&ctx->c, blobs.data(), n_blobs, log_cell, blob_index, cell_index, n_cells, out_values, out_paths);
+    FR_GUARD_END(ctx)
+}
+
+int frieda_verify_cells_blobs(const uint8_t* commitments, uint32_t n_blobs, uint32_t log_domain, uint32_t log_cell, const uint32_t* blob_index,
+                              const uint32_t* cell_index, uint32_t n_cells, const uint32_t* values, const uint8_t* paths, uint8_t* out_status) {
+    if (n_cells == 0) return FRIEDA_OK;
+    if (!commitments || !blob_index || !cell_index || !values || !out_status) return FRIEDA_ERR_ARG;
+    if (cells_blobs_args_error(n_blobs, log_domain, log_cell, blob_index, cell_index, n_cells) || (!paths && log_cell != log_domain)) return FRIEDA_ERR_ARG;
+    try {
+        verify_cells_host(commitments, log_domain, log_cell, blob_index, cell_index, n_cells, values, paths, out_status);
+    } catch (const std::bad_alloc&) {
+        return FRIEDA_ERR_NOMEM;
+    }
+    return FRIEDA_OK;
+}
+
+int frieda_verify_cells_blobs_many(frieda_ctx* ctx, const uint8_t* commitments, uint32_t n_blobs, uint32_t log_domain, uint32_t log_cell,
+                                   const uint32_t* blob_index, const uint32_t* cell_index, uint32_t n_cells, const uint32_t* values, const uint8_t* paths,
+                                   uint8_t* out_status) {
+    if (!ctx) return FRIEDA_ERR_ARG;
+    if (n_cells == 0) return FRIEDA_OK;
+    if (!commitments || !blob_index || !cell_index || !values || !out_status || (!paths && log_cell != log_domain)) return FRIEDA_ERR_ARG;
+    if (const char* bad = cells_blobs_args_error(n_blobs, log_domain, log_cell, blob_index, cell_index, n_cells))
+        return ctx->c.fail(FRIEDA_ERR_ARG, std::string("verify_cells_blobs_many: ") + bad);
+    FR_NO_JOB(&ctx->c);
+    FR_GUARD_BEGIN
+    return verify_cells_passes(&ctx->c, commitments, n_blobs, log_domain, log_cell, blob_index, cell_index, n_cells, values, paths, out_status, nullptr);
+    FR_GUARD_END(ctx)
+}
+
+int frieda_reconstruct_blobs_from_opened_stripes(frieda_ctx* ctx, const uint8_t* commitments, uint32_t n_blobs, uint32_t log_blowup_factor, size_t len,
+                                                 uint32_t log_cell, const uint32_t* stripe_index, uint32_t n_stripes, const uint32_t* values,
+                                                 const uint8_t* paths, uint8_t* out_bytes, uint8_t* out_status, size_t* n_stripes_used) {
+    if (!ctx || !commitments || !n_stripes_used || (len && !out_bytes) || (n_stripes && (!stripe_index || !values || !out_status))) return FRIEDA_ERR_ARG;
+    *n_stripes_used = 0;
+    const char* const fn = "reconstruct_blobs_from_opened_stripes: ";
+    if (n_blobs == 0 || n_blobs > STRIPES_MAX_BLOBS) return ctx->c.fail(FRIEDA_ERR_ARG, std::string(fn) + "n_blobs out of range (1 .. 256)");
+    if (log_blowup_factor > FRIEDA_MAX_LOG_DOMAIN || len > ((size_t)1 << 40)) return ctx->c.fail(FRIEDA_ERR_ARG, std::string(fn) + "shape out of range");
+    const uint32_t L = codec_shape(len).log_size, n = L + log_blowup_factor;
+    if (L < 1 || n < 2 || n + 1 > FRIEDA_MAX_LOG_DOMAIN) return ctx->c.fail(FRIEDA_ERR_ARG, std::string(fn) + "shape out of range");
+    if (const char* bad = cells_args_error(n, log_cell, stripe_index, n_stripes)) return ctx->c.fail(FRIEDA_ERR_ARG, std::string(fn) + bad);
+    if (n_stripes && !paths && log_cell != n) return FRIEDA_ERR_ARG;
+    // the staged values are the point reconstruction's sample buffer: at most 2^32 words (its positions are 32-bit)
+    if ((uint64_t)n_stripes * n_blobs > (0x100000000ull >> (log_cell + 2))) return ctx->c.fail(FRIEDA_ERR_ARG, std::string(fn) + "more than 2^32 value words");
+    FR_NO_JOB(&ctx->c);
+    FR_GUARD_BEGIN
+    const size_t need = log_cell ? (((size_t)1 << L) >> log_cell) + 1 : ((size_t)1 << L) + 2;
+    uint32_t nd = 0;
+    auto too_few = [&]() {
+        return ctx->c.fail(FRIEDA_ERR_ARG, std::to_string(nd) + " distinct fully accepted stripes, " + std::to_string(need) + " needed");
+    };
+    if (n_stripes == 0) return too_few();
+    CellPool pool;
+    int rc = verify_cells_passes(&ctx->c, commitments, n_blobs, n, log_cell, nullptr, stripe_index, n_stripes * n_blobs, values, paths, out_status, &pool);
+    if (rc != FRIEDA_OK) return rc;
+    if (pool.n == 0) return too_few();
+    // the rebuilt bytes stay on the device for the commitment check: blob b at b * stride
+    const size_t stride = std::max<size_t>(256, (len + 255) & ~(size_t)255);
+    std::vector<uint8_t> roots(32 * (size_t)n_blobs), bytes(len * n_blobs);
+    DevBuf out;
+    rc = out.alloc(&ctx->c, stride * n_blobs, "poison(rebuilt bytes)");
+    if (rc != FRIEDA_OK) return rc;
+    uint8_t* d_out = static_cast<uint8_t*>(out.p);
+    rc = reconstruct_pooled(ctx, pool.d_val(), pool.d_idx(), (uint32_t)pool.n, n_blobs, log_cell, L, n, len, d_out, stride, &nd);
+    *n_stripes_used = nd;
+    if (rc == FRIEDA_OK) rc = commit_batch(&ctx->c, d_out, stride, len, n_blobs, true, log_blowup_factor, roots.data());
+    if (rc == FRIEDA_OK && len && hipMemcpy2D(bytes.data(), len, d_out, stride, len, n_blobs, hipMemcpyDeviceToHost) != hipSuccess)
+        rc = ctx->c.hip_fail(hipGetLastError(), "hipMemcpy2D(rebuilt bytes)");
+    (void)hipStreamSynchronize(ctx->c.stream);  // (before the buffer goes, on the error paths too)
+    out.release();
+    if (rc == FRIEDA_ERR_ARG && nd < need) return too_few();
+    if (rc != FRIEDA_OK) return rc;
+    return rebuilt_accept(&ctx->c, roots.data(), commitments, n_blobs, nullptr, bytes, out_bytes);
+    FR_GUARD_END(ctx)
+}
+
+}  // extern "C"

@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include <array>
+#include <functional>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -150,6 +151,51 @@ struct ArenaPlan {
     }
 };
 
+// Device memory of one call (pools, rebuilt bytes): freed when it leaves scope, whichever way.  Not for what outlives a call (Encoded, the
+// arena, the twiddle sets: they have their own owners).  The destructor does not wait for the stream: a path that launched work on
+// the buffer synchronises before it lets go.
+struct DevBuf {
+    void* p = nullptr;
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept : p(o.p) { o.p = nullptr; }
+    DevBuf& operator=(DevBuf&& o) noexcept {
+        std::swap(p, o.p);
+        return *this;
+    }
+    ~DevBuf() { release(); }
+    void release() {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+    }
+    // hipMalloc + poison_fresh; poison_what: the text of a failed poison fill (test hook)
+    int alloc(Ctx* ctx, size_t bytes, const char* poison_what) {
+        release();
+        const hipError_t e = hipMalloc(&p, bytes);
+        if (e != hipSuccess) {
+            p = nullptr;
+            (void)hipGetLastError();  // (not sticky for the next call)
+            ctx->err = std::string("hipMalloc: ") + hipGetErrorString(e);
+            return FRIEDA_ERR_NOMEM;
+        }
+        if (const hipError_t pe = ctx->poison_fresh(p, bytes); pe != hipSuccess) return ctx->hip_fail(pe, poison_what);
+        return FRIEDA_OK;
+    }
+};
+
+// A call's pool of verified samples on the device, in the layout the point reconstruction reads: an index block (256-byte rounded),
+// then `entry_bytes` of values per entry.  Outside the arena: the verify passes and the reconstruction re-plan that.
+struct DevPool {
+    DevBuf buf;
+    size_t cap = 0, n = 0;  // entries allocated / pooled
+    static size_t index_bytes(size_t cap) { return (4 * cap + 255) & ~(size_t)255; }
+    uint32_t* d_idx() const { return static_cast<uint32_t*>(buf.p); }
+    uint32_t* d_val() const { return reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(buf.p) + index_bytes(cap)); }
+    int alloc(Ctx* ctx, size_t entries, size_t entry_bytes, const char* poison_what) {
+        cap = entries;
+        return buf.alloc(ctx, index_bytes(cap) + entry_bytes * cap, poison_what);
+    }
+};
+
 // the size of Ctx::pinned_in (prover.cpp)
 constexpr size_t SMALL_HOST_IN_BYTES = 7680;  // 15 << 9: up to 32 workgroups read the block over PCIe; larger small blobs are copied to the device first
 // the pinned staging block (Ctx::pinned) of at least `bytes` (reallocated when smaller; callers hold no job: FR_NO_JOB)
@@ -237,22 +283,15 @@ struct PairPoints {
 int verify(const ProofData& proof, const uint64_t* seed, int* ok, std::vector<uint32_t>* out_queries = nullptr, PairPoints* out_pairs = nullptr);
 
 // Pairs mode of verify_many (frieda_verify_pairs_many, frieda_reconstruct_from_proof_pairs): the pair points of every accepted proof, pooled
-// in the caller's order.  The kernel's proofs leave theirs in a device allocation of the call's own (not the arena: the verify passes
-// and the reconstruction re-plan it), gathered there pass by pass (k::verify_pairs_gather); host-route proofs keep theirs in `host`
-// until upload_host_rows.  Entry e: d_pos()[e], d_val()[4 e .. 4 e + 3] — the cell layout of the point reconstruction (log_cell 0).
-struct PairPool {
-    uint8_t* d = nullptr;
-    size_t cap = 0, n = 0;            // entries allocated / pooled
+// in the caller's order.  The kernel's proofs leave theirs in the pool's device allocation, gathered there pass by pass
+// (k::verify_pairs_gather); host-route proofs keep theirs in `host` until upload_host_rows.  Entry e: d_pos()[e], d_val()[4 e .. 4 e + 3]
+// — the cell layout of the point reconstruction (log_cell 0).
+struct PairPool : DevPool {
     std::vector<size_t> off;          // per proof: its first entry
     std::vector<uint32_t> cnt;        // per proof: its entries (0 unless accepted)
     std::vector<PairPoints> host;     // per proof: the points of an accepted host-route proof
-    uint32_t* d_pos() const { return reinterpret_cast<uint32_t*>(d); }
-    uint32_t* d_val() const { return reinterpret_cast<uint32_t*>(d + ((4 * cap + 255) & ~(size_t)255)); }
+    uint32_t* d_pos() const { return d_idx(); }
     int upload_host_rows(Ctx* ctx);   // synchronous; a no-op without host-route proofs
-    PairPool() = default;
-    PairPool(const PairPool&) = delete;
-    PairPool& operator=(const PairPool&) = delete;
-    ~PairPool();
 };
 // Many proofs in one call (verify_many.cpp, verify.hip): out_status[i] = a k::VerifyStatus, per proof the result of verify() whatever the
 // route (device passes for the shapes the kernel takes, from Tuning::verify_device_min eligible proofs on; verify() for the rest).
@@ -261,63 +300,30 @@ struct PairPool {
 // pairs (optional, with samples): the pairs mode above.
 int verify_many(Ctx* ctx, const ProofData* const* proofs, const uint64_t* seeds, uint32_t count, const uint8_t* expected_commitment, bool samples,
                 uint8_t* out_status, std::vector<std::vector<uint32_t>>* positions, PairPool* pairs = nullptr);
-// frieda_reconstruct_points_device (log_cell 0, 4 columns) with the positions already on the device: d_index[n_points] next to
-// d_cells[n_points][4].  *n_distinct receives the number of distinct positions whenever the call got as far as counting them (it is
-// what decides the "fewer than 2^log_coef + 2" error); count_distinct_points stops there.
-int reconstruct_points_pooled(frieda_ctx* ctx, const uint32_t* d_cells, const uint32_t* d_index, uint32_t n_points, uint32_t log_coef, uint32_t log_domain,
-                              size_t len, void* d_out_bytes, uint32_t* n_distinct);
+// The point reconstruction with the pool already on the device, outside the arena: d_index[n_entries] next to
+// d_cells[n_entries][n_blobs][4][2^log_cell] — ONE reconstruction over 4 * n_blobs columns (one locator for all of them), then blob b
+// packed to d_out_bytes + b * out_stride.  Pair points: (n_blobs 1, log_cell 0); the cells of a blob: (n_blobs 1); stripes: n_blobs <= 256.
+// *n_distinct receives the number of distinct entries whenever the call got as far as counting them (it is what decides the "too few"
+// errors); count_distinct_points stops there.
+int reconstruct_pooled(frieda_ctx* ctx, const uint32_t* d_cells, const uint32_t* d_index, uint32_t n_entries, uint32_t n_blobs, uint32_t log_cell,
+                       uint32_t log_coef, uint32_t log_domain, size_t len, uint8_t* d_out_bytes, size_t out_stride, uint32_t* n_distinct);
 int count_distinct_points(frieda_ctx* ctx, const uint32_t* d_index, uint32_t n_points, uint32_t log_domain, uint32_t* n_distinct);
+// The tail of the single-blob rebuilds (from proofs, proof pairs, opened cells): a DevBuf of `len` bytes, rebuild(d_out) — the
+// reconstruction, which also turns its "too few" into the caller's words —, download, commit_host, rebuilt_accept.  The stream is
+// drained before the buffer is released, whatever rebuild returned.
+int rebuild_blob(frieda_ctx* ctx, size_t len, uint32_t log_blowup, const uint8_t commitment[32], const char* mismatch, uint8_t* out_bytes,
+                 const std::function<int(uint8_t* d_out)>& rebuild);
+// roots[n_blobs][32] against commitments[n_blobs][32], then `bytes` to out_bytes.  mismatch: the error of a single blob; null: blob b's
+int rebuilt_accept(Ctx* ctx, const uint8_t* roots, const uint8_t* commitments, uint32_t n_blobs, const char* mismatch, const std::vector<uint8_t>& bytes,
+                   uint8_t* out_bytes);
 
-// The same with whole cells of 2^log_cell entries as the pool (frieda_reconstruct_from_opened_cells): d_cells[n_cells][4][2^log_cell] next to
-// d_index[n_cells], both on the device and outside the arena.
-int reconstruct_cells_pooled(frieda_ctx* ctx, const uint32_t* d_cells, const uint32_t* d_index, uint32_t n_cells, uint32_t log_cell, uint32_t log_coef,
-                             uint32_t log_domain, size_t len, void* d_out_bytes, uint32_t* n_distinct);
-
-// ---- authenticated cells (cells_host.cpp, cells.hip) ----
-// The accepted cells of a frieda_reconstruct_from_opened_cells call, in the caller's order, in a device allocation of the call's own
-// (not the arena: the verify passes and the reconstruction re-plan it).  Entry e: d_idx()[e], d_val()[e][4][2^log_cell] — the cell
-// layout of the point reconstruction.
-struct CellPool {
-    uint8_t* d = nullptr;
-    size_t cap = 0, n = 0;  // entries allocated / pooled
-    uint32_t log_cell = 0;
-    uint32_t* d_idx() const { return reinterpret_cast<uint32_t*>(d); }
-    uint32_t* d_val() const { return reinterpret_cast<uint32_t*>(d + ((4 * cap + 255) & ~(size_t)255)); }
-    CellPool() = default;
-    CellPool(const CellPool&) = delete;
-    CellPool& operator=(const CellPool&) = delete;
-    ~CellPool();
-};
+// ---- authenticated cells (cells_host.cpp, cells.hip; the exports are in cells_host.cpp) ----
+// The accepted cells (or fully accepted stripes) of a rebuild call, in the caller's order.  Entry e: d_idx()[e],
+// d_val()[e][group][4][2^log_cell], group = 1, or the blobs of a stripe.
+struct CellPool : DevPool {};
 // the argument rule of every cells entry point: log_cell <= min(log_domain, FRIEDA_MAX_LOG_OPEN_CELL), every index < 2^(log_domain - log_cell);
 // null when it holds, else what is wrong
 const char* cells_args_error(uint32_t log_domain, uint32_t log_cell, const uint32_t* cell_index, uint32_t n_cells);
-// one status byte per cell (FRIEDA_CELL_*): every word a canonical M31 and the subtree root, carried up the path, equal to the commitment.
-// values[n_cells][4][2^log_cell], paths[n_cells][log_domain - log_cell][32] bottom-up.  Arguments already checked (cells_args_error).
-void verify_cells_host(const uint8_t commitment[32], uint32_t log_domain, uint32_t log_cell, const uint32_t* cell_index, uint32_t n_cells,
-                       const uint32_t* values, const uint8_t* paths, uint8_t* out_status);
-// the same status bytes from the kernels, staged in passes; pool (optional): receives the accepted cells.  Uses the arena and the pinned
-// block (callers: FR_NO_JOB).
-int verify_cells_device(Ctx* ctx, const uint8_t commitment[32], uint32_t log_domain, uint32_t log_cell, const uint32_t* cell_index, uint32_t n_cells,
-                        const uint32_t* values, const uint8_t* paths, uint8_t* out_status, CellPool* pool);
-// cells of an encoded blob with their paths: one upload of the indices, the launches, one download, one synchronisation
-int open_cells(Ctx* ctx, const Encoded& enc, uint32_t log_cell, const uint32_t* cell_index, uint32_t n_cells, uint32_t* out_values, uint8_t* out_paths);
-// ---- the cells of many blobs of one shape in one call: cell i is cell cell_index[i] of blob blob_index[i] (arguments already checked) ----
-// host verifier: commitments[n_blobs][32]
-void verify_cells_blobs_host(const uint8_t* commitments, uint32_t log_domain, uint32_t log_cell, const uint32_t* blob_index, const uint32_t* cell_index,
-                             uint32_t n_cells, const uint32_t* values, const uint8_t* paths, uint8_t* out_status);
-// device verifier, staged in passes as verify_cells_device; the commitments are uploaded once.  stripes (optional): the cells are
-// [n_cells / n_blobs][n_blobs] — stripe t is cell cell_index[t] of every blob, blob_index is not read — the passes are cut at stripe
-// boundaries and the stripes whose cells are ALL accepted are gathered into it: entry e: d_idx()[e], d_val()[e][n_blobs][4][2^log_cell].
-int verify_cells_blobs_device(Ctx* ctx, const uint8_t* commitments, uint32_t n_blobs, uint32_t log_domain, uint32_t log_cell, const uint32_t* blob_index,
-                              const uint32_t* cell_index, uint32_t n_cells, const uint32_t* values, const uint8_t* paths, uint8_t* out_status,
-                              CellPool* stripes);
-// provider: one upload (indices, blob numbers, a table row per blob), the launches, one download, one synchronisation; skip_log is per blob
-int open_cells_blobs(Ctx* ctx, const Encoded* const* encs, uint32_t n_blobs, uint32_t log_cell, const uint32_t* blob_index, const uint32_t* cell_index,
-                     uint32_t n_cells, uint32_t* out_values, uint8_t* out_paths);
-// n_blobs blobs from a pool of stripes (d_cells[n_stripes][n_blobs][4][2^log_cell] next to d_index[n_stripes], outside the arena): ONE point
-// reconstruction over 4 * n_blobs columns — one locator for all of them — then blob b packed to d_out_bytes + b * out_stride.
-int reconstruct_stripes_pooled(frieda_ctx* ctx, const uint32_t* d_cells, const uint32_t* d_index, uint32_t n_stripes, uint32_t n_blobs, uint32_t log_cell,
-                               uint32_t log_coef, uint32_t log_domain, size_t len, uint8_t* d_out_bytes, size_t out_stride, uint32_t* n_distinct);
 
 // transcript pieces shared by prover and verifier (transcript.cpp)
 void channel_mix_felts(Channel& ch, const std::vector<QM31>& felts);

@@ -438,6 +438,7 @@ struct CellsOpenBlobsArgs {
 };
 void cells_open_blobs(const Launch& L, const CellsOpenBlobsArgs& a);
 // cells_verify with lane `cell` compared against d_commitments[d_bidx[cell]] (8 words per blob, in device memory); a.commitment is not read
+// (the same kernels: cells.hip instantiates them for the one source and for the table)
 void cells_verify_blobs(const Launch& L, const CellsVerifyArgs& a, const uint32_t* d_bidx, const uint32_t* d_commitments);
 // Stripes: the cells of a pass are [n_stripes][n_blobs].  d_accept[s] = 1 iff all n_blobs status words of stripe s are 1, else 0.
 void cells_stripe_accept(const Launch& L, const uint32_t* d_status, uint32_t n_stripes, uint32_t n_blobs, uint32_t* d_accept);

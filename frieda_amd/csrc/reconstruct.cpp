@@ -453,49 +453,47 @@ int frieda_reconstruct_points_device(frieda_ctx* ctx, const uint32_t* d_cells, c
 
 namespace frieda {
 
-int reconstruct_points_pooled(frieda_ctx* ctx, const uint32_t* d_cells, const uint32_t* d_index, uint32_t n_points, uint32_t log_coef, uint32_t log_domain,
-                              size_t len, void* d_out_bytes, uint32_t* n_distinct) {
-    if (!ctx || !d_cells || !d_index || !n_distinct || (len && !d_out_bytes) || n_points == 0 || log_coef > FRIEDA_MAX_LOG_DOMAIN) return FRIEDA_ERR_ARG;
-    const size_t n_felts = (size_t)4 << log_coef;
-    if ((8 * len + 29) / 30 > n_felts) return ctx->c.fail(FRIEDA_ERR_ARG, "len does not fit the polynomial");
-    FR_HIP(&ctx->c, hipSetDevice(ctx->c.device));
-    const size_t coef_bytes = (sizeof(uint32_t) * n_felts + 255) & ~(size_t)255;
-    int rc = interpolate_points(ctx, d_cells, nullptr, n_points, 4, 0, log_coef, log_domain, nullptr, coef_bytes, d_index, n_distinct);
-    if (rc) return rc;
-    k::pack30(ctx->c.launch(), reinterpret_cast<const uint32_t*>(ctx->c.arena), n_felts, static_cast<uint8_t*>(d_out_bytes), len);
-    FR_HIP(&ctx->c, hipGetLastError());
-    return FRIEDA_OK;
-}
-
-int reconstruct_cells_pooled(frieda_ctx* ctx, const uint32_t* d_cells, const uint32_t* d_index, uint32_t n_cells, uint32_t log_cell, uint32_t log_coef,
-                             uint32_t log_domain, size_t len, void* d_out_bytes, uint32_t* n_distinct) {
-    if (!ctx || !d_cells || !d_index || !n_distinct || (len && !d_out_bytes) || n_cells == 0 || log_coef > FRIEDA_MAX_LOG_DOMAIN) return FRIEDA_ERR_ARG;
-    const size_t n_felts = (size_t)4 << log_coef;
-    if ((8 * len + 29) / 30 > n_felts) return ctx->c.fail(FRIEDA_ERR_ARG, "len does not fit the polynomial");
-    FR_HIP(&ctx->c, hipSetDevice(ctx->c.device));
-    const size_t coef_bytes = (sizeof(uint32_t) * n_felts + 255) & ~(size_t)255;
-    int rc = interpolate_points(ctx, d_cells, nullptr, n_cells, 4, log_cell, log_coef, log_domain, nullptr, coef_bytes, d_index, n_distinct);
-    if (rc) return rc;
-    k::pack30(ctx->c.launch(), reinterpret_cast<const uint32_t*>(ctx->c.arena), n_felts, static_cast<uint8_t*>(d_out_bytes), len);
-    FR_HIP(&ctx->c, hipGetLastError());
-    return FRIEDA_OK;
-}
-
-int reconstruct_stripes_pooled(frieda_ctx* ctx, const uint32_t* d_cells, const uint32_t* d_index, uint32_t n_stripes, uint32_t n_blobs, uint32_t log_cell,
-                               uint32_t log_coef, uint32_t log_domain, size_t len, uint8_t* d_out_bytes, size_t out_stride, uint32_t* n_distinct) {
-    if (!ctx || !d_cells || !d_index || !n_distinct || (len && !d_out_bytes) || n_stripes == 0 || n_blobs == 0 || n_blobs > 256 ||
+int reconstruct_pooled(frieda_ctx* ctx, const uint32_t* d_cells, const uint32_t* d_index, uint32_t n_entries, uint32_t n_blobs, uint32_t log_cell,
+                       uint32_t log_coef, uint32_t log_domain, size_t len, uint8_t* d_out_bytes, size_t out_stride, uint32_t* n_distinct) {
+    if (!ctx || !d_cells || !d_index || !n_distinct || (len && !d_out_bytes) || n_entries == 0 || n_blobs == 0 || n_blobs > 256 ||
         log_coef > FRIEDA_MAX_LOG_DOMAIN)
         return FRIEDA_ERR_ARG;
     const size_t n_felts = (size_t)4 << log_coef;
     if ((8 * len + 29) / 30 > n_felts) return ctx->c.fail(FRIEDA_ERR_ARG, "len does not fit the polynomial");
     FR_HIP(&ctx->c, hipSetDevice(ctx->c.device));
     const size_t coef_bytes = (sizeof(uint32_t) * n_felts * n_blobs + 255) & ~(size_t)255;
-    int rc = interpolate_points(ctx, d_cells, nullptr, n_stripes, 4 * n_blobs, log_cell, log_coef, log_domain, nullptr, coef_bytes, d_index, n_distinct);
+    int rc = interpolate_points(ctx, d_cells, nullptr, n_entries, 4 * n_blobs, log_cell, log_coef, log_domain, nullptr, coef_bytes, d_index, n_distinct);
     if (rc) return rc;
     // blob b's four coefficient columns are columns 4 b .. 4 b + 3: n_felts consecutive words
     for (uint32_t b = 0; b < n_blobs; b++)
         k::pack30(ctx->c.launch(), reinterpret_cast<const uint32_t*>(ctx->c.arena) + (size_t)b * n_felts, n_felts, d_out_bytes + (size_t)b * out_stride, len);
     FR_HIP(&ctx->c, hipGetLastError());
+    return FRIEDA_OK;
+}
+
+int rebuild_blob(frieda_ctx* ctx, size_t len, uint32_t log_blowup, const uint8_t commitment[32], const char* mismatch, uint8_t* out_bytes,
+                 const std::function<int(uint8_t* d_out)>& rebuild) {
+    std::vector<uint8_t> bytes(len);
+    DevBuf out;
+    int rc = out.alloc(&ctx->c, len ? len : 1, "poison(rebuilt bytes)");
+    if (rc != FRIEDA_OK) return rc;
+    rc = rebuild(static_cast<uint8_t*>(out.p));
+    if (rc == FRIEDA_OK) rc = frieda_dev_download(ctx, bytes.data(), out.p, len);
+    (void)hipStreamSynchronize(ctx->c.stream);  // (before the buffer goes, on the error paths too)
+    out.release();
+    if (rc != FRIEDA_OK) return rc;
+    uint8_t root[32];
+    rc = commit_host(&ctx->c, bytes.data(), len, log_blowup, root);
+    if (rc != FRIEDA_OK) return rc;
+    return rebuilt_accept(&ctx->c, root, commitment, 1, mismatch, bytes, out_bytes);
+}
+
+int rebuilt_accept(Ctx* ctx, const uint8_t* roots, const uint8_t* commitments, uint32_t n_blobs, const char* mismatch, const std::vector<uint8_t>& bytes,
+                   uint8_t* out_bytes) {
+    for (uint32_t b = 0; b < n_blobs; b++)
+        if (memcmp(roots + 32 * (size_t)b, commitments + 32 * (size_t)b, 32) != 0)
+            return ctx->fail(FRIEDA_ERR_ARG, mismatch ? mismatch : "the rebuilt blob " + std::to_string(b) + " does not commit to its commitment (wrong len?)");
+    if (!bytes.empty()) memcpy(out_bytes, bytes.data(), bytes.size());
     return FRIEDA_OK;
 }
 

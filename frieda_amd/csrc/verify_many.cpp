@@ -122,24 +122,12 @@ int init_device_tables(Ctx* ctx) {
 }
 
 int pool_alloc(Ctx* ctx, PairPool& pool) {
-    if (pool.d || !pool.cap) return FRIEDA_OK;
+    if (pool.buf.p || !pool.cap) return FRIEDA_OK;
     FR_HIP(ctx, hipSetDevice(ctx->device));
-    void* d = nullptr;
-    const hipError_t e = hipMalloc(&d, ((4 * pool.cap + 255) & ~(size_t)255) + 16 * pool.cap);
-    if (e != hipSuccess) {
-        ctx->err = std::string("hipMalloc: ") + hipGetErrorString(e);
-        return FRIEDA_ERR_NOMEM;
-    }
-    pool.d = static_cast<uint8_t*>(d);
-    FR_HIP(ctx, ctx->poison_fresh(d, ((4 * pool.cap + 255) & ~(size_t)255) + 16 * pool.cap));
-    return FRIEDA_OK;
+    return pool.alloc(ctx, pool.cap, 16, "poison(pair pool)");
 }
 
 }  // namespace
-
-PairPool::~PairPool() {
-    if (d) (void)hipFree(d);
-}
 
 int PairPool::upload_host_rows(Ctx* ctx) {
     bool any = false;
@@ -375,36 +363,14 @@ int frieda_reconstruct_from_proofs(frieda_ctx* ctx, const frieda_proof* const* p
         return ctx->c.fail(FRIEDA_ERR_ARG, std::to_string(index.size()) + " distinct verified points, " + std::to_string(((size_t)1 << L) + 2) + " needed");
     if ((8 * len + 29) / 30 > ((size_t)4 << L)) return ctx->c.fail(FRIEDA_ERR_ARG, "len does not fit the polynomial");
     FR_HIP(&ctx->c, hipSetDevice(ctx->c.device));
-    void *d_cells = nullptr, *d_out = nullptr;
-    hipError_t e = hipMalloc(&d_cells, 4 * cells.size());
-    if (e == hipSuccess) e = hipMalloc(&d_out, len ? len : 1);
-    if (e != hipSuccess) {
-        if (d_cells) (void)hipFree(d_cells);
-        ctx->c.err = std::string("hipMalloc: ") + hipGetErrorString(e);
-        return FRIEDA_ERR_NOMEM;
-    }
-    e = ctx->c.poison_fresh(d_cells, 4 * cells.size());
-    if (e == hipSuccess) e = ctx->c.poison_fresh(d_out, len ? len : 1);
-    if (e != hipSuccess) {
-        (void)hipFree(d_cells);
-        (void)hipFree(d_out);
-        return ctx->c.hip_fail(e, "poison(rebuilt bytes)");
-    }
-    std::vector<uint8_t> bytes(len);
-    rc = frieda_dev_upload(ctx, d_cells, cells.data(), 4 * cells.size());
-    if (rc == FRIEDA_OK)
-        rc = frieda_reconstruct_points_device(ctx, static_cast<const uint32_t*>(d_cells), index.data(), (uint32_t)index.size(), 0, L, L + B, len, d_out);
-    if (rc == FRIEDA_OK) rc = frieda_dev_download(ctx, bytes.data(), d_out, len);
-    (void)hipStreamSynchronize(ctx->c.stream);
-    (void)hipFree(d_cells);
-    (void)hipFree(d_out);
+    DevBuf d_cells;
+    rc = d_cells.alloc(&ctx->c, 4 * cells.size(), "poison(rebuilt bytes)");
     if (rc != FRIEDA_OK) return rc;
-    uint8_t root[32];
-    rc = commit_host(&ctx->c, bytes.data(), len, B, root);
-    if (rc != FRIEDA_OK) return rc;
-    if (memcmp(root, expected_commitment, 32) != 0) return ctx->c.fail(FRIEDA_ERR_ARG, "the rebuilt blob does not commit to expected_commitment (wrong len?)");
-    if (len) memcpy(out_bytes, bytes.data(), len);
-    return FRIEDA_OK;
+    return rebuild_blob(ctx, len, B, expected_commitment, "the rebuilt blob does not commit to expected_commitment (wrong len?)", out_bytes, [&](uint8_t* d_out) {
+        const int up = frieda_dev_upload(ctx, d_cells.p, cells.data(), 4 * cells.size());
+        if (up != FRIEDA_OK) return up;
+        return frieda_reconstruct_points_device(ctx, static_cast<const uint32_t*>(d_cells.p), index.data(), (uint32_t)index.size(), 0, L, L + B, len, d_out);
+    });
     FR_GUARD_END(ctx)
 }
 
@@ -425,7 +391,7 @@ int frieda_verify_pairs_many(frieda_ctx* ctx, const frieda_proof* const* proofs,
     if (rc != FRIEDA_OK) return rc;
     // the gathered rows of the kernel's proofs come back in one copy each (the entries between them, kept for host-route proofs, are not read)
     std::vector<uint32_t> pos, val;
-    if (pool.d && pool.n) {
+    if (pool.buf.p && pool.n) {
         pos.resize(pool.n);
         val.resize(4 * pool.n);
         FR_HIP(&ctx->c, hipMemcpyAsync(pos.data(), pool.d_pos(), 4 * pool.n, hipMemcpyDeviceToHost, ctx->c.stream));
@@ -479,30 +445,11 @@ int frieda_reconstruct_from_proof_pairs(frieda_ctx* ctx, const frieda_proof* con
         *n_points = nd;
         return nd < need ? too_few() : ctx->c.fail(FRIEDA_ERR_ARG, "len does not fit the polynomial");
     }
-    void* d_out = nullptr;
-    const hipError_t e = hipMalloc(&d_out, len ? len : 1);
-    if (e != hipSuccess) {
-        ctx->c.err = std::string("hipMalloc: ") + hipGetErrorString(e);
-        return FRIEDA_ERR_NOMEM;
-    }
-    if (const hipError_t pe = ctx->c.poison_fresh(d_out, len ? len : 1); pe != hipSuccess) {
-        (void)hipFree(d_out);
-        return ctx->c.hip_fail(pe, "poison(rebuilt bytes)");
-    }
-    std::vector<uint8_t> bytes(len);
-    rc = reconstruct_points_pooled(ctx, pool.d_val(), pool.d_pos(), (uint32_t)pool.n, L, L + B, len, d_out, &nd);
-    *n_points = nd;
-    if (rc == FRIEDA_OK) rc = frieda_dev_download(ctx, bytes.data(), d_out, len);
-    (void)hipStreamSynchronize(ctx->c.stream);
-    (void)hipFree(d_out);
-    if (rc == FRIEDA_ERR_ARG && nd < need) return too_few();
-    if (rc != FRIEDA_OK) return rc;
-    uint8_t root[32];
-    rc = commit_host(&ctx->c, bytes.data(), len, B, root);
-    if (rc != FRIEDA_OK) return rc;
-    if (memcmp(root, expected_commitment, 32) != 0) return ctx->c.fail(FRIEDA_ERR_ARG, "the rebuilt blob does not commit to expected_commitment (wrong len?)");
-    if (len) memcpy(out_bytes, bytes.data(), len);
-    return FRIEDA_OK;
+    return rebuild_blob(ctx, len, B, expected_commitment, "the rebuilt blob does not commit to expected_commitment (wrong len?)", out_bytes, [&](uint8_t* d_out) {
+        rc = reconstruct_pooled(ctx, pool.d_val(), pool.d_pos(), (uint32_t)pool.n, 1, 0, L, L + B, len, d_out, 0, &nd);
+        *n_points = nd;
+        return rc == FRIEDA_ERR_ARG && nd < need ? too_few() : rc;
+    });
     FR_GUARD_END(ctx)
 }
 

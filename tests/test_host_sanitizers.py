@@ -87,3 +87,11 @@ def test_unit_pipeline_order_and_retry(tmp_path):
     unit is abandoned, `done` ends behind the last finished unit), and the retry of a pass that ran out of device memory (17 cuts
     at most, each from the first blob not done; none for single blobs, another error or an aborted call)."""
     _run_host_program(tmp_path, "test_unit_pipeline")
+
+
+def test_cells_pass_planner_matches_the_written_out_formulas(tmp_path):
+    """cells_pass.h under UBSan against the verifier's formulas restated in the test: cells per pass for one commitment, many blobs and
+    stripes (log_cell 0 .. 10, depth 0 .. 12, 1 / 63 / 64 / 65 / 300 cells, groups of 1, 3 and 256, budgets of one byte, exactly k cells,
+    one byte less and the default), 256-byte rounding, the order of the staged image, and whole calls walked pass by pass: the passes
+    partition the cells, no stripe straddles a pass, every later pass fits the plan of the first."""
+    _run_host_program(tmp_path, "test_cells_pass")
