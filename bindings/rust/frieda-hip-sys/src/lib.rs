@@ -43,6 +43,11 @@ pub const FRIEDA_VERIFY_REJECTED: u8 = 0;
 pub const FRIEDA_VERIFY_ACCEPTED: u8 = 1;
 pub const FRIEDA_VERIFY_INVARIANT: u8 = 2;
 pub const FRIEDA_VERIFY_WRONG_COMMITMENT: u8 = 3;
+/// status bytes of frieda_verify_cell_bundles / frieda_verify_cell_bundles_many / frieda_reconstruct_from_cell_bundles
+pub const FRIEDA_BUNDLE_REJECTED: u8 = 0;
+pub const FRIEDA_BUNDLE_ACCEPTED: u8 = 1;
+pub const FRIEDA_BUNDLE_MALFORMED: u8 = 2;
+pub const FRIEDA_MAX_BUNDLE_CELLS: u32 = 1024;
 
 extern "C" {
     pub fn frieda_abi_version() -> u32;
@@ -145,6 +150,13 @@ extern "C" {
     pub fn frieda_verify_cells_blobs(commitments: *const u8, n_blobs: u32, log_domain: u32, log_cell: u32, blob_index: *const u32, cell_index: *const u32, n_cells: u32, values: *const u32, paths: *const u8, out_status: *mut u8) -> c_int;
     pub fn frieda_verify_cells_blobs_many(ctx: *mut frieda_ctx, commitments: *const u8, n_blobs: u32, log_domain: u32, log_cell: u32, blob_index: *const u32, cell_index: *const u32, n_cells: u32, values: *const u32, paths: *const u8, out_status: *mut u8) -> c_int;
     pub fn frieda_reconstruct_blobs_from_opened_stripes(ctx: *mut frieda_ctx, commitments: *const u8, n_blobs: u32, log_blowup_factor: u32, len: usize, log_cell: u32, stripe_index: *const u32, n_stripes: u32, values: *const u32, paths: *const u8, out_bytes: *mut u8, out_status: *mut u8, n_stripes_used: *mut usize) -> c_int;
+    // cell bundles: k cells of one blob (indices strictly ascending) under one shared hash witness; a call carries n_bundles of them back to
+    // back, bundle_first / witness_first have n_bundles + 1 entries (witness_first in hashes); one status byte per bundle (0 rejected, 1 accepted, 2 malformed)
+    pub fn frieda_cell_bundle_witness_count(log_domain: u32, log_cell: u32, cell_index: *const u32, n_cells: u32, n_hashes: *mut usize) -> c_int;
+    pub fn frieda_open_cell_bundles(ctx: *mut frieda_ctx, enc: *const frieda_encoded, log_cell: u32, cell_index: *const u32, bundle_first: *const u32, n_bundles: u32, out_values: *mut u32, out_witness: *mut u8, cap_hashes: usize, out_witness_first: *mut u64) -> c_int;
+    pub fn frieda_verify_cell_bundles(commitment: *const u8, log_domain: u32, log_cell: u32, cell_index: *const u32, bundle_first: *const u32, n_bundles: u32, values: *const u32, witness: *const u8, witness_first: *const u64, out_status: *mut u8) -> c_int;
+    pub fn frieda_verify_cell_bundles_many(ctx: *mut frieda_ctx, commitment: *const u8, log_domain: u32, log_cell: u32, cell_index: *const u32, bundle_first: *const u32, n_bundles: u32, values: *const u32, witness: *const u8, witness_first: *const u64, out_status: *mut u8) -> c_int;
+    pub fn frieda_reconstruct_from_cell_bundles(ctx: *mut frieda_ctx, commitment: *const u8, log_blowup_factor: u32, len: usize, log_cell: u32, cell_index: *const u32, bundle_first: *const u32, n_bundles: u32, values: *const u32, witness: *const u8, witness_first: *const u64, out_bytes: *mut u8, out_status: *mut u8, n_cells_used: *mut usize) -> c_int;
 
     // struct Proof
     pub fn frieda_proof_free(p: *mut frieda_proof);

@@ -18,6 +18,8 @@ OK, ERR_ARG, ERR_HIP, ERR_INVARIANT, ERR_NOMEM, ERR_FORMAT = 0, 1, 2, 3, 4, 5
 VERIFY_REJECTED, VERIFY_ACCEPTED, VERIFY_INVARIANT, VERIFY_WRONG_COMMITMENT = 0, 1, 2, 3  # status bytes of frieda_verify_many
 CELL_REJECTED, CELL_ACCEPTED = 0, 1  # status bytes of frieda_verify_cells*
 MAX_LOG_OPEN_CELL = 10
+BUNDLE_REJECTED, BUNDLE_ACCEPTED, BUNDLE_MALFORMED = 0, 1, 2  # status bytes of frieda_verify_cell_bundles*
+MAX_BUNDLE_CELLS = 1024
 
 
 class PcsConfigC(C.Structure):
@@ -152,6 +154,11 @@ def lib():
         "frieda_verify_cells_blobs": (C.c_int, [vp, u32, u32, u32, vp, vp, u32, vp, vp, vp]),
         "frieda_verify_cells_blobs_many": (C.c_int, [vp, vp, u32, u32, u32, vp, vp, u32, vp, vp, vp]),
         "frieda_reconstruct_blobs_from_opened_stripes": (C.c_int, [vp, vp, u32, u32, sz, u32, vp, u32, vp, vp, vp, vp, C.POINTER(sz)]),
+        "frieda_cell_bundle_witness_count": (C.c_int, [u32, u32, vp, u32, C.POINTER(sz)]),
+        "frieda_open_cell_bundles": (C.c_int, [vp, vp, u32, vp, vp, u32, vp, vp, sz, vp]),
+        "frieda_verify_cell_bundles": (C.c_int, [vp, u32, u32, vp, vp, u32, vp, vp, vp, vp]),
+        "frieda_verify_cell_bundles_many": (C.c_int, [vp, vp, u32, u32, vp, vp, u32, vp, vp, vp, vp]),
+        "frieda_reconstruct_from_cell_bundles": (C.c_int, [vp, vp, u32, sz, u32, vp, vp, u32, vp, vp, vp, vp, vp, C.POINTER(sz)]),
         "frieda_proof_free": (None, [vp]),
         "frieda_proof_clone": (C.c_int, [vp, pp]),
         "frieda_proof_proof_of_work": (u64, [vp]),

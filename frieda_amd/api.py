@@ -564,6 +564,45 @@ class Context:
             raise
         return out[:n_bytes].tobytes(), status[:count], n.value
 
+    # ---- cell bundles: many cells under one shared Merkle witness (Encoded.open_cell_bundles is the provider's half) ----
+    def verify_cell_bundles_many(self, commitment, log_domain, log_cell, bundles, values, witness, witness_first):
+        """One status byte per bundle (numpy uint8: BUNDLE_REJECTED / BUNDLE_ACCEPTED / BUNDLE_MALFORMED), verified on the device; the
+        bytes verify_cell_bundles() gives.  bundles: one ascending index list per bundle; values / witness / witness_first as
+        Encoded.open_cell_bundles returns them."""
+        idx, first, val, wit, wfirst = _bundle_arrays(log_cell, bundles, values, witness, witness_first)
+        status = np.zeros(max(len(first) - 1, 1), dtype=np.uint8)
+        com = (C.c_uint8 * 32)(*commitment)
+        _check(
+            self._L.frieda_verify_cell_bundles_many(self._h, com, log_domain, log_cell, idx.ctypes.data, first.ctypes.data, len(first) - 1, val.ctypes.data,
+                                                    wit.ctypes.data, wfirst.ctypes.data, status.ctypes.data),
+            self._h,
+        )
+        return status[: len(first) - 1]
+
+    def reconstruct_from_cell_bundles(self, commitment, log_blowup_factor, n_bytes, log_cell, bundles, values, witness, witness_first):
+        """Verify the bundles against the commitment, pool the cells of the accepted ones and rebuild the blob: (bytes, status,
+        n_cells_used).  Raises FriedaError (with .n_cells_used and .bundle_status set) when the cells of the accepted bundles do not
+        suffice or the result does not commit to `commitment`."""
+        idx, first, val, wit, wfirst = _bundle_arrays(log_cell, bundles, values, witness, witness_first)
+        count = len(first) - 1
+        status = np.zeros(max(count, 1), dtype=np.uint8)
+        out = np.zeros(max(n_bytes, 1), dtype=np.uint8)
+        n = C.c_size_t(0)
+        com = (C.c_uint8 * 32)(*commitment)
+        try:
+            _check(
+                self._L.frieda_reconstruct_from_cell_bundles(
+                    self._h, com, log_blowup_factor, n_bytes, log_cell, idx.ctypes.data, first.ctypes.data, count, val.ctypes.data, wit.ctypes.data,
+                    wfirst.ctypes.data, out.ctypes.data, status.ctypes.data, C.byref(n)
+                ),
+                self._h,
+            )
+        except FriedaError as e:
+            e.n_cells_used = n.value
+            e.bundle_status = status[:count]
+            raise
+        return out[:n_bytes].tobytes(), status[:count], n.value
+
     # ---- the cells of a block: many blobs of one shape in one call (cell i is cell cell_index[i] of blob blob_index[i]) ----
     def verify_cells_blobs_many(self, commitments, log_domain, log_cell, blob_index, cell_index, values, paths):
         """One status byte per (blob, cell) pair, verified on the device in one call; the bytes verify_cells_blobs() gives."""
@@ -631,6 +670,38 @@ def _cell_arrays(log_domain, log_cell, cell_index, values, paths):
     return idx, val, pth
 
 
+def _bundle_index_arrays(bundles):
+    """one index list per bundle -> (the indices back to back, bundle_first[n_bundles + 1])"""
+    lists = [np.ascontiguousarray(b, dtype=np.uint32).reshape(-1) for b in bundles]
+    first = np.zeros(len(lists) + 1, dtype=np.uint32)
+    if lists:
+        first[1:] = np.cumsum([len(x) for x in lists])
+    idx = np.concatenate(lists) if lists else np.zeros(0, dtype=np.uint32)
+    return np.ascontiguousarray(idx, dtype=np.uint32), first
+
+
+def _bundle_arrays(log_cell, bundles, values, witness, witness_first):
+    """the host arrays of a bundles call, contiguous and of the sizes the C ABI reads: a short array must not reach the library (what the
+    arrays SAY — order, range, witness lengths — is the library's to judge: a bad bundle gets its own status)"""
+    if not 0 <= log_cell <= _lib.MAX_LOG_OPEN_CELL:
+        raise FriedaError(_lib.ERR_ARG, "log_cell out of range")
+    idx, first = _bundle_index_arrays(bundles)
+    val = np.ascontiguousarray(values, dtype=np.uint32).reshape(-1)
+    wit = np.ascontiguousarray(witness, dtype=np.uint8).reshape(-1)
+    wfirst = np.ascontiguousarray(witness_first, dtype=np.uint64).reshape(-1)
+    if val.size != (len(idx) * 4) << log_cell:
+        raise FriedaError(_lib.ERR_ARG, "values do not have the shape of the cell list")
+    if len(wfirst) != len(first) or (len(wfirst) and wit.size < 32 * int(wfirst.max())):
+        raise FriedaError(_lib.ERR_ARG, "witness_first: one entry per bundle and one more, none beyond the witness")
+    if wit.size == 0:
+        wit = np.zeros(1, dtype=np.uint8)
+    if val.size == 0:
+        val = np.zeros(1, dtype=np.uint32)
+    if idx.size == 0:
+        idx = np.zeros(1, dtype=np.uint32)
+    return idx, first, val, wit, wfirst
+
+
 def _commitment_table(commitments):
     """[K][32] commitments -> one contiguous uint8 array of 32 K bytes"""
     rows = [bytes(c) for c in commitments]
@@ -694,6 +765,25 @@ class Encoded:
             ctx._h,
         )
         return values, paths
+
+    def open_cell_bundles(self, ctx, log_cell, bundles):
+        """Cells of the codeword in bundles, each bundle (one strictly ascending index list) under ONE shared Merkle witness
+        (frieda_open_cell_bundles on `ctx`): (values uint32 [n, 4, 2^log_cell] over all cells of the call, witness uint8 [H, 32] of all
+        bundles back to back, witness_first uint64 [n_bundles + 1] in hashes)."""
+        idx, first = _bundle_index_arrays(bundles)
+        nb = len(first) - 1
+        wfirst = np.zeros(nb + 1, dtype=np.uint64)
+        if nb == 0:
+            return np.zeros((0, 4, 1 << log_cell), dtype=np.uint32), np.zeros((0, 32), dtype=np.uint8), wfirst
+        L = _lib.lib()
+        iptr = idx.ctypes.data if idx.size else None
+        _check(L.frieda_open_cell_bundles(ctx._h, self._handle(), log_cell, iptr, first.ctypes.data, nb, None, None, 0, wfirst.ctypes.data), ctx._h)
+        total = int(wfirst[-1])
+        values = np.zeros((len(idx), 4, 1 << log_cell), dtype=np.uint32)
+        witness = np.zeros((max(total, 1), 32), dtype=np.uint8)
+        _check(L.frieda_open_cell_bundles(ctx._h, self._handle(), log_cell, iptr, first.ctypes.data, nb, values.ctypes.data, witness.ctypes.data, total,
+                                          wfirst.ctypes.data), ctx._h)
+        return values, witness[:total], wfirst
 
     def close(self):
         if self._h:
@@ -1134,6 +1224,41 @@ def verify_cells_many(commitment, log_domain, log_cell, cell_index, values, path
 def reconstruct_from_opened_cells(commitment, log_blowup_factor, n_bytes, log_cell, cell_index, values, paths):
     """frieda_reconstruct_from_opened_cells on the default context: (bytes, status, n_cells_used)."""
     return default_context().reconstruct_from_opened_cells(commitment, log_blowup_factor, n_bytes, log_cell, cell_index, values, paths)
+
+
+def cell_bundle_witness_count(log_domain, log_cell, cell_index):
+    """The witness length, in hashes, of one bundle of the strictly ascending cells `cell_index` (frieda_cell_bundle_witness_count: host
+    only).  Raises FriedaError for a malformed bundle."""
+    idx = np.ascontiguousarray(cell_index, dtype=np.uint32).reshape(-1)
+    n = C.c_size_t(0)
+    _check(_lib.lib().frieda_cell_bundle_witness_count(log_domain, log_cell, idx.ctypes.data if idx.size else None, len(idx), C.byref(n)))
+    return int(n.value)
+
+
+def open_cell_bundles(encoded, log_cell, bundles):
+    """Encoded.open_cell_bundles on the default context: (values, witness, witness_first)."""
+    return encoded.open_cell_bundles(default_context(), log_cell, bundles)
+
+
+def verify_cell_bundles(commitment, log_domain, log_cell, bundles, values, witness, witness_first):
+    """The host verifier of cell bundles (frieda_verify_cell_bundles: no context, one core): one status byte per bundle (numpy uint8),
+    BUNDLE_REJECTED / BUNDLE_ACCEPTED / BUNDLE_MALFORMED."""
+    idx, first, val, wit, wfirst = _bundle_arrays(log_cell, bundles, values, witness, witness_first)
+    status = np.zeros(max(len(first) - 1, 1), dtype=np.uint8)
+    com = (C.c_uint8 * 32)(*commitment)
+    _check(_lib.lib().frieda_verify_cell_bundles(com, log_domain, log_cell, idx.ctypes.data, first.ctypes.data, len(first) - 1, val.ctypes.data, wit.ctypes.data,
+                                                 wfirst.ctypes.data, status.ctypes.data))
+    return status[: len(first) - 1]
+
+
+def verify_cell_bundles_many(commitment, log_domain, log_cell, bundles, values, witness, witness_first):
+    """frieda_verify_cell_bundles_many on the default context: one status byte per bundle, verified on the device."""
+    return default_context().verify_cell_bundles_many(commitment, log_domain, log_cell, bundles, values, witness, witness_first)
+
+
+def reconstruct_from_cell_bundles(commitment, log_blowup_factor, n_bytes, log_cell, bundles, values, witness, witness_first):
+    """frieda_reconstruct_from_cell_bundles on the default context: (bytes, status, n_cells_used)."""
+    return default_context().reconstruct_from_cell_bundles(commitment, log_blowup_factor, n_bytes, log_cell, bundles, values, witness, witness_first)
 
 
 def open_cells_blobs(ctx, encs, log_cell, blob_index, cell_index):

@@ -7,7 +7,7 @@
 //   cells_open      per requested cell the four runs of 2^c words (16-byte copies from c = 2 on) and the siblings of its path, read from
 //                   the encoded blob's tree where the level is stored and re-hashed from the evaluation where it is not (the leaf hashes
 //                   never are; a tree built at or above its skip threshold also lacks the two levels above them): at most four leaves
-//                   and three nodes, and only for c <= 2.
+//                   and three nodes, and only for c <= 2 (cells_dev.h: bundles.hip opens its shared witnesses by the same code).
 //   cells_verify    two launches.  Roots: a lane per leaf pair (pair_node: two leaves and their parent), then an LDS reduction to the
 //                   cell's subtree root; a workgroup covers 256 pairs, i.e. 2^(9 - c) cells (c = 10: one cell, two pairs per lane).  The
 //                   canonical-word check runs there.  Walk: a lane per cell, n - c dependent compressions up the path, then the compare
@@ -22,6 +22,7 @@
 //                   accepted stripes -> the pool, which is the point reconstruction's layout at 4 * n_blobs columns.
 #include <type_traits>
 
+#include "cells_dev.h"
 #include "kernels.h"
 #include "tree_dev.h"
 
@@ -31,39 +32,6 @@ namespace k {
 namespace {
 
 constexpr int CL_THREADS = 256;
-
-__device__ __forceinline__ void leaf_at(const uint32_t* __restrict__ v, size_t cs, size_t j, uint32_t (&l)[4]) {
-    l[0] = v[j], l[1] = v[cs + j], l[2] = v[2 * cs + j], l[3] = v[3 * cs + j];
-}
-
-// node `node` of level n - up (up = 0: a leaf hash, 1: the parent of two leaves, 2: of four) from the evaluation v[4][2^n]
-__device__ __forceinline__ void node_from_eval(const uint32_t* __restrict__ v, uint32_t n, uint32_t up, size_t node, uint32_t (&h)[8]) {
-    const size_t cs = (size_t)1 << n;
-    uint32_t l[4], r[4];
-    if (up == 0) {
-        leaf_at(v, cs, node, l);
-        treedev::leaf_hash<B2_LAT>(l[0], l[1], l[2], l[3], h);
-        return;
-    }
-    if (up == 1) {
-        leaf_at(v, cs, 2 * node, l);
-        leaf_at(v, cs, 2 * node + 1, r);
-        treedev::pair_node<B2_LAT>(l, r, h);
-        return;
-    }
-    uint32_t hb[8], m[16];
-    leaf_at(v, cs, 4 * node, l);
-    leaf_at(v, cs, 4 * node + 1, r);
-    treedev::pair_node<B2_LAT>(l, r, hb);
-#pragma unroll
-    for (int w = 0; w < 8; w++) m[w] = hb[w];
-    leaf_at(v, cs, 4 * node + 2, l);
-    leaf_at(v, cs, 4 * node + 3, r);
-    treedev::pair_node<B2_LAT>(l, r, hb);
-#pragma unroll
-    for (int w = 0; w < 8; w++) m[8 + w] = hb[w];
-    b2_merkle_block<B2_LAT>(m, h);
-}
 
 // The blob cell `cell` is opened from: the one of the call, or row bidx[cell] of the call's table (cell i is cell idx[i] of blob bidx[i]).
 // The single-blob form reads the kernel arguments and nothing else.
@@ -105,20 +73,8 @@ __global__ __launch_bounds__(CL_THREADS) void cells_open_paths_kernel(Args a) {
     const size_t node = (size_t)(a.idx[cell] >> s) ^ 1;
     const BlobSource b = blob_of(a, cell);
     uint4* o = a.out_paths + 2 * e;
-    // Deliberately conservative: decommit.hip's rule, by the threshold alone.  A route that wrote levels n - 1, n - 2 although n >= skip_log
-    // (the fused small-domain launch never skips them) is re-hashed all the same — the words are equal, and no route is ever read where
-    // it did not write.
-    const bool stored = level < a.n && !(a.n >= b.skip_log && level + 2 >= a.n);
-    if (stored) {
-        const uint4* p = reinterpret_cast<const uint4*>(b.tree + treedev::layer_off(a.n, level) + 32 * node);
-        const uint4 x = p[0], y = p[1];
-        o[0] = x, o[1] = y;
-    } else {
-        uint32_t h[8];
-        node_from_eval(b.eval, a.n, a.n - level, node, h);
-        o[0] = make_uint4(h[0], h[1], h[2], h[3]);
-        o[1] = make_uint4(h[4], h[5], h[6], h[7]);
-    }
+    // stored levels are read, the others re-hashed from the evaluation (cells_dev.h: the rule bundles.hip opens by too)
+    cellsdev::open_node(b.eval, b.tree, a.n, b.skip_log, level, node, o);
 }
 
 constexpr uint32_t CV_MAX_T = 512;  // pair nodes of a workgroup: 256, or the 512 of one cell of 2^10 entries
@@ -258,20 +214,31 @@ __global__ __launch_bounds__(CL_THREADS) void cells_stripe_gather_kernel(const u
 unsigned blocks_for(size_t units) { return (unsigned)((units + CL_THREADS - 1) / CL_THREADS); }
 
 template <class Args>
+void open_values_launch(const Launch& L, const Args& a) {
+    constexpr bool TABLE = std::is_same<Args, CellsOpenBlobsArgs>::value;
+    if (!a.n_cells) return;
+    Scope scope(L, TABLE ? "cells_open_blobs_values" : "cells_open_values", 32.0 * (double)(((size_t)a.n_cells) << a.log_cell));
+    if (a.log_cell >= 2)
+        cells_open_values_kernel<4><<<blocks_for(((size_t)a.n_cells * 4) << (a.log_cell - 2)), CL_THREADS, 0, L.stream>>>(a);
+    else
+        cells_open_values_kernel<1><<<blocks_for(((size_t)a.n_cells * 4) << a.log_cell), CL_THREADS, 0, L.stream>>>(a);
+}
+
+template <class Args>
 void open_launch(const Launch& L, const Args& a) {
     constexpr bool TABLE = std::is_same<Args, CellsOpenBlobsArgs>::value;
     if (!a.n_cells) return;
-    {
-        Scope scope(L, TABLE ? "cells_open_blobs_values" : "cells_open_values", 32.0 * (double)(((size_t)a.n_cells) << a.log_cell));
-        if (a.log_cell >= 2)
-            cells_open_values_kernel<4><<<blocks_for(((size_t)a.n_cells * 4) << (a.log_cell - 2)), CL_THREADS, 0, L.stream>>>(a);
-        else
-            cells_open_values_kernel<1><<<blocks_for(((size_t)a.n_cells * 4) << a.log_cell), CL_THREADS, 0, L.stream>>>(a);
-    }
+    open_values_launch(L, a);
     if (a.n > a.log_cell) {
         Scope scope(L, TABLE ? "cells_open_blobs_paths" : "cells_open_paths", 64.0 * (double)a.n_cells * (a.n - a.log_cell));
         cells_open_paths_kernel<<<blocks_for((size_t)a.n_cells * (a.n - a.log_cell)), CL_THREADS, 0, L.stream>>>(a);
     }
+}
+
+void roots_launch(const Launch& L, const CellsVerifyArgs& a) {
+    Scope scope(L, "cells_roots", 0.0);  // (knows neither index nor commitment)
+    const uint32_t cpw = a.log_cell >= 10 ? 1u : 1u << (9 - a.log_cell);
+    cells_roots_kernel<<<(a.n_cells + cpw - 1) / cpw, CL_THREADS, 0, L.stream>>>(a);
 }
 
 template <bool TABLE>
@@ -282,11 +249,7 @@ void verify_launch(const Launch& L, const CellsVerifyArgs& a, const uint32_t* d_
         cells_walk_kernel<true, TABLE><<<blocks_for(a.n_cells), CL_THREADS, 0, L.stream>>>(a, d_bidx, d_commitments);
         return;
     }
-    {
-        Scope scope(L, "cells_roots", 0.0);  // (knows neither index nor commitment)
-        const uint32_t cpw = a.log_cell >= 10 ? 1u : 1u << (9 - a.log_cell);
-        cells_roots_kernel<<<(a.n_cells + cpw - 1) / cpw, CL_THREADS, 0, L.stream>>>(a);
-    }
+    roots_launch(L, a);
     Scope scope(L, TABLE ? "cells_walk_blobs" : "cells_walk", 0.0);
     cells_walk_kernel<false, TABLE><<<blocks_for(a.n_cells), CL_THREADS, 0, L.stream>>>(a, d_bidx, d_commitments);
 }
@@ -294,9 +257,13 @@ void verify_launch(const Launch& L, const CellsVerifyArgs& a, const uint32_t* d_
 }  // namespace
 
 void cells_open(const Launch& L, const CellsOpenArgs& a) { open_launch(L, a); }
+void cells_open_values(const Launch& L, const CellsOpenArgs& a) { open_values_launch(L, a); }
 void cells_open_blobs(const Launch& L, const CellsOpenBlobsArgs& a) { open_launch(L, a); }
 
 void cells_verify(const Launch& L, const CellsVerifyArgs& a) { verify_launch<false>(L, a, nullptr, nullptr); }
+void cells_roots(const Launch& L, const CellsVerifyArgs& a) {
+    if (a.n_cells && a.log_cell) roots_launch(L, a);
+}
 void cells_verify_blobs(const Launch& L, const CellsVerifyArgs& a, const uint32_t* d_bidx, const uint32_t* d_commitments) {
     verify_launch<true>(L, a, d_bidx, d_commitments);
 }

@@ -406,6 +406,7 @@ struct CellsOpenArgs {
     uint4* out_paths;      // [n_cells][n - log_cell] hashes
 };
 void cells_open(const Launch& L, const CellsOpenArgs& a);
+void cells_open_values(const Launch& L, const CellsOpenArgs& a);  // the values alone (out_paths is not read): bundles open their own witness
 struct CellsVerifyArgs {
     const uint32_t* values;  // [n_cells][4][2^log_cell], 16-byte aligned
     const uint4* paths;      // level-major: [n - log_cell][n_cells] hashes
@@ -417,6 +418,8 @@ struct CellsVerifyArgs {
     uint32_t commitment[8];
 };
 void cells_verify(const Launch& L, const CellsVerifyArgs& a);
+// the first launch alone: roots[8][n_cells] and bad[n_cells] (nothing for log_cell 0); reads neither paths, idx nor commitment
+void cells_roots(const Launch& L, const CellsVerifyArgs& a);
 // cells of a pass -> the call's pool.  d_tab[n_rows][2]: slot of the pass, entry of the pool; d_pool_idx[entry], d_pool_val[entry][4][2^log_cell]
 void cells_gather(const Launch& L, const uint32_t* d_tab, uint32_t n_rows, const uint32_t* d_values, const uint32_t* d_idx, uint32_t log_cell,
                   uint32_t* d_pool_idx, uint32_t* d_pool_val);
@@ -446,6 +449,40 @@ void cells_stripe_accept(const Launch& L, const uint32_t* d_status, uint32_t n_s
 // (d_idx of its first cell), d_pool_val[entry][n_blobs][4][2^log_cell]: the d_cells layout of the point reconstruction at 4 * n_blobs columns
 void cells_stripe_gather(const Launch& L, const uint32_t* d_tab, uint32_t n_rows, const uint32_t* d_values, const uint32_t* d_idx, uint32_t n_blobs,
                          uint32_t log_cell, uint32_t* d_pool_idx, uint32_t* d_pool_val);
+
+// ---- bundles.hip: cell bundles, k cells of one blob under one shared Merkle witness (frieda_open_cell_bundles, frieda_verify_cell_bundles_many) ----
+// The witness of a bundle is stwo's hash witness for the tree cut at level d = n - log_cell with the cell indices as positions: the
+// tables E_1 .. E_d of queries_dev.h, E_s read at tree level d - s + 1, bottom-up and ascending within a level.
+constexpr uint32_t BUNDLE_MAX_CELLS = 1024;  // = FRIEDA_MAX_BUNDLE_CELLS
+struct BundleRow {  // one bundle of a call or pass
+    uint32_t first_cell, n_cells;  // its cells in idx / values: strictly ascending indices (checked by the caller)
+    uint32_t first_hash;           // its witness in `witness`, in hashes (verify only)
+};
+struct BundleOpenArgs {
+    const uint32_t* eval;  // as CellsOpenArgs
+    const uint8_t* tree;
+    uint32_t n, log_cell, skip_log, n_bundles;
+    const uint32_t* idx;        // the cell indices of all bundles, back to back
+    const BundleRow* rows;      // n_bundles rows
+    const uint64_t* level_base; // [n_bundles][n - log_cell]: where E_s of bundle b starts in out_witness, in hashes (from the host)
+    uint4* out_witness;
+};
+// one wave per (bundle, level): entry r of E_s goes to out_witness[level_base[b][s - 1] + r]
+void bundle_open_witness(const Launch& L, const BundleOpenArgs& a);
+struct BundleWalkArgs {
+    const uint32_t* values;   // LEAF (log_cell 0): [n_cells][4] words, 16-byte aligned
+    const uint32_t* roots;    // else: [8][n_cells] words and bad[n_cells] from cells_roots
+    const uint32_t* bad;
+    const uint32_t* idx;      // [n_cells]
+    const BundleRow* rows;    // [n_bundles]
+    const uint32_t* witness;  // 8 words per hash; bundle b's hashes run from rows[b].first_hash to the next row's (the host checked the count)
+    uint32_t* status;         // out: [n_bundles], 1 = accepted, 0 = rejected
+    uint32_t n, log_cell, n_cells, n_bundles, n_hashes, max_cells;  // n_hashes: of the whole witness; max_cells: the largest bundle (sizes the LDS)
+    uint32_t commitment[8];
+};
+size_t bundle_walk_lds_bytes(uint32_t max_cells);
+// one wave per bundle: the (position, hash) list in LDS merged upward level by level (walk_dev.h), the root compared with the commitment
+void bundle_walk(const Launch& L, const BundleWalkArgs& a);
 
 // ---- opening.hip: Level B openings (frieda_dev_gather*, frieda_merkle_decommit*) ----
 constexpr uint32_t OPEN_BAD_WORD = 0xFFFFFFFFu;   // gathered word of an out-of-range index (device forms only; not a canonical M31)

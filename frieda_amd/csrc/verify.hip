@@ -22,6 +22,7 @@
 #include "kernels.h"
 #include "queries_dev.h"
 #include "tree_dev.h"
+#include "walk_dev.h"
 
 namespace frieda {
 namespace k {
@@ -47,32 +48,8 @@ __device__ __forceinline__ uint32_t coset_index(uint32_t n, uint32_t doublings, 
     return (uint32_t)((init + step * i) & 0x7fffffffull);
 }
 
-struct Group {
-    bool first, miss, has_l, has_r;
-    uint32_t x, k, w;
-};
-
-// One 64-entry chunk of a level: lane `lane` looks at entry i = i0 + lane of the ascending list p[0 .. c).  The first entry of every
-// parent group (x >> 1) owns the group: k = its index in the next level, w = the index of its missing child among the missing children
-// of the level (a group misses at most one).  `carry`: the entry below the chunk (valid for i0 > 0).
-__device__ __forceinline__ Group group_of(const uint32_t* p, uint32_t c, uint32_t i0, uint32_t lane, uint32_t carry, uint32_t& kbase, uint32_t& wbase) {
-    const unsigned long long lt_mask = (1ull << lane) - 1;
-    const uint32_t i = i0 + lane;
-    Group g;
-    g.x = i < c ? p[i] : 0u;
-    const uint32_t prev = lane == 0 ? carry : p[i < c ? i - 1 : 0];
-    const uint32_t next = i + 1 < c ? p[i + 1] : 0xFFFFFFFFu;
-    g.first = i < c && (i == 0 || (prev >> 1) != (g.x >> 1));
-    g.has_l = !(g.x & 1u);
-    g.has_r = (g.x & 1u) || next == g.x + 1;
-    g.miss = g.first && !(g.has_l && g.has_r);
-    const unsigned long long mf = __ballot(g.first), mm = __ballot(g.miss);
-    g.k = kbase + (uint32_t)__popcll(mf & lt_mask);
-    g.w = wbase + (uint32_t)__popcll(mm & lt_mask);
-    kbase += (uint32_t)__popcll(mf);
-    wbase += (uint32_t)__popcll(mm);
-    return g;
-}
+using walkdev::Group;
+using walkdev::group_of;
 
 __device__ __forceinline__ QM31 load_qm(const uint32_t* p) { return QM31{p[0], p[1], p[2], p[3]}; }
 
@@ -206,35 +183,7 @@ __global__ __launch_bounds__(64) void verify_many_kernel(VerifyArgs a) {
         // ---- the Merkle walk of this layer: levels m - 2 .. 0 ----
         uint32_t cn = c, hbase = 0;
         for (uint32_t lv = m - 1; lv > 0; lv--) {
-            uint32_t kb = 0, cr = 0;
-            for (uint32_t i0 = 0; i0 < cn; i0 += 64) {
-                const Group g = group_of(s_hp, cn, i0, lane, cr, kb, hbase);
-                const uint32_t i = i0 + lane;
-                uint32_t mm[16];
-                if (g.first) {
-                    const bool wok = !g.miss || g.w < nh;
-                    if (!wok) bad = true;  // WitnessTooShort
-                    const uint32_t* wsrc = hw + 8 * (size_t)(wok && g.miss ? g.w : 0);
-                    const uint32_t* own = s_h + 8 * i;
-                    const uint32_t* nxt = s_h + 8 * (g.has_l && g.has_r ? i + 1 : i);
-#pragma unroll
-                    for (int w = 0; w < 8; w++) {
-                        const uint32_t wv = (g.miss && wok) ? wsrc[w] : 0u;
-                        mm[w] = g.has_l ? own[w] : wv;
-                        mm[8 + w] = (g.x & 1u) ? own[w] : (g.has_r ? nxt[w] : wv);
-                    }
-                }
-                cr = (uint32_t)__shfl((int)g.x, 63);
-                __syncthreads();
-                if (g.first) {
-                    uint32_t hp[8];
-                    b2_merkle_block<B2_LAT>(mm, hp);
-#pragma unroll
-                    for (int w = 0; w < 8; w++) s_h[8 * g.k + w] = hp[w];
-                    s_hp[g.k] = g.x >> 1;
-                }
-                __syncthreads();
-            }
+            const uint32_t kb = walkdev::walk_level(s_hp, s_h, cn, lane, hw, nh, hbase, bad);  // (WitnessTooShort sets bad)
             cn = kb;
             if (__any(bad)) VK_FINISH(VERIFY_REJECTED);
         }

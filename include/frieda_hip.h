@@ -142,7 +142,8 @@ int frieda_commit_and_generate_proof_device(frieda_ctx* ctx, const void* d_data,
  * frieda_verify_pairs_many, frieda_reconstruct_from_proof_pairs (frieda_verify_pairs is host-only and takes no context),
  * frieda_open_cells, frieda_verify_cells_many, frieda_reconstruct_from_opened_cells (frieda_verify_cells is host-only and takes no context),
  * frieda_open_cells_blobs, frieda_verify_cells_blobs_many, frieda_reconstruct_blobs_from_opened_stripes (frieda_verify_cells_blobs is host-only
- * and takes no context).  Level B calls that only read the twiddle cache and caller buffers stay available.
+ * and takes no context), frieda_open_cell_bundles, frieda_verify_cell_bundles_many, frieda_reconstruct_from_cell_bundles
+ * (frieda_cell_bundle_witness_count and frieda_verify_cell_bundles are host-only and take no context).  Level B calls that only read the twiddle cache and caller buffers stay available.
  * A blob passed to _begin_device must stay valid until _finish returns. */
 int frieda_prove_begin(frieda_ctx* ctx, const uint8_t* data, size_t len, const uint64_t* seed, frieda_pcs_config cfg);
 int frieda_prove_begin_device(frieda_ctx* ctx, const void* d_data, size_t len, const uint64_t* seed, frieda_pcs_config cfg);
@@ -389,6 +390,68 @@ int frieda_verify_cells_blobs_many(frieda_ctx* ctx, const uint8_t* commitments, 
 int frieda_reconstruct_blobs_from_opened_stripes(frieda_ctx* ctx, const uint8_t* commitments, uint32_t n_blobs, uint32_t log_blowup_factor, size_t len,
                                                  uint32_t log_cell, const uint32_t* stripe_index, uint32_t n_stripes, const uint32_t* values,
                                                  const uint8_t* paths, uint8_t* out_bytes, uint8_t* out_status, size_t* n_stripes_used);
+
+/* ---- cell bundles: many cells under one shared Merkle witness -------------------------------------------------------------------
+ * Every opened cell above travels with its own path of log_domain - log_cell siblings, and the paths of the cells one peer asks for
+ * share most of their upper nodes.  A BUNDLE is the answer to one request: k cells of one blob at one log_cell, 1 <= k <=
+ * FRIEDA_MAX_BUNDLE_CELLS, cell indices STRICTLY ASCENDING, values[k][4][2^log_cell] as the cell calls lay them out, and ONE hash witness:
+ * stwo's (MerkleProver::decommit / MerkleVerifier::verify) for the tree cut at level d = log_domain - log_cell with the cell indices as
+ * positions — bottom-up, and within a level ascending, the hash of every child that the verifier cannot compute from the cells.  Its
+ * length depends on the indices alone (frieda_cell_bundle_witness_count): d for one cell, strictly below k * d for k >= 2, 0 when the
+ * bundle holds every cell of the domain.  At log_cell 0 a point is 16 bytes and its path 32 * log_domain, so there the path is almost the
+ * whole message: 64 random cells of a depth-13 tree need 402 hashes instead of 832, 499 need 1659 instead of 6487.
+ * A bundle is accepted or not AS A WHOLE — that is the price of sharing; the per-cell calls stay for callers who want independent cells.
+ * A call carries n_bundles bundles back to back: cell i of the call belongs to bundle b when bundle_first[b] <= i < bundle_first[b + 1];
+ * bundle_first and witness_first have n_bundles + 1 entries each, and witness_first counts in hashes of 32 bytes.  All pointers are host
+ * arrays or handles.
+ * MALFORMED: a bundle that is empty, above the cap, not strictly ascending or holds an index >= 2^(log_domain - log_cell); for the
+ * verifiers also one whose witness_first[b + 1] - witness_first[b] is not the count its indices give.  The verifiers decide that on the
+ * host before anything is hashed (one function for both), never stage such a bundle, and report it in its own status byte: bundles
+ * come from untrusted peers, so a bad one costs only itself.  The provider's call refuses a malformed bundle outright.  FRIEDA_ERR_ARG
+ * is kept for the call's own structure: null pointers, a *_first array that does not start at 0 or that decreases, log_cell or the shape
+ * out of range (0 <= log_cell <= min(log_domain, FRIEDA_MAX_LOG_OPEN_CELL)).  n_bundles == 0 is a no-op.
+ * ACCEPTED: every word is a canonical M31, and the subtree roots of the cells, merged upward with the witness consumed in order, give
+ * exactly the commitment.  With log_cell == log_domain the witness is empty and the one cell's root must be the commitment.
+ * The times of these calls are records, not gates: one wave verifies one bundle, so a call of few large bundles is latency-bound by
+ * design.  Measured on the 128 KiB fixture (a 2^19 codeword), 513 cells of 64 entries as one bundle / as eight bundles, against the
+ * per-cell calls on the same cells in the same run on one MI355X (profiles/r15_cell_bundles.txt, tools/cell_bundles_timing.py): 1673 /
+ * 3132 witness hashes instead of 6669 path hashes; open 0.090 / 0.089 ms against 0.071 ms; GPU verify 0.243 / 0.135 ms against 0.108 ms;
+ * host verify on one core 3.79 / 3.89 ms against 3.52 ms; the whole rebuild 0.67 / 0.56 ms against 0.54 ms.  The bundle form buys bytes,
+ * not time.  Other cell sizes and domains are not measured. */
+#define FRIEDA_MAX_BUNDLE_CELLS 1024
+#define FRIEDA_BUNDLE_REJECTED 0
+#define FRIEDA_BUNDLE_ACCEPTED 1
+#define FRIEDA_BUNDLE_MALFORMED 2
+/* Host only, no context: *n_hashes receives the witness length of one bundle.  FRIEDA_ERR_ARG for a malformed bundle. */
+int frieda_cell_bundle_witness_count(uint32_t log_domain, uint32_t log_cell, const uint32_t* cell_index, uint32_t n_cells, size_t* n_hashes);
+/* Provider: out_values[n_cells][4][2^log_cell] for all cells of the call, the witnesses of the bundles back to back in out_witness
+ * (cap_hashes hashes of room), and out_witness_first[n_bundles + 1].  out_witness == NULL fills out_witness_first only and launches
+ * nothing (out_values may then be NULL too).  One upload (indices, a table row per bundle, a witness offset per bundle and level: the
+ * host computes them from the indices), the launches, one download, one synchronisation.  Like frieda_open_cells the call is NOT cut
+ * into passes, and FRIEDA_ERR_NOMEM when the workspace cannot hold the answer leaves ctx usable.  A malformed bundle, or cap_hashes
+ * below the total, refuses the whole call: FRIEDA_ERR_ARG, outputs untouched, and frieda_last_error names the bundle.  Only reads the
+ * blob: it may be in use by a frieda_prove_seeds job on another context.  FRIEDA_ERR_ARG while a proof is in flight on ctx. */
+int frieda_open_cell_bundles(frieda_ctx* ctx, const frieda_encoded* enc, uint32_t log_cell, const uint32_t* cell_index, const uint32_t* bundle_first,
+                             uint32_t n_bundles, uint32_t* out_values, uint8_t* out_witness, size_t cap_hashes, uint64_t* out_witness_first);
+/* Client, host verifier: no context, one core; a bottom-up merge written independently of the kernel.  One status byte per bundle
+ * (FRIEDA_BUNDLE_*). */
+int frieda_verify_cell_bundles(const uint8_t commitment[32], uint32_t log_domain, uint32_t log_cell, const uint32_t* cell_index, const uint32_t* bundle_first,
+                               uint32_t n_bundles, const uint32_t* values, const uint8_t* witness, const uint64_t* witness_first, uint8_t* out_status);
+/* Client, the same status bytes from the GPU (bundles.hip): per pass the subtree roots of all cells as frieda_verify_cells_many computes
+ * them, then one wave per bundle merges its (position, hash) list upward.  Stages the well-formed bundles through the workspace in
+ * passes under the budget of frieda_verify_cells_many; a bundle never straddles two passes.  FRIEDA_ERR_ARG while a proof is in flight
+ * on ctx. */
+int frieda_verify_cell_bundles_many(frieda_ctx* ctx, const uint8_t commitment[32], uint32_t log_domain, uint32_t log_cell, const uint32_t* cell_index,
+                                    const uint32_t* bundle_first, uint32_t n_bundles, const uint32_t* values, const uint8_t* witness,
+                                    const uint64_t* witness_first, uint8_t* out_status);
+/* The client's whole flow from bundles: verify them as frieda_verify_cell_bundles_many does, pool the cells of the ACCEPTED bundles,
+ * de-duplicate by index, and rebuild as frieda_reconstruct_from_opened_cells does — the same cell counts needed, *n_cells_used = the
+ * distinct cells of accepted bundles, FRIEDA_ERR_ARG with out_bytes untouched when they are too few or the result does not commit to
+ * commitment (a wrong len).  out_status[n_bundles] is always valid.  A cell of a rejected or malformed bundle is never used. */
+int frieda_reconstruct_from_cell_bundles(frieda_ctx* ctx, const uint8_t commitment[32], uint32_t log_blowup_factor, size_t len, uint32_t log_cell,
+                                         const uint32_t* cell_index, const uint32_t* bundle_first, uint32_t n_bundles, const uint32_t* values,
+                                         const uint8_t* witness, const uint64_t* witness_first, uint8_t* out_bytes, uint8_t* out_status,
+                                         size_t* n_cells_used);
 
 /* ---- batch policy: how a stream of equal-length blobs is cut into batched calls ("bytes in flight") -------------------------
  * Every kernel of a batched call covers all its blobs, so the launch / Fiat-Shamir latency chain is paid once per call: small
