@@ -157,6 +157,13 @@ extern "C" {
     pub fn frieda_verify_cell_bundles(commitment: *const u8, log_domain: u32, log_cell: u32, cell_index: *const u32, bundle_first: *const u32, n_bundles: u32, values: *const u32, witness: *const u8, witness_first: *const u64, out_status: *mut u8) -> c_int;
     pub fn frieda_verify_cell_bundles_many(ctx: *mut frieda_ctx, commitment: *const u8, log_domain: u32, log_cell: u32, cell_index: *const u32, bundle_first: *const u32, n_bundles: u32, values: *const u32, witness: *const u8, witness_first: *const u64, out_status: *mut u8) -> c_int;
     pub fn frieda_reconstruct_from_cell_bundles(ctx: *mut frieda_ctx, commitment: *const u8, log_blowup_factor: u32, len: usize, log_cell: u32, cell_index: *const u32, bundle_first: *const u32, n_bundles: u32, values: *const u32, witness: *const u8, witness_first: *const u64, out_bytes: *mut u8, out_status: *mut u8, n_cells_used: *mut usize) -> c_int;
+    // stripe bundles: k stripes of a block of n_blobs blobs (stripe indices strictly ascending) under one shared hash witness per blob;
+    // values[stripes][n_blobs][4][2^log_cell]; witness_first counts hashes per blob, bundle b's block starts at hash n_blobs * witness_first[b],
+    // blob j's piece at j * W_b inside it; out_status[n_bundles][n_blobs]
+    pub fn frieda_open_stripe_bundles(ctx: *mut frieda_ctx, encs: *const *const frieda_encoded, n_blobs: u32, log_cell: u32, stripe_index: *const u32, bundle_first: *const u32, n_bundles: u32, out_values: *mut u32, out_witness: *mut u8, cap_hashes: usize, out_witness_first: *mut u64) -> c_int;
+    pub fn frieda_verify_stripe_bundles(commitments: *const u8, n_blobs: u32, log_domain: u32, log_cell: u32, stripe_index: *const u32, bundle_first: *const u32, n_bundles: u32, values: *const u32, witness: *const u8, witness_first: *const u64, out_status: *mut u8) -> c_int;
+    pub fn frieda_verify_stripe_bundles_many(ctx: *mut frieda_ctx, commitments: *const u8, n_blobs: u32, log_domain: u32, log_cell: u32, stripe_index: *const u32, bundle_first: *const u32, n_bundles: u32, values: *const u32, witness: *const u8, witness_first: *const u64, out_status: *mut u8) -> c_int;
+    pub fn frieda_reconstruct_blobs_from_stripe_bundles(ctx: *mut frieda_ctx, commitments: *const u8, n_blobs: u32, log_blowup_factor: u32, len: usize, log_cell: u32, stripe_index: *const u32, bundle_first: *const u32, n_bundles: u32, values: *const u32, witness: *const u8, witness_first: *const u64, out_bytes: *mut u8, out_status: *mut u8, n_stripes_used: *mut usize) -> c_int;
 
     // struct Proof
     pub fn frieda_proof_free(p: *mut frieda_proof);

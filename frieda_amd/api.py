@@ -644,6 +644,47 @@ class Context:
             raise
         return [out[b * n_bytes : (b + 1) * n_bytes].tobytes() for b in range(K)], status[: S * K].reshape(S, K), n.value
 
+    # ---- stripe bundles: a block's stripes under one shared witness per blob (open_stripe_bundles is the provider's half) ----
+    def verify_stripe_bundles_many(self, commitments, log_domain, log_cell, bundles, values, witness, witness_first):
+        """One status byte per (bundle, blob), numpy uint8 [n_bundles, K], verified on the device; the bytes verify_stripe_bundles()
+        gives.  bundles: one ascending stripe index list per bundle; values / witness / witness_first as open_stripe_bundles returns them."""
+        com = _commitment_table(commitments)
+        K = len(com) // 32
+        idx, first, val, wit, wfirst = _stripe_bundle_arrays(K, log_cell, bundles, values, witness, witness_first)
+        count = len(first) - 1
+        status = np.zeros(max(count * K, 1), dtype=np.uint8)
+        _check(
+            self._L.frieda_verify_stripe_bundles_many(self._h, com.ctypes.data, K, log_domain, log_cell, idx.ctypes.data, first.ctypes.data, count,
+                                                      val.ctypes.data, wit.ctypes.data, wfirst.ctypes.data, status.ctypes.data),
+            self._h,
+        )
+        return status[: count * K].reshape(count, K)
+
+    def reconstruct_blobs_from_stripe_bundles(self, commitments, log_blowup_factor, n_bytes, log_cell, bundles, values, witness, witness_first):
+        """Verify the stripe bundles of a block, use the bundles whose K pieces are all accepted and rebuild all K blobs in one
+        reconstruction: (list of K bytes, status uint8 [n_bundles, K], n_stripes_used).  Raises FriedaError (with .n_stripes_used and
+        .bundle_status set) when the stripes of the used bundles do not suffice or a blob does not commit to its commitment."""
+        com = _commitment_table(commitments)
+        K = len(com) // 32
+        idx, first, val, wit, wfirst = _stripe_bundle_arrays(K, log_cell, bundles, values, witness, witness_first)
+        count = len(first) - 1
+        status = np.zeros(max(count * K, 1), dtype=np.uint8)
+        out = np.zeros(max(n_bytes * K, 1), dtype=np.uint8)
+        n = C.c_size_t(0)
+        try:
+            _check(
+                self._L.frieda_reconstruct_blobs_from_stripe_bundles(
+                    self._h, com.ctypes.data, K, log_blowup_factor, n_bytes, log_cell, idx.ctypes.data, first.ctypes.data, count, val.ctypes.data,
+                    wit.ctypes.data, wfirst.ctypes.data, out.ctypes.data, status.ctypes.data, C.byref(n)
+                ),
+                self._h,
+            )
+        except FriedaError as e:
+            e.n_stripes_used = n.value
+            e.bundle_status = status[: count * K].reshape(count, K)
+            raise
+        return [out[b * n_bytes : (b + 1) * n_bytes].tobytes() for b in range(K)], status[: count * K].reshape(count, K), n.value
+
 
 def codec_log_size(n_bytes):
     """log2 of the coefficients per column of a blob of n_bytes (frieda_codec_shape)."""
@@ -692,6 +733,29 @@ def _bundle_arrays(log_cell, bundles, values, witness, witness_first):
     if val.size != (len(idx) * 4) << log_cell:
         raise FriedaError(_lib.ERR_ARG, "values do not have the shape of the cell list")
     if len(wfirst) != len(first) or (len(wfirst) and wit.size < 32 * int(wfirst.max())):
+        raise FriedaError(_lib.ERR_ARG, "witness_first: one entry per bundle and one more, none beyond the witness")
+    if wit.size == 0:
+        wit = np.zeros(1, dtype=np.uint8)
+    if val.size == 0:
+        val = np.zeros(1, dtype=np.uint32)
+    if idx.size == 0:
+        idx = np.zeros(1, dtype=np.uint32)
+    return idx, first, val, wit, wfirst
+
+
+def _stripe_bundle_arrays(n_blobs, log_cell, bundles, values, witness, witness_first):
+    """the host arrays of a stripe-bundles call: as _bundle_arrays with K blobs behind every stripe and every witness hash"""
+    if not 0 <= log_cell <= _lib.MAX_LOG_OPEN_CELL:
+        raise FriedaError(_lib.ERR_ARG, "log_cell out of range")
+    if n_blobs < 1:
+        raise FriedaError(_lib.ERR_ARG, "no commitments")
+    idx, first = _bundle_index_arrays(bundles)
+    val = np.ascontiguousarray(values, dtype=np.uint32).reshape(-1)
+    wit = np.ascontiguousarray(witness, dtype=np.uint8).reshape(-1)
+    wfirst = np.ascontiguousarray(witness_first, dtype=np.uint64).reshape(-1)
+    if val.size != (len(idx) * n_blobs * 4) << log_cell:
+        raise FriedaError(_lib.ERR_ARG, "values do not have the shape of the stripe list")
+    if len(wfirst) != len(first) or (len(wfirst) and wit.size < 32 * n_blobs * int(wfirst.max())):
         raise FriedaError(_lib.ERR_ARG, "witness_first: one entry per bundle and one more, none beyond the witness")
     if wit.size == 0:
         wit = np.zeros(1, dtype=np.uint8)
@@ -1313,3 +1377,52 @@ def verify_cells_blobs_many(commitments, log_domain, log_cell, blob_index, cell_
 def reconstruct_blobs_from_opened_stripes(commitments, log_blowup_factor, n_bytes, log_cell, stripe_index, values, paths):
     """frieda_reconstruct_blobs_from_opened_stripes on the default context: (list of bytes, status [S, K], n_stripes_used)."""
     return default_context().reconstruct_blobs_from_opened_stripes(commitments, log_blowup_factor, n_bytes, log_cell, stripe_index, values, paths)
+
+
+def open_stripe_bundles(ctx, encs, log_cell, bundles):
+    """Stripes of a block of K encoded blobs in bundles (one strictly ascending stripe index list each), every bundle under ONE shared
+    Merkle witness per blob (frieda_open_stripe_bundles on `ctx`): (values uint32 [S, K, 4, 2^log_cell] over all stripes of the call,
+    witness uint8 [K * H, 32] — bundle b's block starts at hash K * witness_first[b], blob j's piece at j * W_b inside it —,
+    witness_first uint64 [n_bundles + 1] in hashes per blob)."""
+    encs = list(encs)
+    if not encs:
+        raise FriedaError(_lib.ERR_ARG, "open_stripe_bundles: no blobs")
+    K = len(encs)
+    idx, first = _bundle_index_arrays(bundles)
+    nb = len(first) - 1
+    L = _lib.lib()
+    handles = (C.c_void_p * K)(*[e._handle() for e in encs])
+    wfirst = np.zeros(nb + 1, dtype=np.uint64)
+    values = np.zeros((len(idx), K, 4, 1 << log_cell), dtype=np.uint32)
+    if nb == 0:
+        return values, np.zeros((0, 32), dtype=np.uint8), wfirst
+    iptr = idx.ctypes.data if idx.size else None
+    _check(L.frieda_open_stripe_bundles(ctx._h, handles, K, log_cell, iptr, first.ctypes.data, nb, None, None, 0, wfirst.ctypes.data), ctx._h)
+    total = K * int(wfirst[-1])
+    witness = np.zeros((max(total, 1), 32), dtype=np.uint8)
+    _check(L.frieda_open_stripe_bundles(ctx._h, handles, K, log_cell, iptr, first.ctypes.data, nb, values.ctypes.data, witness.ctypes.data, total,
+                                        wfirst.ctypes.data), ctx._h)
+    return values, witness[:total], wfirst
+
+
+def verify_stripe_bundles(commitments, log_domain, log_cell, bundles, values, witness, witness_first):
+    """The host verifier of stripe bundles (frieda_verify_stripe_bundles: no context, one core): one status byte per (bundle, blob),
+    numpy uint8 [n_bundles, K]."""
+    com = _commitment_table(commitments)
+    K = len(com) // 32
+    idx, first, val, wit, wfirst = _stripe_bundle_arrays(K, log_cell, bundles, values, witness, witness_first)
+    count = len(first) - 1
+    status = np.zeros(max(count * K, 1), dtype=np.uint8)
+    _check(_lib.lib().frieda_verify_stripe_bundles(com.ctypes.data, K, log_domain, log_cell, idx.ctypes.data, first.ctypes.data, count, val.ctypes.data,
+                                                   wit.ctypes.data, wfirst.ctypes.data, status.ctypes.data))
+    return status[: count * K].reshape(count, K)
+
+
+def verify_stripe_bundles_many(commitments, log_domain, log_cell, bundles, values, witness, witness_first):
+    """frieda_verify_stripe_bundles_many on the default context: status [n_bundles, K], verified on the device."""
+    return default_context().verify_stripe_bundles_many(commitments, log_domain, log_cell, bundles, values, witness, witness_first)
+
+
+def reconstruct_blobs_from_stripe_bundles(commitments, log_blowup_factor, n_bytes, log_cell, bundles, values, witness, witness_first):
+    """frieda_reconstruct_blobs_from_stripe_bundles on the default context: (list of bytes, status [n_bundles, K], n_stripes_used)."""
+    return default_context().reconstruct_blobs_from_stripe_bundles(commitments, log_blowup_factor, n_bytes, log_cell, bundles, values, witness, witness_first)

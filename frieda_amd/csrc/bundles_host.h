@@ -119,9 +119,10 @@ struct BundleScratch {
 
 // One WELL-FORMED bundle (bundle_malformed is null): every word canonical, and the cells' subtree roots merged upward with the
 // witness consumed in order give exactly `want`.  n_witness is what the caller holds; nothing is read beyond it.
+// n_blobs (default 1): cell i's values lie n_blobs cells apart — one blob's cells of a stripe bundle, whose values are stripe-major.
 inline bool bundle_accept(const uint32_t want[8], uint32_t log_domain, uint32_t log_cell, const uint32_t* cell_index, size_t k, const uint32_t* values,
-                          const uint8_t* witness, uint64_t n_witness, BundleScratch& sc) {
-    const size_t vw = (size_t)4 << log_cell;
+                          const uint8_t* witness, uint64_t n_witness, BundleScratch& sc, size_t n_blobs = 1) {
+    const size_t vw = ((size_t)4 << log_cell) * n_blobs;
     sc.pos.resize(k);
     sc.hash.resize(8 * k);
     for (size_t i = 0; i < k; i++) {
@@ -176,6 +177,51 @@ inline void verify_cell_bundles_host(const uint8_t commitment[32], uint32_t log_
         const uint8_t* wit = nw ? witness + 32 * witness_first[b] : nullptr;
         out_status[b] = bundle_accept(want, log_domain, log_cell, cell_index + first, k, values + first * vw, wit, nw, sc) ? FRIEDA_BUNDLE_ACCEPTED
                                                                                                                          : FRIEDA_BUNDLE_REJECTED;
+    }
+}
+
+// ---- stripe bundles: k stripes of a block of n_blobs blobs (a stripe is cell j of every blob) with one witness per blob ----
+// values [stripes][n_blobs][4][2^log_cell]; witness_first counts hashes PER BLOB: bundle b's block starts at hash n_blobs * witness_first[b],
+// blob j's piece is the W_b = witness_first[b + 1] - witness_first[b] hashes at j * W_b inside it, and is that blob's cell-bundle witness.
+// the argument rule of the verifiers and the rebuild: null pointers and the call's own structure; null when it holds
+inline const char* stripe_bundles_args_error(const uint8_t* commitments, uint32_t n_blobs, uint32_t max_blobs, uint32_t log_domain, uint32_t log_cell,
+                                             const uint32_t* stripe_index, const uint32_t* bundle_first, uint32_t n_bundles, const uint32_t* values,
+                                             const uint8_t* witness, const uint64_t* witness_first, const uint8_t* out_status) {
+    if (n_blobs == 0 || n_blobs > max_blobs) return "n_blobs out of range";
+    if (!commitments || !bundle_first || !witness_first || !out_status) return "null argument";
+    if (const char* bad = bundle_shape_error(log_domain, log_cell)) return bad;
+    if (const char* bad = bundles_call_error(bundle_first, witness_first, n_bundles)) return bad;
+    if (bundle_first[n_bundles] && (!stripe_index || !values)) return "null argument";
+    if (witness_first[n_bundles] && !witness) return "null argument";
+    if (witness_first[n_bundles] > ((uint64_t)1 << 40) / n_blobs) return "witness_first out of range";
+    return nullptr;
+}
+
+// Every (bundle, blob) of a structurally sound call: out_status[n_bundles][n_blobs].  MALFORMED depends on the indices and W_b alone: it
+// is decided once per bundle and written to the bundle's whole row; else byte (b, j) is the single-blob verifier's on blob j's piece.
+inline void verify_stripe_bundles_host(const uint8_t* commitments, uint32_t n_blobs, uint32_t log_domain, uint32_t log_cell, const uint32_t* stripe_index,
+                                       const uint32_t* bundle_first, uint32_t n_bundles, const uint32_t* values, const uint8_t* witness,
+                                       const uint64_t* witness_first, uint8_t* out_status) {
+    std::vector<uint8_t> cls(n_bundles);
+    bundles_classify(log_domain, log_cell, stripe_index, bundle_first, n_bundles, witness_first, cls.data());
+    BundleScratch sc;
+    const size_t vw = (size_t)4 << log_cell;
+    for (uint32_t b = 0; b < n_bundles; b++) {
+        uint8_t* st = out_status + (size_t)b * n_blobs;
+        if (cls[b] == FRIEDA_BUNDLE_MALFORMED) {
+            memset(st, FRIEDA_BUNDLE_MALFORMED, n_blobs);
+            continue;
+        }
+        const size_t first = bundle_first[b], k = bundle_first[b + 1] - first;
+        const uint64_t nw = witness_first[b + 1] - witness_first[b];
+        for (uint32_t j = 0; j < n_blobs; j++) {
+            uint32_t want[8];
+            memcpy(want, commitments + 32 * (size_t)j, 32);
+            const uint8_t* wit = nw ? witness + 32 * (n_blobs * witness_first[b] + j * nw) : nullptr;
+            st[j] = bundle_accept(want, log_domain, log_cell, stripe_index + first, k, values + (first * n_blobs + j) * vw, wit, nw, sc, n_blobs)
+                        ? FRIEDA_BUNDLE_ACCEPTED
+                        : FRIEDA_BUNDLE_REJECTED;
+        }
     }
 }
 

@@ -12,6 +12,11 @@
 // row) | values, cell-major as given | the witness as given; every piece from a 256-byte boundary.  Behind it in the pinned block: one
 // status word per bundle as it comes back, then the gather table the host builds from the statuses (two words per cell of an accepted
 // bundle).  In the arena behind the image: roots (32 bytes a cell), bad (a word a cell), the status words, the gather table.
+//
+// Stripe bundles (stripe_bundles_host.cpp) run the same arithmetic with a factor n_blobs (default 1: the single-blob form, unchanged):
+// a bundle's k stripes are cell j of EVERY blob, so it stages its table row and its indices once and its values and its witness n_blobs
+// times, 12 + cells * 4 + n_blobs * (cells * vb + 32 * hashes) bytes with `hashes` counted per blob; roots and bad are per (stripe, blob)
+// cell, there is a status word per (bundle, blob), and the gather table has a row per stripe.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -27,13 +32,15 @@ struct BundleSize {
 
 inline size_t bundles_al(size_t b) { return (b + 255) & ~(size_t)255; }
 
-inline size_t bundle_staged_bytes(uint32_t log_cell, const BundleSize& z) { return 12 + (size_t)z.cells * (4 + ((size_t)16 << log_cell)) + 32 * (size_t)z.hashes; }
+inline size_t bundle_staged_bytes(uint32_t log_cell, const BundleSize& z, size_t n_blobs = 1) {
+    return 12 + (size_t)z.cells * 4 + n_blobs * ((size_t)z.cells * ((size_t)16 << log_cell) + 32 * (size_t)z.hashes);
+}
 
 // the end (exclusive) of the pass that begins at bundle `first` < n
-inline size_t bundles_pass_end(uint32_t log_cell, const BundleSize* sz, size_t n, size_t first, size_t pass_bytes) {
-    size_t end = first + 1, sum = bundle_staged_bytes(log_cell, sz[first]);
+inline size_t bundles_pass_end(uint32_t log_cell, const BundleSize* sz, size_t n, size_t first, size_t pass_bytes, size_t n_blobs = 1) {
+    size_t end = first + 1, sum = bundle_staged_bytes(log_cell, sz[first], n_blobs);
     while (end < n) {
-        const size_t next = bundle_staged_bytes(log_cell, sz[end]);
+        const size_t next = bundle_staged_bytes(log_cell, sz[end], n_blobs);
         if (next > pass_bytes || sum > pass_bytes - next) break;
         sum += next, end++;
     }
@@ -50,10 +57,10 @@ inline BundlesPassCount bundles_pass_count(const BundleSize* sz, size_t first, s
     return c;
 }
 // the component-wise largest pass of the call: what the one plan of the call is made from
-inline BundlesPassCount bundles_call_count(uint32_t log_cell, const BundleSize* sz, size_t n, size_t pass_bytes) {
+inline BundlesPassCount bundles_call_count(uint32_t log_cell, const BundleSize* sz, size_t n, size_t pass_bytes, size_t n_blobs = 1) {
     BundlesPassCount m;
     for (size_t first = 0; first < n;) {
-        const size_t end = bundles_pass_end(log_cell, sz, n, first, pass_bytes);
+        const size_t end = bundles_pass_end(log_cell, sz, n, first, pass_bytes, n_blobs);
         const BundlesPassCount c = bundles_pass_count(sz, first, end);
         m.cells = std::max(m.cells, c.cells), m.bundles = std::max(m.bundles, c.bundles), m.hashes = std::max(m.hashes, c.hashes);
         m.max_cells = std::max(m.max_cells, c.max_cells);
@@ -68,11 +75,12 @@ struct BundlesPassPlan {
     size_t a_in, a_roots, a_bad, a_res, a_tab, arena;     // arena offsets, `arena` bytes in all
 };
 
-inline BundlesPassPlan bundles_pass_plan(uint32_t log_cell, const BundlesPassCount& c) {
+// c counts indices (`cells`) and per-blob hashes; n_blobs multiplies what a bundle holds once per blob
+inline BundlesPassPlan bundles_pass_plan(uint32_t log_cell, const BundlesPassCount& c, size_t n_blobs = 1) {
     BundlesPassPlan p;
     p.i_idx = 0, p.i_tab = bundles_al(4 * c.cells), p.i_val = p.i_tab + bundles_al(12 * c.bundles);
-    p.i_wit = p.i_val + bundles_al(((size_t)16 << log_cell) * c.cells), p.in_bytes = p.i_wit + bundles_al(32 * c.hashes);
-    p.res_bytes = 4 * c.bundles;
+    p.i_wit = p.i_val + bundles_al(((size_t)16 << log_cell) * c.cells * n_blobs), p.in_bytes = p.i_wit + bundles_al(32 * c.hashes * n_blobs);
+    p.res_bytes = 4 * c.bundles * n_blobs;
     p.p_res = p.in_bytes, p.p_tab = p.p_res + bundles_al(p.res_bytes), p.pinned = p.p_tab + 8 * c.cells;
     size_t off = 0;
     auto take = [&off](size_t bytes) {
@@ -80,7 +88,7 @@ inline BundlesPassPlan bundles_pass_plan(uint32_t log_cell, const BundlesPassCou
         off = bundles_al(off + bytes);
         return o;
     };
-    p.a_in = take(p.in_bytes), p.a_roots = take(32 * c.cells), p.a_bad = take(4 * c.cells), p.a_res = take(p.res_bytes), p.a_tab = take(8 * c.cells);
+    p.a_in = take(p.in_bytes), p.a_roots = take(32 * c.cells * n_blobs), p.a_bad = take(4 * c.cells * n_blobs), p.a_res = take(p.res_bytes), p.a_tab = take(8 * c.cells);
     p.arena = off;
     return p;
 }

@@ -200,15 +200,15 @@ __global__ __launch_bounds__(CL_THREADS) void cells_stripe_accept_kernel(const u
 
 // row r of the table: (stripe of the pass, entry of the pool); 16-byte copies (a cell is at least four words)
 __global__ __launch_bounds__(CL_THREADS) void cells_stripe_gather_kernel(const uint32_t* __restrict__ tab, uint32_t n_rows, const uint32_t* __restrict__ values,
-                                                                         const uint32_t* __restrict__ idx, uint32_t n_blobs, uint32_t log_cell,
-                                                                         uint32_t* __restrict__ pool_idx, uint32_t* __restrict__ pool_val) {
+                                                                         const uint32_t* __restrict__ idx, uint32_t idx_stride, uint32_t n_blobs,
+                                                                         uint32_t log_cell, uint32_t* __restrict__ pool_idx, uint32_t* __restrict__ pool_val) {
     const size_t e = (size_t)blockIdx.x * CL_THREADS + threadIdx.x;
     const size_t units = (size_t)n_blobs << log_cell;  // 16-byte units of a stripe
     if (e >= (size_t)n_rows * units) return;
     const size_t row = e / units, u = e - row * units;
     const size_t src = tab[2 * row], dst = tab[2 * row + 1];
     reinterpret_cast<uint4*>(pool_val)[dst * units + u] = reinterpret_cast<const uint4*>(values)[src * units + u];
-    if (u == 0) pool_idx[dst] = idx[src * n_blobs];
+    if (u == 0) pool_idx[dst] = idx[src * idx_stride];
 }
 
 unsigned blocks_for(size_t units) { return (unsigned)((units + CL_THREADS - 1) / CL_THREADS); }
@@ -259,6 +259,7 @@ void verify_launch(const Launch& L, const CellsVerifyArgs& a, const uint32_t* d_
 void cells_open(const Launch& L, const CellsOpenArgs& a) { open_launch(L, a); }
 void cells_open_values(const Launch& L, const CellsOpenArgs& a) { open_values_launch(L, a); }
 void cells_open_blobs(const Launch& L, const CellsOpenBlobsArgs& a) { open_launch(L, a); }
+void cells_open_blobs_values(const Launch& L, const CellsOpenBlobsArgs& a) { open_values_launch(L, a); }
 
 void cells_verify(const Launch& L, const CellsVerifyArgs& a) { verify_launch<false>(L, a, nullptr, nullptr); }
 void cells_roots(const Launch& L, const CellsVerifyArgs& a) {
@@ -283,12 +284,12 @@ void cells_stripe_accept(const Launch& L, const uint32_t* d_status, uint32_t n_s
     cells_stripe_accept_kernel<<<(n_stripes + per - 1) / per, CL_THREADS, 0, L.stream>>>(d_status, n_stripes, n_blobs, d_accept);
 }
 
-void cells_stripe_gather(const Launch& L, const uint32_t* d_tab, uint32_t n_rows, const uint32_t* d_values, const uint32_t* d_idx, uint32_t n_blobs,
-                         uint32_t log_cell, uint32_t* d_pool_idx, uint32_t* d_pool_val) {
+void cells_stripe_gather(const Launch& L, const uint32_t* d_tab, uint32_t n_rows, const uint32_t* d_values, const uint32_t* d_idx, uint32_t idx_stride,
+                         uint32_t n_blobs, uint32_t log_cell, uint32_t* d_pool_idx, uint32_t* d_pool_val) {
     if (!n_rows) return;
     Scope scope(L, "cells_stripe_gather", 0.0);
-    cells_stripe_gather_kernel<<<blocks_for((size_t)n_rows * ((size_t)n_blobs << log_cell)), CL_THREADS, 0, L.stream>>>(d_tab, n_rows, d_values, d_idx, n_blobs,
-                                                                                                                      log_cell, d_pool_idx, d_pool_val);
+    cells_stripe_gather_kernel<<<blocks_for((size_t)n_rows * ((size_t)n_blobs << log_cell)), CL_THREADS, 0, L.stream>>>(d_tab, n_rows, d_values, d_idx, idx_stride,
+                                                                                                                      n_blobs, log_cell, d_pool_idx, d_pool_val);
 }
 
 }  // namespace k

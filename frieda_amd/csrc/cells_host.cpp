@@ -158,7 +158,7 @@ int verify_cells_passes(Ctx* ctx, const uint8_t* commitments, uint32_t n_blobs, 
             const uint32_t* d_tab = reinterpret_cast<const uint32_t*>(ctx->arena + p.a_tab);
             FR_HIP(ctx, hipMemcpyAsync(ctx->arena + p.a_tab, tab, 8 * (size_t)n_rows, hipMemcpyHostToDevice, s));
             if (shape.stripes)
-                k::cells_stripe_gather(ctx->launch(), d_tab, n_rows, va.values, va.idx, n_blobs, log_cell, pool->d_idx(), pool->d_val());
+                k::cells_stripe_gather(ctx->launch(), d_tab, n_rows, va.values, va.idx, n_blobs, n_blobs, log_cell, pool->d_idx(), pool->d_val());
             else
                 k::cells_gather(ctx->launch(), d_tab, n_rows, va.values, va.idx, log_cell, pool->d_idx(), pool->d_val());
             FR_HIP(ctx, hipGetLastError());
@@ -221,6 +221,28 @@ const char* cells_blobs_args_error(uint32_t n_blobs, uint32_t log_domain, uint32
 }
 
 }  // namespace
+
+// The tail of the block rebuilds (opened stripes, stripe bundles): one point reconstruction over 4 * n_blobs columns, commit_batch over
+// the rebuilt bytes, every root against its commitment.  *n_distinct: the distinct stripes of the pool (on an error too).
+int rebuild_blobs_from_stripes(frieda_ctx* ctx, const CellPool& pool, const uint8_t* commitments, uint32_t n_blobs, uint32_t log_blowup_factor, size_t len,
+                               uint32_t log_cell, uint8_t* out_bytes, uint32_t* n_distinct) {
+    const uint32_t L = codec_shape(len).log_size, n = L + log_blowup_factor;
+    // the rebuilt bytes stay on the device for the commitment check: blob b at b * stride
+    const size_t stride = std::max<size_t>(256, (len + 255) & ~(size_t)255);
+    std::vector<uint8_t> roots(32 * (size_t)n_blobs), bytes(len * n_blobs);
+    DevBuf out;
+    int rc = out.alloc(&ctx->c, stride * n_blobs, "poison(rebuilt bytes)");
+    if (rc != FRIEDA_OK) return rc;
+    uint8_t* d_out = static_cast<uint8_t*>(out.p);
+    rc = reconstruct_pooled(ctx, pool.d_val(), pool.d_idx(), (uint32_t)pool.n, n_blobs, log_cell, L, n, len, d_out, stride, n_distinct);
+    if (rc == FRIEDA_OK) rc = commit_batch(&ctx->c, d_out, stride, len, n_blobs, true, log_blowup_factor, roots.data());
+    if (rc == FRIEDA_OK && len && hipMemcpy2D(bytes.data(), len, d_out, stride, len, n_blobs, hipMemcpyDeviceToHost) != hipSuccess)
+        rc = ctx->c.hip_fail(hipGetLastError(), "hipMemcpy2D(rebuilt bytes)");
+    (void)hipStreamSynchronize(ctx->c.stream);  // (before the buffer goes, on the error paths too)
+    out.release();
+    if (rc != FRIEDA_OK) return rc;
+    return rebuilt_accept(&ctx->c, roots.data(), commitments, n_blobs, nullptr, bytes, out_bytes);
+}
 
 const char* cells_args_error(uint32_t log_domain, uint32_t log_cell, const uint32_t* cell_index, uint32_t n_cells) {
     if (log_domain > FRIEDA_MAX_LOG_DOMAIN) return "log_domain out of range";
@@ -381,23 +403,9 @@ int frieda_reconstruct_blobs_from_opened_stripes(frieda_ctx* ctx, const uint8_t*
     int rc = verify_cells_passes(&ctx->c, commitments, n_blobs, n, log_cell, nullptr, stripe_index, n_stripes * n_blobs, values, paths, out_status, &pool);
     if (rc != FRIEDA_OK) return rc;
     if (pool.n == 0) return too_few();
-    // the rebuilt bytes stay on the device for the commitment check: blob b at b * stride
-    const size_t stride = std::max<size_t>(256, (len + 255) & ~(size_t)255);
-    std::vector<uint8_t> roots(32 * (size_t)n_blobs), bytes(len * n_blobs);
-    DevBuf out;
-    rc = out.alloc(&ctx->c, stride * n_blobs, "poison(rebuilt bytes)");
-    if (rc != FRIEDA_OK) return rc;
-    uint8_t* d_out = static_cast<uint8_t*>(out.p);
-    rc = reconstruct_pooled(ctx, pool.d_val(), pool.d_idx(), (uint32_t)pool.n, n_blobs, log_cell, L, n, len, d_out, stride, &nd);
+    rc = rebuild_blobs_from_stripes(ctx, pool, commitments, n_blobs, log_blowup_factor, len, log_cell, out_bytes, &nd);
     *n_stripes_used = nd;
-    if (rc == FRIEDA_OK) rc = commit_batch(&ctx->c, d_out, stride, len, n_blobs, true, log_blowup_factor, roots.data());
-    if (rc == FRIEDA_OK && len && hipMemcpy2D(bytes.data(), len, d_out, stride, len, n_blobs, hipMemcpyDeviceToHost) != hipSuccess)
-        rc = ctx->c.hip_fail(hipGetLastError(), "hipMemcpy2D(rebuilt bytes)");
-    (void)hipStreamSynchronize(ctx->c.stream);  // (before the buffer goes, on the error paths too)
-    out.release();
-    if (rc == FRIEDA_ERR_ARG && nd < need) return too_few();
-    if (rc != FRIEDA_OK) return rc;
-    return rebuilt_accept(&ctx->c, roots.data(), commitments, n_blobs, nullptr, bytes, out_bytes);
+    return rc == FRIEDA_ERR_ARG && nd < need ? too_few() : rc;
     FR_GUARD_END(ctx)
 }
 

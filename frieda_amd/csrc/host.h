@@ -324,6 +324,10 @@ struct CellPool : DevPool {};
 // the argument rule of every cells entry point: log_cell <= min(log_domain, FRIEDA_MAX_LOG_OPEN_CELL), every index < 2^(log_domain - log_cell);
 // null when it holds, else what is wrong
 const char* cells_args_error(uint32_t log_domain, uint32_t log_cell, const uint32_t* cell_index, uint32_t n_cells);
+// the tail of the block rebuilds (opened stripes, stripe bundles): the pool's fully accepted stripes -> one point reconstruction over
+// 4 * n_blobs columns, commit_batch, every root against its commitment, out_bytes[n_blobs][len]; *n_distinct also on an error
+int rebuild_blobs_from_stripes(frieda_ctx* ctx, const CellPool& pool, const uint8_t* commitments, uint32_t n_blobs, uint32_t log_blowup_factor, size_t len,
+                               uint32_t log_cell, uint8_t* out_bytes, uint32_t* n_distinct);
 
 // transcript pieces shared by prover and verifier (transcript.cpp)
 void channel_mix_felts(Channel& ch, const std::vector<QM31>& felts);

@@ -440,15 +440,17 @@ struct CellsOpenBlobsArgs {
     uint4* out_paths;      // [n_cells][n - log_cell] hashes
 };
 void cells_open_blobs(const Launch& L, const CellsOpenBlobsArgs& a);
+void cells_open_blobs_values(const Launch& L, const CellsOpenBlobsArgs& a);  // the values alone (out_paths is not read)
 // cells_verify with lane `cell` compared against d_commitments[d_bidx[cell]] (8 words per blob, in device memory); a.commitment is not read
 // (the same kernels: cells.hip instantiates them for the one source and for the table)
 void cells_verify_blobs(const Launch& L, const CellsVerifyArgs& a, const uint32_t* d_bidx, const uint32_t* d_commitments);
 // Stripes: the cells of a pass are [n_stripes][n_blobs].  d_accept[s] = 1 iff all n_blobs status words of stripe s are 1, else 0.
 void cells_stripe_accept(const Launch& L, const uint32_t* d_status, uint32_t n_stripes, uint32_t n_blobs, uint32_t* d_accept);
 // stripes of a pass -> the call's pool.  d_tab[n_rows][2]: stripe of the pass, entry of the pool; d_pool_idx[entry] = the stripe's cell index
-// (d_idx of its first cell), d_pool_val[entry][n_blobs][4][2^log_cell]: the d_cells layout of the point reconstruction at 4 * n_blobs columns
-void cells_stripe_gather(const Launch& L, const uint32_t* d_tab, uint32_t n_rows, const uint32_t* d_values, const uint32_t* d_idx, uint32_t n_blobs,
-                         uint32_t log_cell, uint32_t* d_pool_idx, uint32_t* d_pool_val);
+// (d_idx[stripe * idx_stride]: n_blobs where every cell staged its index, 1 where a stripe staged one),
+// d_pool_val[entry][n_blobs][4][2^log_cell]: the d_cells layout of the point reconstruction at 4 * n_blobs columns
+void cells_stripe_gather(const Launch& L, const uint32_t* d_tab, uint32_t n_rows, const uint32_t* d_values, const uint32_t* d_idx, uint32_t idx_stride,
+                         uint32_t n_blobs, uint32_t log_cell, uint32_t* d_pool_idx, uint32_t* d_pool_val);
 
 // ---- bundles.hip: cell bundles, k cells of one blob under one shared Merkle witness (frieda_open_cell_bundles, frieda_verify_cell_bundles_many) ----
 // The witness of a bundle is stwo's hash witness for the tree cut at level d = n - log_cell with the cell indices as positions: the
@@ -483,6 +485,34 @@ struct BundleWalkArgs {
 size_t bundle_walk_lds_bytes(uint32_t max_cells);
 // one wave per bundle: the (position, hash) list in LDS merged upward level by level (walk_dev.h), the root compared with the commitment
 void bundle_walk(const Launch& L, const BundleWalkArgs& a);
+
+// ---- stripe_bundles.hip: stripe bundles, k stripes of a block under one shared witness per blob (frieda_open_stripe_bundles,
+// frieda_verify_stripe_bundles_many) ----
+// The rows are BundleRow with `cells` read as stripes: the indices are shared by the n_blobs blobs.  first_hash counts PER BLOB: bundle b's
+// witness block starts at hash n_blobs * first_hash, blob j's piece at j * W inside it, W = the next row's first_hash (or n_hashes) - first_hash.
+struct StripeBundleOpenArgs {
+    const CellsBlobRow* table;  // n_blobs rows, all of domain 2^n (the table cells_open_blobs reads)
+    uint32_t n, log_cell, n_blobs, n_bundles, n_hashes;  // n_hashes: per blob, of all bundles
+    const uint32_t* idx;         // the stripe indices of all bundles, back to back
+    const BundleRow* rows;       // n_bundles rows
+    const uint64_t* level_base;  // [n_bundles][n - log_cell]: where E_s of bundle b, blob 0 starts in out_witness, in hashes (from the host)
+    uint4* out_witness;
+};
+// one wave per (bundle, blob, level): entry r of E_s of blob j goes to out_witness[level_base[b][s - 1] + j * W + r]
+void stripe_bundle_open_witness(const Launch& L, const StripeBundleOpenArgs& a);
+struct StripeBundleWalkArgs {
+    const uint32_t* values;       // LEAF (log_cell 0): [n_cells][4] words, 16-byte aligned; pass cell = stripe * n_blobs + blob
+    const uint32_t* roots;        // else: [8][n_cells] words and bad[n_cells] from cells_roots over the same cells
+    const uint32_t* bad;
+    const uint32_t* idx;          // [stripes of the pass]: one index per stripe
+    const BundleRow* rows;        // [n_bundles]
+    const uint32_t* witness;      // 8 words per hash, laid out as above (the host checked every W)
+    const uint32_t* commitments;  // [n_blobs][8] words, in device memory
+    uint32_t* status;             // out: [n_bundles][n_blobs], 1 = accepted, 0 = rejected
+    uint32_t n, log_cell, n_cells, n_blobs, n_bundles, n_hashes, max_cells;  // n_cells = stripes * n_blobs; max_cells: the largest bundle, in stripes
+};
+// one wave per (bundle, blob), LDS as bundle_walk (bundle_walk_lds_bytes); n_bundles * n_blobs < 2^31
+void stripe_bundle_walk(const Launch& L, const StripeBundleWalkArgs& a);
 
 // ---- opening.hip: Level B openings (frieda_dev_gather*, frieda_merkle_decommit*) ----
 constexpr uint32_t OPEN_BAD_WORD = 0xFFFFFFFFu;   // gathered word of an out-of-range index (device forms only; not a canonical M31)

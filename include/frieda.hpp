@@ -431,6 +431,84 @@ class Context {
         for (size_t b = 0; b < K; b++) blobs[b].assign(out.begin() + b * len, out.begin() + (b + 1) * len);
         return blobs;
     }
+    // ---- stripe bundles: k stripes of a block under one shared hash witness per blob (frieda_open_stripe_bundles,
+    // frieda_verify_stripe_bundles*, frieda_reconstruct_blobs_from_stripe_bundles).  Stripe t of a call belongs to bundle b when
+    // bundle_first[b] <= t < bundle_first[b + 1]; values[stripes][K][4][2^log_cell]; witness_first counts hashes per blob; bundle b's witness
+    // block starts at hash K * witness_first[b], blob j's piece lies j * W_b hashes into it.
+    struct OpenedStripeBundles {
+        std::vector<uint32_t> values;
+        std::vector<uint8_t> witness;         // K * witness_first.back() hashes of 32 bytes
+        std::vector<uint64_t> witness_first;  // [n_bundles + 1]
+    };
+    // the sizes a stripe-bundles call reads: a short array must not reach the library
+    static void check_stripe_bundle_shapes(const char* fn, size_t K, uint32_t log_cell, const std::vector<uint32_t>& stripe_index,
+                                           const std::vector<uint32_t>& bundle_first, size_t n_values, size_t n_witness_bytes,
+                                           const std::vector<uint64_t>* witness_first) {
+        if (K == 0 || bundle_first.empty() || bundle_first.back() > stripe_index.size() || log_cell > FRIEDA_MAX_LOG_OPEN_CELL)
+            throw Error(FRIEDA_ERR_ARG, std::string(fn) + ": bundle_first has n_bundles + 1 entries, none beyond the stripe list");
+        if (!witness_first) return;
+        if (witness_first->size() != bundle_first.size() || n_values != ((stripe_index.size() * K * 4) << log_cell))
+            throw Error(FRIEDA_ERR_ARG, std::string(fn) + ": values / witness_first do not have the shape of the stripe list");
+        for (uint64_t w : *witness_first)
+            if (w > n_witness_bytes / 32 / K) throw Error(FRIEDA_ERR_ARG, std::string(fn) + ": witness_first beyond the witness");
+    }
+    OpenedStripeBundles open_stripe_bundles(const std::vector<const Encoded*>& encs, uint32_t log_cell, const std::vector<uint32_t>& stripe_index,
+                                            const std::vector<uint32_t>& bundle_first) {
+        std::vector<const frieda_encoded*> handles;
+        for (const Encoded* e : encs) handles.push_back(e ? e->handle() : nullptr);
+        check_stripe_bundle_shapes("open_stripe_bundles", encs.size(), log_cell, stripe_index, bundle_first, 0, 0, nullptr);
+        const uint32_t nb = (uint32_t)bundle_first.size() - 1, K = (uint32_t)handles.size();
+        OpenedStripeBundles out;
+        out.witness_first.assign(nb + 1, 0);
+        if (nb == 0) return out;
+        check(frieda_open_stripe_bundles(h_, handles.data(), K, log_cell, stripe_index.data(), bundle_first.data(), nb, nullptr, nullptr, 0, out.witness_first.data()), h_);
+        const size_t total = (size_t)K * out.witness_first.back();
+        out.values.resize(((stripe_index.size() * K * 4) << log_cell) + 1);
+        out.witness.resize(32 * total + 1);
+        check(frieda_open_stripe_bundles(h_, handles.data(), K, log_cell, stripe_index.data(), bundle_first.data(), nb, out.values.data(), out.witness.data(), total,
+                                         out.witness_first.data()),
+              h_);
+        out.values.resize(out.values.size() - 1), out.witness.resize(32 * total);
+        return out;
+    }
+    // status[n_bundles][K]
+    std::vector<uint8_t> verify_stripe_bundles_many(const std::vector<Commitment>& commitments, uint32_t log_domain, uint32_t log_cell,
+                                                    const std::vector<uint32_t>& stripe_index, const std::vector<uint32_t>& bundle_first,
+                                                    const std::vector<uint32_t>& values, const std::vector<uint8_t>& witness,
+                                                    const std::vector<uint64_t>& witness_first) {
+        const size_t K = commitments.size();
+        check_stripe_bundle_shapes("verify_stripe_bundles_many", K, log_cell, stripe_index, bundle_first, values.size(), witness.size(), &witness_first);
+        const std::vector<uint8_t> flat = flat_commitments(commitments);
+        const uint32_t nb = (uint32_t)bundle_first.size() - 1;
+        std::vector<uint8_t> status((size_t)nb * K + 1);
+        check(frieda_verify_stripe_bundles_many(h_, flat.data(), (uint32_t)K, log_domain, log_cell, stripe_index.data(), bundle_first.data(), nb, values.data(),
+                                                witness.data(), witness_first.data(), status.data()),
+              h_);
+        status.resize((size_t)nb * K);
+        return status;
+    }
+    std::vector<std::vector<uint8_t>> reconstruct_blobs_from_stripe_bundles(const std::vector<Commitment>& commitments, uint32_t log_blowup_factor, size_t len,
+                                                                            uint32_t log_cell, const std::vector<uint32_t>& stripe_index,
+                                                                            const std::vector<uint32_t>& bundle_first, const std::vector<uint32_t>& values,
+                                                                            const std::vector<uint8_t>& witness, const std::vector<uint64_t>& witness_first,
+                                                                            std::vector<uint8_t>* out_status = nullptr, size_t* n_stripes_used = nullptr) {
+        const size_t K = commitments.size();
+        check_stripe_bundle_shapes("reconstruct_blobs_from_stripe_bundles", K, log_cell, stripe_index, bundle_first, values.size(), witness.size(), &witness_first);
+        const std::vector<uint8_t> flat = flat_commitments(commitments);
+        const uint32_t nb = (uint32_t)bundle_first.size() - 1;
+        std::vector<uint8_t> status((size_t)nb * K + 1), out(len * K + 1);
+        size_t used = 0;
+        const int rc = frieda_reconstruct_blobs_from_stripe_bundles(h_, flat.data(), (uint32_t)K, log_blowup_factor, len, log_cell, stripe_index.data(),
+                                                                    bundle_first.data(), nb, values.data(), witness.data(), witness_first.data(), out.data(),
+                                                                    status.data(), &used);
+        status.resize((size_t)nb * K);
+        if (out_status) *out_status = status;
+        if (n_stripes_used) *n_stripes_used = used;
+        check(rc, h_);
+        std::vector<std::vector<uint8_t>> blobs(K);
+        for (size_t b = 0; b < K; b++) blobs[b].assign(out.begin() + b * len, out.begin() + (b + 1) * len);
+        return blobs;
+    }
     // Level B openings over caller device buffers (frieda_dev_gather, frieda_dev_gather_hashes, frieda_merkle_decommit)
     // rows[i * ncols + c] = column c at idx[i]
     std::vector<uint32_t> dev_gather(const uint32_t* d_cols, size_t stride, uint32_t ncols, const std::vector<uint64_t>& idx) {
@@ -600,6 +678,21 @@ inline std::vector<uint8_t> verify_cells_blobs(const std::vector<Commitment>& co
     std::vector<uint8_t> status(cell_index.size());
     check(frieda_verify_cells_blobs(flat.data(), (uint32_t)commitments.size(), log_domain, log_cell, blob_index.data(), cell_index.data(),
                                     (uint32_t)cell_index.size(), values.data(), paths.data(), status.data()));
+    return status;
+}
+// host verifier of stripe bundles (frieda_verify_stripe_bundles): status[n_bundles][K]
+inline std::vector<uint8_t> verify_stripe_bundles(const std::vector<Commitment>& commitments, uint32_t log_domain, uint32_t log_cell,
+                                                  const std::vector<uint32_t>& stripe_index, const std::vector<uint32_t>& bundle_first,
+                                                  const std::vector<uint32_t>& values, const std::vector<uint8_t>& witness,
+                                                  const std::vector<uint64_t>& witness_first) {
+    const size_t K = commitments.size();
+    Context::check_stripe_bundle_shapes("verify_stripe_bundles", K, log_cell, stripe_index, bundle_first, values.size(), witness.size(), &witness_first);
+    const std::vector<uint8_t> flat = Context::flat_commitments(commitments);
+    const uint32_t nb = (uint32_t)bundle_first.size() - 1;
+    std::vector<uint8_t> status((size_t)nb * K + 1);
+    check(frieda_verify_stripe_bundles(flat.data(), (uint32_t)K, log_domain, log_cell, stripe_index.data(), bundle_first.data(), nb, values.data(), witness.data(),
+                                       witness_first.data(), status.data()));
+    status.resize((size_t)nb * K);
     return status;
 }
 }  // namespace api

@@ -143,7 +143,9 @@ int frieda_commit_and_generate_proof_device(frieda_ctx* ctx, const void* d_data,
  * frieda_open_cells, frieda_verify_cells_many, frieda_reconstruct_from_opened_cells (frieda_verify_cells is host-only and takes no context),
  * frieda_open_cells_blobs, frieda_verify_cells_blobs_many, frieda_reconstruct_blobs_from_opened_stripes (frieda_verify_cells_blobs is host-only
  * and takes no context), frieda_open_cell_bundles, frieda_verify_cell_bundles_many, frieda_reconstruct_from_cell_bundles
- * (frieda_cell_bundle_witness_count and frieda_verify_cell_bundles are host-only and take no context).  Level B calls that only read the twiddle cache and caller buffers stay available.
+ * (frieda_cell_bundle_witness_count and frieda_verify_cell_bundles are host-only and take no context), frieda_open_stripe_bundles,
+ * frieda_verify_stripe_bundles_many, frieda_reconstruct_blobs_from_stripe_bundles (frieda_verify_stripe_bundles is host-only and takes no
+ * context).  Level B calls that only read the twiddle cache and caller buffers stay available.
  * A blob passed to _begin_device must stay valid until _finish returns. */
 int frieda_prove_begin(frieda_ctx* ctx, const uint8_t* data, size_t len, const uint64_t* seed, frieda_pcs_config cfg);
 int frieda_prove_begin_device(frieda_ctx* ctx, const void* d_data, size_t len, const uint64_t* seed, frieda_pcs_config cfg);
@@ -452,6 +454,65 @@ int frieda_reconstruct_from_cell_bundles(frieda_ctx* ctx, const uint8_t commitme
                                          const uint32_t* cell_index, const uint32_t* bundle_first, uint32_t n_bundles, const uint32_t* values,
                                          const uint8_t* witness, const uint64_t* witness_first, uint8_t* out_bytes, uint8_t* out_status,
                                          size_t* n_cells_used);
+
+/* ---- stripe bundles: a block's stripes under one shared witness per blob -----------------------------------------------------------
+ * The bundle form of the block calls above.  A STRIPE BUNDLE is the answer to one request over a block of n_blobs blobs of one shape:
+ * k stripes (a stripe is cell j of every blob; 1 <= k <= FRIEDA_MAX_BUNDLE_CELLS, stripe indices strictly ascending) with ONE hash
+ * witness per blob instead of one path per (stripe, blob) cell.  Every blob of a bundle has the same indices, so the witness length,
+ * the per-level offsets and the malformed rule are computed once per bundle, not once per (bundle, blob); all blobs are rebuilt with
+ * one erasure locator.  A call carries n_bundles bundles back to back: stripe t of the call belongs to bundle b when
+ * bundle_first[b] <= t < bundle_first[b + 1].  All pointers are host memory.  Layouts:
+ *   values          [n_stripes_total][n_blobs][4][2^log_cell], stripe-major: exactly what frieda_reconstruct_blobs_from_opened_stripes takes.
+ *   witness_first   [n_bundles + 1], counts hashes PER BLOB: W_b = witness_first[b + 1] - witness_first[b] must equal
+ *                   frieda_cell_bundle_witness_count of bundle b's indices.
+ *   witness         bundle b's block starts at hash n_blobs * witness_first[b]; blob j's piece is the W_b hashes at offset j * W_b inside
+ *                   that block, byte for byte the witness frieda_open_cell_bundles gives for blob j on the same indices.  cap_hashes
+ *                   counts against n_blobs * witness_first[n_bundles].
+ *   out_status      [n_bundles][n_blobs] bytes FRIEDA_BUNDLE_*.  Byte (b, j) is exactly what frieda_verify_cell_bundles(commitments + 32 j, ...)
+ *                   gives for blob j's piece alone; it never depends on another blob or bundle, and the host and GPU routes agree.
+ * MALFORMED depends on the indices and W_b only: it is decided once per bundle, on the host, by the rule of the cell bundles, and written
+ * to all n_blobs bytes of that bundle; such a bundle is never staged.  The provider's call refuses it outright.  FRIEDA_ERR_ARG
+ * (statuses untouched) is for what makes the call itself meaningless: the argument rules of the block cell calls and of the bundle calls
+ * combined — 1 <= n_blobs <= 65536 for open and verify (<= 256 for the rebuild), every encs[b] non-NULL, where ctx sits and of one
+ * log_domain (an entry may repeat, and the blobs' tree-skip thresholds may differ), NULL pointers, *_first arrays that do not start at 0
+ * or decrease, log_domain or log_cell out of range.  n_bundles == 0 is a no-op.
+ * The times of these calls are records, not gates; what the form buys is bytes.  Measured on a block of 16 blobs of 128 KiB, 513 stripes
+ * of 64 entries as one bundle / as eight bundles, against the loop of 16 single-blob bundle calls and against the per-cell stripe calls on
+ * the same stripes in the same run on one MI355X (profiles/r16_stripe_bundles.txt, tools/stripe_bundles_timing.py): 16 x 1673 / 16 x 3132
+ * witness hashes instead of 16 x 6669 path hashes (arithmetic); open 0.78 / 0.84 ms against 1.51 ms (loop) and 0.94 ms (per cell); device
+ * verify 0.80 / 0.74 ms against 3.91 / 2.26 ms and 0.92 ms; host verify on one core 61.9 / 63.4 ms against 61.6 / 63.2 ms and 56.8 ms; the
+ * whole rebuild 3.23 / 3.16 ms against 11.01 / 9.40 ms (sixteen locators) and 3.25 ms.  Other block sizes, cell sizes and domains are not
+ * measured. */
+/* Provider: out_values for all stripes of the call, the witness blocks of the bundles back to back in out_witness (cap_hashes hashes of
+ * room) and out_witness_first[n_bundles + 1].  out_witness == NULL is the size query: it fills out_witness_first only and launches
+ * nothing (out_values may then be NULL too).  One upload, the launches (stripe_bundles.hip: one wave per (bundle, blob, level)), one
+ * download, one synchronisation.  A malformed bundle, or cap_hashes below n_blobs * the per-blob total, refuses the whole call:
+ * FRIEDA_ERR_ARG, outputs untouched, and frieda_last_error names the bundle.  Only reads the encoded blobs; FRIEDA_ERR_ARG while a proof
+ * is in flight on ctx. */
+int frieda_open_stripe_bundles(frieda_ctx* ctx, const frieda_encoded* const* encs, uint32_t n_blobs, uint32_t log_cell, const uint32_t* stripe_index,
+                               const uint32_t* bundle_first, uint32_t n_bundles, uint32_t* out_values, uint8_t* out_witness, size_t cap_hashes,
+                               uint64_t* out_witness_first);
+/* Client, host verifier: no context, one core; the independent bottom-up merge of frieda_verify_cell_bundles run per blob piece.
+ * commitments[n_blobs][32]. */
+int frieda_verify_stripe_bundles(const uint8_t* commitments, uint32_t n_blobs, uint32_t log_domain, uint32_t log_cell, const uint32_t* stripe_index,
+                                 const uint32_t* bundle_first, uint32_t n_bundles, const uint32_t* values, const uint8_t* witness,
+                                 const uint64_t* witness_first, uint8_t* out_status);
+/* Client, the same status bytes from the GPU: per pass the subtree roots of all (stripe, blob) cells, then one wave per (bundle, blob)
+ * merges that blob's list upward.  A bundle stages its indices once and its values and witness n_blobs times; a bundle never straddles
+ * two passes.  FRIEDA_ERR_ARG while a proof is in flight on ctx. */
+int frieda_verify_stripe_bundles_many(frieda_ctx* ctx, const uint8_t* commitments, uint32_t n_blobs, uint32_t log_domain, uint32_t log_cell,
+                                      const uint32_t* stripe_index, const uint32_t* bundle_first, uint32_t n_bundles, const uint32_t* values,
+                                      const uint8_t* witness, const uint64_t* witness_first, uint8_t* out_status);
+/* The client's whole block flow from stripe bundles: verify as frieda_verify_stripe_bundles_many does; a bundle is USED only when all
+ * n_blobs of its bytes are ACCEPTED; the stripes of the used bundles are de-duplicated by index and all blobs rebuilt by ONE point
+ * reconstruction over 4 * n_blobs columns, then every rebuilt blob must commit to its commitment.  The stripe counts needed,
+ * *n_stripes_used (the distinct stripes of used bundles), the FRIEDA_ERR_ARG cases (too few stripes, a wrong len: out_bytes untouched,
+ * out_status[n_bundles][n_blobs] valid), n_blobs <= 256 and the 2^32-word bound are those of frieda_reconstruct_blobs_from_opened_stripes.
+ * out_bytes[n_blobs][len].  There is no per-blob fallback. */
+int frieda_reconstruct_blobs_from_stripe_bundles(frieda_ctx* ctx, const uint8_t* commitments, uint32_t n_blobs, uint32_t log_blowup_factor, size_t len,
+                                                 uint32_t log_cell, const uint32_t* stripe_index, const uint32_t* bundle_first, uint32_t n_bundles,
+                                                 const uint32_t* values, const uint8_t* witness, const uint64_t* witness_first, uint8_t* out_bytes,
+                                                 uint8_t* out_status, size_t* n_stripes_used);
 
 /* ---- batch policy: how a stream of equal-length blobs is cut into batched calls ("bytes in flight") -------------------------
  * Every kernel of a batched call covers all its blobs, so the launch / Fiat-Shamir latency chain is paid once per call: small
