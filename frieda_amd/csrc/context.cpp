@@ -151,6 +151,7 @@ const KnobDesc KNOBS[] = {
     {"FRIEDA_TREE_SKIP_LONE_LOG", 10, 40, [](Tuning& t, long v) { t.tree_skip_lone_log = (uint32_t)v; return true; }},
     {"FRIEDA_SEEDS_FOLD_GROUP", 0, 64, [](Tuning& t, long v) { t.seeds_fold_group = (uint32_t)v; return true; }},
     {"FRIEDA_TP_MIN_WGS", 0, 1 << 30, [](Tuning& t, long v) { t.tp_min_wgs = (uint32_t)v; return true; }},
+    {"FRIEDA_GRIND_FRONT_WGS", 0, 2048, [](Tuning& t, long v) { t.grind_front_wgs = (uint32_t)v; return true; }},
     {"FRIEDA_GRIND_ITERS", 0, 64, [](Tuning& t, long v) { t.grind_iters = (uint32_t)v; return true; }},
     {"FRIEDA_BATCH_BUDGET_MB", 0, 262144, [](Tuning& t, long v) { t.batch_budget_mb = (uint32_t)v; return true; }},
     {"FRIEDA_BATCH_CALLS_PER_CTX", 1, 64, [](Tuning& t, long v) { t.batch_calls_per_ctx = (uint32_t)v; return true; }},

@@ -61,6 +61,11 @@ struct Tuning {
                                          // in the decommitment whatever the size; a batch shares it, a lone proof pays it: worth it from 2^23 on)
     uint32_t tp_min_wgs = 768;           // FRIEDA_TP_MIN_WGS: launches of at least this many 256-thread workgroups hash in the throughput form (blake2s.h)
     uint32_t grind_iters = 0;            // FRIEDA_GRIND_ITERS: nonces per lane and claim in the batched grind (window = 256 x this); 0 = by batch size
+    uint32_t grind_front_wgs = 768;      // FRIEDA_GRIND_FRONT_WGS: batched grind of up to 64 blobs: with k blobs still searching only max(k x the launch's
+                                         // workgroups per blob, this many) workgroups go on claiming windows, the rest leave (tree.hip, "the front rule");
+                                         // 0 = all stay (A/B).  Measured: 512, 768 and 1024 alike within the noise in both shapes; 256 costs nothing at
+                                         // 2^24 x 15 but is slower than no rule at 2^20 x 64; 768 is the middle of the flat range
+                                         // (profiles/r17_batched_leftovers.txt)
     uint32_t seeds_fold_group = 0;       // FRIEDA_SEEDS_FOLD_GROUP: proofs of one encoded blob under many seeds (prove_seeds): seeds per workgroup of the
                                          // seed-looped first fold (route B: the evaluation is read once per group); 0 = route A, the batch kernels
                                          // with every seed re-reading the shared evaluation (measured: profiles/r08_prove_seeds.txt)

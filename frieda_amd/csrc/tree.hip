@@ -1192,8 +1192,8 @@ __global__ __launch_bounds__(WG1_THREADS) void tail_kernel(TailArgs a) {
 // atomicMin on a hit) and moves on; it leaves once no blob has work.  Windows are claimed in order and always scanned to the
 // point where a smaller hit is known, so tr->nonce ends as the MINIMUM qualifying nonce of the range, as in the reference's
 // sequential search; blobs that finish early release their workgroups to the others (in a batch the slowest blob needs
-// several times the mean).  Every loop is bounded: a claim consumes one of n_windows * batch windows, a fruitless walk over
-// all blobs ends the workgroup.
+// several times the mean) — as far as the front rule (GrindArgs) lets them stay.  Every loop is bounded: a claim consumes one of
+// n_windows * batch windows, a fruitless walk over all blobs ends the workgroup.
 constexpr uint32_t GRIND_WINDOW = 1024;  // the unit n_windows counts in: 4 nonces per lane (256-nonce windows were tried: the claim — an atomic
                                          // and two barriers — then costs as much as the scan, 47 instead of 19 us on the bench blob)
 // A claim takes `iters / 4` consecutive units (GrindArgs::iters nonces per lane): in a batch 2048 workgroups claim ~45 M units per second
@@ -1208,7 +1208,25 @@ struct GrindArgs {
     unsigned long long base;
     uint32_t n_windows;  // per blob, in units of GRIND_WINDOW nonces
     uint32_t units;      // units per claim (a lane scans 4 * units nonces of the claim)
+    uint32_t front_wgs;  // the front rule below: workgroups that saturate the chip (0 = every workgroup walks to the end)
+    uint32_t per_blob;   // workgroups of the launch per blob (rounded up)
 };
+// The front rule.  Every window in flight beyond a blob's hit is scanned for nothing, and while the chip is full it is scanned at the
+// expense of windows that are needed: what a blob wastes is about half of what is in flight for it when its hit arrives.  With every
+// workgroup walking to the end, the windows in flight per blob grow as blobs finish — 2048 / 15 workgroups per blob at first, all 2048 on the
+// last one, whose claim counter then runs 2048 claims ahead of its lowest unfinished window.  So the launch shrinks with the search:
+// with k blobs still searching, only the workgroups blockIdx.x < max(k * per_blob, front_wgs) go on claiming; the others leave (they
+// leave BEFORE a claim, never with a window in hand, and never come back: k only falls).  The claims in flight for all blobs together
+// are then at most that many once the leavers' last windows are done, and a blob's counter leads its lowest unfinished window by its
+// share of them — every window is the same work, so none lags far —: about per_blob claims, the blob's share of the launch (batch
+// size, workgroups in flight), or front_wgs / k where that is more; front_wgs is the fewest workgroups that still fill the vector
+// pipes (Tuning::grind_front_wgs).  The workgroups below front_wgs never leave by this rule, so every window below a hit is still
+// claimed and scanned: the minimum stands.  Nobody waits for anybody: a workgroup that may not claim is gone.  Batches of more than
+// 64 blobs are launched without the rule (front_wgs = 0): counting their searching blobs would take a pass over the batch per claim.
+__device__ __forceinline__ uint32_t grind_allowed_wgs(const GrindArgs& a, uint32_t searching) {
+    const uint32_t share = searching * a.per_blob;
+    return share > a.front_wgs ? share : a.front_wgs;
+}
 
 __global__ __launch_bounds__(256) void grind_dev_kernel(GrindArgs a) {
     __shared__ uint32_t s_claim[2];  // blob, window (blob == ~0: nothing left)
@@ -1230,6 +1248,9 @@ __global__ __launch_bounds__(256) void grind_dev_kernel(GrindArgs a) {
                     idle += adv;
                     continue;
                 }
+                // the front rule (GrindArgs): this step's ballot holds every blob of the launch (the launcher applies the rule up to 64 blobs),
+                // so the blobs still searching are its set bits; got_b stays ~0 and the workgroup leaves
+                if (a.front_wgs && blockIdx.x >= grind_allowed_wgs(a, (uint32_t)__popcll(mask))) break;
                 const uint32_t l = (uint32_t)__ffsll((long long)mask) - 1;
                 uint32_t tb = b + l;
                 if (tb >= a.batch) tb -= a.batch;
@@ -1667,6 +1688,9 @@ void grind_dev(const Launch& L, DevTranscript* tr, uint32_t* d_next, uint32_t po
     if (want < 64) want = 64;
     if (want > 2048) want = 2048;
     if (want > (uint64_t)a.n_windows * L.batch) want = (uint64_t)a.n_windows * L.batch;
+    // the front rule where wave 0's one ballot sees the whole batch and where it was measured (15 and 64 blobs): larger batches walk as before
+    a.front_wgs = L.batch <= 64 ? L.tune->grind_front_wgs : 0;
+    a.per_blob = (uint32_t)((want + L.batch - 1) / L.batch);
     grind_dev_kernel<<<(unsigned)want, 256, 0, L.stream>>>(a);
 }
 
