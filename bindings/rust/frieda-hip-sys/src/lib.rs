@@ -164,6 +164,13 @@ extern "C" {
     pub fn frieda_verify_stripe_bundles(commitments: *const u8, n_blobs: u32, log_domain: u32, log_cell: u32, stripe_index: *const u32, bundle_first: *const u32, n_bundles: u32, values: *const u32, witness: *const u8, witness_first: *const u64, out_status: *mut u8) -> c_int;
     pub fn frieda_verify_stripe_bundles_many(ctx: *mut frieda_ctx, commitments: *const u8, n_blobs: u32, log_domain: u32, log_cell: u32, stripe_index: *const u32, bundle_first: *const u32, n_bundles: u32, values: *const u32, witness: *const u8, witness_first: *const u64, out_status: *mut u8) -> c_int;
     pub fn frieda_reconstruct_blobs_from_stripe_bundles(ctx: *mut frieda_ctx, commitments: *const u8, n_blobs: u32, log_blowup_factor: u32, len: usize, log_cell: u32, stripe_index: *const u32, bundle_first: *const u32, n_bundles: u32, values: *const u32, witness: *const u8, witness_first: *const u64, out_bytes: *mut u8, out_status: *mut u8, n_stripes_used: *mut usize) -> c_int;
+    // encoded handles for a block in one call, and straight from a rebuild: the handles of a call share one reference-counted allocation and
+    // are freed one by one with frieda_encoded_free; out_bytes of the rebuild calls may be null (only the handles are wanted)
+    pub fn frieda_encode_batch(ctx: *mut frieda_ctx, data: *const u8, stride: usize, len: usize, count: u32, log_blowup_factor: u32, out_encs: *mut *mut frieda_encoded) -> c_int;
+    pub fn frieda_rebuild_encoded_from_opened_cells(ctx: *mut frieda_ctx, commitment: *const u8, log_blowup_factor: u32, len: usize, log_cell: u32, cell_index: *const u32, n_cells: u32, values: *const u32, paths: *const u8, out_bytes: *mut u8, out_status: *mut u8, n_cells_used: *mut usize, out_enc: *mut *mut frieda_encoded) -> c_int;
+    pub fn frieda_rebuild_encoded_from_cell_bundles(ctx: *mut frieda_ctx, commitment: *const u8, log_blowup_factor: u32, len: usize, log_cell: u32, cell_index: *const u32, bundle_first: *const u32, n_bundles: u32, values: *const u32, witness: *const u8, witness_first: *const u64, out_bytes: *mut u8, out_status: *mut u8, n_cells_used: *mut usize, out_enc: *mut *mut frieda_encoded) -> c_int;
+    pub fn frieda_rebuild_encoded_blobs_from_opened_stripes(ctx: *mut frieda_ctx, commitments: *const u8, n_blobs: u32, log_blowup_factor: u32, len: usize, log_cell: u32, stripe_index: *const u32, n_stripes: u32, values: *const u32, paths: *const u8, out_bytes: *mut u8, out_status: *mut u8, n_stripes_used: *mut usize, out_encs: *mut *mut frieda_encoded) -> c_int;
+    pub fn frieda_rebuild_encoded_blobs_from_stripe_bundles(ctx: *mut frieda_ctx, commitments: *const u8, n_blobs: u32, log_blowup_factor: u32, len: usize, log_cell: u32, stripe_index: *const u32, bundle_first: *const u32, n_bundles: u32, values: *const u32, witness: *const u8, witness_first: *const u64, out_bytes: *mut u8, out_status: *mut u8, n_stripes_used: *mut usize, out_encs: *mut *mut frieda_encoded) -> c_int;
 
     // struct Proof
     pub fn frieda_proof_free(p: *mut frieda_proof);

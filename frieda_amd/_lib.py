@@ -163,6 +163,11 @@ def lib():
         "frieda_verify_stripe_bundles": (C.c_int, [vp, u32, u32, u32, vp, vp, u32, vp, vp, vp, vp]),
         "frieda_verify_stripe_bundles_many": (C.c_int, [vp, vp, u32, u32, u32, vp, vp, u32, vp, vp, vp, vp]),
         "frieda_reconstruct_blobs_from_stripe_bundles": (C.c_int, [vp, vp, u32, u32, sz, u32, vp, vp, u32, vp, vp, vp, vp, vp, C.POINTER(sz)]),
+        "frieda_encode_batch": (C.c_int, [vp, vp, sz, sz, u32, u32, vp]),
+        "frieda_rebuild_encoded_from_opened_cells": (C.c_int, [vp, vp, u32, sz, u32, vp, u32, vp, vp, vp, vp, C.POINTER(sz), vp]),
+        "frieda_rebuild_encoded_from_cell_bundles": (C.c_int, [vp, vp, u32, sz, u32, vp, vp, u32, vp, vp, vp, vp, vp, C.POINTER(sz), vp]),
+        "frieda_rebuild_encoded_blobs_from_opened_stripes": (C.c_int, [vp, vp, u32, u32, sz, u32, vp, u32, vp, vp, vp, vp, C.POINTER(sz), vp]),
+        "frieda_rebuild_encoded_blobs_from_stripe_bundles": (C.c_int, [vp, vp, u32, u32, sz, u32, vp, vp, u32, vp, vp, vp, vp, vp, C.POINTER(sz), vp]),
         "frieda_proof_free": (None, [vp]),
         "frieda_proof_clone": (C.c_int, [vp, pp]),
         "frieda_proof_proof_of_work": (u64, [vp]),

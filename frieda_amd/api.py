@@ -685,6 +685,120 @@ class Context:
             raise
         return [out[b * n_bytes : (b + 1) * n_bytes].tobytes() for b in range(K)], status[: count * K].reshape(count, K), n.value
 
+    # ---- encoded handles for a block in one call, and straight from a rebuild (frieda_encode_batch, frieda_rebuild_encoded_*) ----
+    def encode_batch(self, blobs, log_blowup_factor, stride=None):
+        """Context.encode of every blob of a block in one call: a list of Encoded sharing one device allocation, each closed on its own.
+        blobs: equal-length byte strings; stride (optional, >= the length): the distance of the blobs in the array handed to the library."""
+        count = len(blobs)
+        if count == 0:
+            return []
+        length = len(blobs[0])
+        if any(len(b) != length for b in blobs):
+            raise ValueError("a batch holds blobs of one length")
+        stride = length if stride is None else int(stride)
+        if stride < length:
+            raise ValueError("stride smaller than the blob length")
+        flat = b"".join(bytes(b) + b"\xa5" * (stride - length) for b in blobs)
+        buf = (C.c_uint8 * max(len(flat), 1)).from_buffer_copy(flat or b"\0")
+        outs = (C.c_void_p * count)()
+        _check(self._L.frieda_encode_batch(self._h, buf, stride, length, count, log_blowup_factor, outs), self._h)
+        return [Encoded(C.c_void_p(outs[b]), length, log_blowup_factor) for b in range(count)]
+
+    def _rebuild_encoded(self, fn, args_before, n_bytes, n_blobs, status, log_blowup_factor, want_bytes):
+        """the shared tail of the four rebuild_encoded_* methods: (out array or None, list of Encoded, n_used); raises with .n set"""
+        out = np.zeros(max(n_bytes * n_blobs, 1), dtype=np.uint8) if want_bytes else None
+        n = C.c_size_t(0)
+        encs = (C.c_void_p * n_blobs)()
+        try:
+            _check(fn(self._h, *args_before, out.ctypes.data if want_bytes else None, status.ctypes.data, C.byref(n), encs), self._h)
+        except FriedaError as e:
+            e.n_used = n.value
+            raise
+        return out, [Encoded(C.c_void_p(encs[b]), n_bytes, log_blowup_factor) for b in range(n_blobs)], n.value
+
+    def rebuild_encoded_from_opened_cells(self, commitment, log_blowup_factor, n_bytes, log_cell, cell_index, values, paths, want_bytes=True):
+        """reconstruct_from_opened_cells that also returns the rebuilt blob as an Encoded, without encoding the bytes again: (bytes, status,
+        n_cells_used, Encoded); bytes is None with want_bytes=False (nothing is packed or downloaded).  Raises FriedaError as the twin does
+        (with .n_cells_used and .cell_status set)."""
+        log_domain = codec_log_size(n_bytes) + log_blowup_factor
+        idx, val, pth = _cell_arrays(log_domain, log_cell, cell_index, values, paths)
+        count = len(idx)
+        status = np.zeros(max(count, 1), dtype=np.uint8)
+        com = (C.c_uint8 * 32)(*commitment)
+        try:
+            out, encs, n = self._rebuild_encoded(
+                self._L.frieda_rebuild_encoded_from_opened_cells,
+                (com, log_blowup_factor, n_bytes, log_cell, idx.ctypes.data, count, val.ctypes.data, pth.ctypes.data), n_bytes, 1, status, log_blowup_factor, want_bytes
+            )
+        except FriedaError as e:
+            e.n_cells_used = e.n_used
+            e.cell_status = status[:count]
+            raise
+        return (out[:n_bytes].tobytes() if want_bytes else None), status[:count], n, encs[0]
+
+    def rebuild_encoded_from_cell_bundles(self, commitment, log_blowup_factor, n_bytes, log_cell, bundles, values, witness, witness_first, want_bytes=True):
+        """reconstruct_from_cell_bundles + the Encoded: (bytes or None, status, n_cells_used, Encoded); errors as the twin (.n_cells_used,
+        .bundle_status)."""
+        idx, first, val, wit, wfirst = _bundle_arrays(log_cell, bundles, values, witness, witness_first)
+        count = len(first) - 1
+        status = np.zeros(max(count, 1), dtype=np.uint8)
+        com = (C.c_uint8 * 32)(*commitment)
+        try:
+            out, encs, n = self._rebuild_encoded(
+                self._L.frieda_rebuild_encoded_from_cell_bundles,
+                (com, log_blowup_factor, n_bytes, log_cell, idx.ctypes.data, first.ctypes.data, count, val.ctypes.data, wit.ctypes.data, wfirst.ctypes.data),
+                n_bytes, 1, status, log_blowup_factor, want_bytes
+            )
+        except FriedaError as e:
+            e.n_cells_used = e.n_used
+            e.bundle_status = status[:count]
+            raise
+        return (out[:n_bytes].tobytes() if want_bytes else None), status[:count], n, encs[0]
+
+    def rebuild_encoded_blobs_from_opened_stripes(self, commitments, log_blowup_factor, n_bytes, log_cell, stripe_index, values, paths, want_bytes=True):
+        """reconstruct_blobs_from_opened_stripes + one Encoded per blob (sharing one allocation): (list of K bytes or None, status [S, K],
+        n_stripes_used, list of K Encoded); errors as the twin (.n_stripes_used, .cell_status)."""
+        com = _commitment_table(commitments)
+        K = len(com) // 32
+        log_domain = codec_log_size(n_bytes) + log_blowup_factor
+        stripes = np.ascontiguousarray(stripe_index, dtype=np.uint32).reshape(-1)
+        S = len(stripes)
+        _, val, pth = _cell_arrays(log_domain, log_cell, np.zeros(S * K, dtype=np.uint32), values, paths)
+        status = np.zeros(max(S * K, 1), dtype=np.uint8)
+        try:
+            out, encs, n = self._rebuild_encoded(
+                self._L.frieda_rebuild_encoded_blobs_from_opened_stripes,
+                (com.ctypes.data, K, log_blowup_factor, n_bytes, log_cell, stripes.ctypes.data, S, val.ctypes.data, pth.ctypes.data), n_bytes, K, status,
+                log_blowup_factor, want_bytes
+            )
+        except FriedaError as e:
+            e.n_stripes_used = e.n_used
+            e.cell_status = status[: S * K].reshape(S, K)
+            raise
+        blobs = [out[b * n_bytes : (b + 1) * n_bytes].tobytes() for b in range(K)] if want_bytes else None
+        return blobs, status[: S * K].reshape(S, K), n, encs
+
+    def rebuild_encoded_blobs_from_stripe_bundles(self, commitments, log_blowup_factor, n_bytes, log_cell, bundles, values, witness, witness_first, want_bytes=True):
+        """reconstruct_blobs_from_stripe_bundles + one Encoded per blob: (list of K bytes or None, status [n_bundles, K], n_stripes_used,
+        list of K Encoded); errors as the twin (.n_stripes_used, .bundle_status)."""
+        com = _commitment_table(commitments)
+        K = len(com) // 32
+        idx, first, val, wit, wfirst = _stripe_bundle_arrays(K, log_cell, bundles, values, witness, witness_first)
+        count = len(first) - 1
+        status = np.zeros(max(count * K, 1), dtype=np.uint8)
+        try:
+            out, encs, n = self._rebuild_encoded(
+                self._L.frieda_rebuild_encoded_blobs_from_stripe_bundles,
+                (com.ctypes.data, K, log_blowup_factor, n_bytes, log_cell, idx.ctypes.data, first.ctypes.data, count, val.ctypes.data, wit.ctypes.data,
+                 wfirst.ctypes.data), n_bytes, K, status, log_blowup_factor, want_bytes
+            )
+        except FriedaError as e:
+            e.n_stripes_used = e.n_used
+            e.bundle_status = status[: count * K].reshape(count, K)
+            raise
+        blobs = [out[b * n_bytes : (b + 1) * n_bytes].tobytes() for b in range(K)] if want_bytes else None
+        return blobs, status[: count * K].reshape(count, K), n, encs
+
 
 def codec_log_size(n_bytes):
     """log2 of the coefficients per column of a blob of n_bytes (frieda_codec_shape)."""
@@ -1426,3 +1540,29 @@ def verify_stripe_bundles_many(commitments, log_domain, log_cell, bundles, value
 def reconstruct_blobs_from_stripe_bundles(commitments, log_blowup_factor, n_bytes, log_cell, bundles, values, witness, witness_first):
     """frieda_reconstruct_blobs_from_stripe_bundles on the default context: (list of bytes, status [n_bundles, K], n_stripes_used)."""
     return default_context().reconstruct_blobs_from_stripe_bundles(commitments, log_blowup_factor, n_bytes, log_cell, bundles, values, witness, witness_first)
+
+
+def encode_batch(blobs, log_blowup_factor):
+    """frieda_encode_batch on the default context: one Encoded per blob, sharing one allocation."""
+    return default_context().encode_batch(blobs, log_blowup_factor)
+
+
+def rebuild_encoded_from_opened_cells(commitment, log_blowup_factor, n_bytes, log_cell, cell_index, values, paths, want_bytes=True):
+    """frieda_rebuild_encoded_from_opened_cells on the default context: (bytes, status, n_cells_used, Encoded)."""
+    return default_context().rebuild_encoded_from_opened_cells(commitment, log_blowup_factor, n_bytes, log_cell, cell_index, values, paths, want_bytes)
+
+
+def rebuild_encoded_from_cell_bundles(commitment, log_blowup_factor, n_bytes, log_cell, bundles, values, witness, witness_first, want_bytes=True):
+    """frieda_rebuild_encoded_from_cell_bundles on the default context: (bytes, status, n_cells_used, Encoded)."""
+    return default_context().rebuild_encoded_from_cell_bundles(commitment, log_blowup_factor, n_bytes, log_cell, bundles, values, witness, witness_first, want_bytes)
+
+
+def rebuild_encoded_blobs_from_opened_stripes(commitments, log_blowup_factor, n_bytes, log_cell, stripe_index, values, paths, want_bytes=True):
+    """frieda_rebuild_encoded_blobs_from_opened_stripes on the default context: (list of bytes, status [S, K], n_stripes_used, list of Encoded)."""
+    return default_context().rebuild_encoded_blobs_from_opened_stripes(commitments, log_blowup_factor, n_bytes, log_cell, stripe_index, values, paths, want_bytes)
+
+
+def rebuild_encoded_blobs_from_stripe_bundles(commitments, log_blowup_factor, n_bytes, log_cell, bundles, values, witness, witness_first, want_bytes=True):
+    """frieda_rebuild_encoded_blobs_from_stripe_bundles on the default context: (list of bytes, status [n_bundles, K], n_stripes_used, list of Encoded)."""
+    return default_context().rebuild_encoded_blobs_from_stripe_bundles(commitments, log_blowup_factor, n_bytes, log_cell, bundles, values, witness, witness_first,
+                                                                       want_bytes)

@@ -250,12 +250,15 @@ int frieda_verify_cell_bundles_many(frieda_ctx* ctx, const uint8_t commitment[32
     FR_GUARD_END(ctx)
 }
 
-int frieda_reconstruct_from_cell_bundles(frieda_ctx* ctx, const uint8_t commitment[32], uint32_t log_blowup_factor, size_t len, uint32_t log_cell,
-                                         const uint32_t* cell_index, const uint32_t* bundle_first, uint32_t n_bundles, const uint32_t* values,
-                                         const uint8_t* witness, const uint64_t* witness_first, uint8_t* out_bytes, uint8_t* out_status, size_t* n_cells_used) {
-    if (!ctx || !commitment || !n_cells_used || (len && !out_bytes)) return FRIEDA_ERR_ARG;
+namespace {
+// frieda_reconstruct_from_cell_bundles (out_enc == nullptr: its tail rebuild_blob, out_bytes required) and
+// frieda_rebuild_encoded_from_cell_bundles (the tail that returns the handle; out_bytes optional)
+int reconstruct_from_cell_bundles(frieda_ctx* ctx, const uint8_t commitment[32], uint32_t log_blowup_factor, size_t len, uint32_t log_cell,
+                                  const uint32_t* cell_index, const uint32_t* bundle_first, uint32_t n_bundles, const uint32_t* values, const uint8_t* witness,
+                                  const uint64_t* witness_first, uint8_t* out_bytes, uint8_t* out_status, size_t* n_cells_used, frieda_encoded** out_enc) {
+    if (!ctx || !commitment || !n_cells_used || (len && !out_bytes && !out_enc)) return FRIEDA_ERR_ARG;
     *n_cells_used = 0;
-    const char* const fn = "reconstruct_from_cell_bundles: ";
+    const char* const fn = out_enc ? "rebuild_encoded_from_cell_bundles: " : "reconstruct_from_cell_bundles: ";
     if (log_blowup_factor > FRIEDA_MAX_LOG_DOMAIN || len > ((size_t)1 << 40)) return ctx->c.fail(FRIEDA_ERR_ARG, std::string(fn) + "shape out of range");
     const uint32_t L = codec_shape(len).log_size, n = L + log_blowup_factor;
     if (L < 1 || n < 2 || n + 1 > FRIEDA_MAX_LOG_DOMAIN) return ctx->c.fail(FRIEDA_ERR_ARG, std::string(fn) + "shape out of range");
@@ -276,12 +279,35 @@ int frieda_reconstruct_from_cell_bundles(frieda_ctx* ctx, const uint8_t commitme
     int rc = verify_bundles_passes(&ctx->c, commitment, n, log_cell, cell_index, bundle_first, n_bundles, values, witness, witness_first, out_status, &pool);
     if (rc != FRIEDA_OK) return rc;
     if (pool.n == 0) return too_few();
-    return rebuild_blob(ctx, len, log_blowup_factor, commitment, "the rebuilt blob does not commit to the commitment (wrong len?)", out_bytes, [&](uint8_t* d_out) {
+    const char* const mismatch = "the rebuilt blob does not commit to the commitment (wrong len?)";
+    if (out_enc) {
+        rc = rebuild_encoded_from_pool(ctx, pool, commitment, 1, log_blowup_factor, len, log_cell, mismatch, out_bytes, &nd, out_enc);
+        *n_cells_used = nd;
+        return rc == FRIEDA_ERR_ARG && nd < need ? too_few() : rc;
+    }
+    return rebuild_blob(ctx, len, log_blowup_factor, commitment, mismatch, out_bytes, [&](uint8_t* d_out) {
         rc = reconstruct_pooled(ctx, pool.d_val(), pool.d_idx(), (uint32_t)pool.n, 1, log_cell, L, n, len, d_out, 0, &nd);
         *n_cells_used = nd;
         return rc == FRIEDA_ERR_ARG && nd < need ? too_few() : rc;
     });
     FR_GUARD_END(ctx)
+}
+}  // namespace
+
+int frieda_reconstruct_from_cell_bundles(frieda_ctx* ctx, const uint8_t commitment[32], uint32_t log_blowup_factor, size_t len, uint32_t log_cell,
+                                         const uint32_t* cell_index, const uint32_t* bundle_first, uint32_t n_bundles, const uint32_t* values,
+                                         const uint8_t* witness, const uint64_t* witness_first, uint8_t* out_bytes, uint8_t* out_status, size_t* n_cells_used) {
+    return reconstruct_from_cell_bundles(ctx, commitment, log_blowup_factor, len, log_cell, cell_index, bundle_first, n_bundles, values, witness, witness_first,
+                                         out_bytes, out_status, n_cells_used, nullptr);
+}
+int frieda_rebuild_encoded_from_cell_bundles(frieda_ctx* ctx, const uint8_t commitment[32], uint32_t log_blowup_factor, size_t len, uint32_t log_cell,
+                                             const uint32_t* cell_index, const uint32_t* bundle_first, uint32_t n_bundles, const uint32_t* values,
+                                             const uint8_t* witness, const uint64_t* witness_first, uint8_t* out_bytes, uint8_t* out_status,
+                                             size_t* n_cells_used, frieda_encoded** out_enc) {
+    if (!out_enc) return FRIEDA_ERR_ARG;
+    *out_enc = nullptr;
+    return reconstruct_from_cell_bundles(ctx, commitment, log_blowup_factor, len, log_cell, cell_index, bundle_first, n_bundles, values, witness, witness_first,
+                                         out_bytes, out_status, n_cells_used, out_enc);
 }
 
 }  // extern "C"

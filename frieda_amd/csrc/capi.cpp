@@ -492,6 +492,13 @@ int frieda_encode(frieda_ctx* ctx, const uint8_t* data, size_t len, uint32_t log
 int frieda_encode_device(frieda_ctx* ctx, const void* d_data, size_t len, uint32_t log_blowup_factor, frieda_encoded** out) {
     return encode_common(ctx, d_data, len, true, log_blowup_factor, out);
 }
+int frieda_encode_batch(frieda_ctx* ctx, const uint8_t* data, size_t stride, size_t len, uint32_t count, uint32_t log_blowup_factor,
+                        frieda_encoded** out_encs) {
+    if (!ctx || !out_encs || (!data && len) || count == 0) return FRIEDA_ERR_ARG;
+    FR_GUARD_BEGIN
+    return encode_batch(&ctx->c, data, stride, len, count, log_blowup_factor, out_encs);
+    FR_GUARD_END(ctx)
+}
 int frieda_encoded_commitment(const frieda_encoded* enc, uint8_t out_root[32]) {
     if (!enc || !out_root) return FRIEDA_ERR_ARG;
     memcpy(out_root, enc->e.root, 32);

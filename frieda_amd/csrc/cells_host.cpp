@@ -297,15 +297,19 @@ int frieda_verify_cells_many(frieda_ctx* ctx, const uint8_t commitment[32], uint
     FR_GUARD_END(ctx)
 }
 
-int frieda_reconstruct_from_opened_cells(frieda_ctx* ctx, const uint8_t commitment[32], uint32_t log_blowup_factor, size_t len, uint32_t log_cell,
-                                         const uint32_t* cell_index, uint32_t n_cells, const uint32_t* values, const uint8_t* paths,
-                                         uint8_t* out_bytes, uint8_t* out_status, size_t* n_cells_used) {
-    if (!ctx || !commitment || !n_cells_used || (len && !out_bytes) || (n_cells && (!cell_index || !values || !out_status))) return FRIEDA_ERR_ARG;
+namespace {
+// frieda_reconstruct_from_opened_cells (out_enc == nullptr: its tail rebuild_blob, out_bytes required) and
+// frieda_rebuild_encoded_from_opened_cells (the tail that returns the handle; out_bytes optional)
+int reconstruct_from_opened_cells(frieda_ctx* ctx, const uint8_t commitment[32], uint32_t log_blowup_factor, size_t len, uint32_t log_cell,
+                                  const uint32_t* cell_index, uint32_t n_cells, const uint32_t* values, const uint8_t* paths, uint8_t* out_bytes,
+                                  uint8_t* out_status, size_t* n_cells_used, frieda_encoded** out_enc) {
+    if (!ctx || !commitment || !n_cells_used || (len && !out_bytes && !out_enc) || (n_cells && (!cell_index || !values || !out_status))) return FRIEDA_ERR_ARG;
     *n_cells_used = 0;
-    if (log_blowup_factor > FRIEDA_MAX_LOG_DOMAIN || len > ((size_t)1 << 40)) return ctx->c.fail(FRIEDA_ERR_ARG, "reconstruct_from_opened_cells: shape out of range");
+    const char* const fn = out_enc ? "rebuild_encoded_from_opened_cells: " : "reconstruct_from_opened_cells: ";
+    if (log_blowup_factor > FRIEDA_MAX_LOG_DOMAIN || len > ((size_t)1 << 40)) return ctx->c.fail(FRIEDA_ERR_ARG, std::string(fn) + "shape out of range");
     const uint32_t L = codec_shape(len).log_size, n = L + log_blowup_factor;
-    if (L < 1 || n < 2 || n + 1 > FRIEDA_MAX_LOG_DOMAIN) return ctx->c.fail(FRIEDA_ERR_ARG, "reconstruct_from_opened_cells: shape out of range");
-    if (const char* bad = cells_args_error(n, log_cell, cell_index, n_cells)) return ctx->c.fail(FRIEDA_ERR_ARG, std::string("reconstruct_from_opened_cells: ") + bad);
+    if (L < 1 || n < 2 || n + 1 > FRIEDA_MAX_LOG_DOMAIN) return ctx->c.fail(FRIEDA_ERR_ARG, std::string(fn) + "shape out of range");
+    if (const char* bad = cells_args_error(n, log_cell, cell_index, n_cells)) return ctx->c.fail(FRIEDA_ERR_ARG, std::string(fn) + bad);
     if (n_cells && !paths && log_cell != n) return FRIEDA_ERR_ARG;
     FR_NO_JOB(&ctx->c);
     FR_GUARD_BEGIN
@@ -319,12 +323,34 @@ int frieda_reconstruct_from_opened_cells(frieda_ctx* ctx, const uint8_t commitme
     int rc = verify_cells_passes(&ctx->c, commitment, 0, n, log_cell, nullptr, cell_index, n_cells, values, paths, out_status, &pool);
     if (rc != FRIEDA_OK) return rc;
     if (pool.n == 0) return too_few();
-    return rebuild_blob(ctx, len, log_blowup_factor, commitment, "the rebuilt blob does not commit to the commitment (wrong len?)", out_bytes, [&](uint8_t* d_out) {
+    const char* const mismatch = "the rebuilt blob does not commit to the commitment (wrong len?)";
+    if (out_enc) {
+        rc = rebuild_encoded_from_pool(ctx, pool, commitment, 1, log_blowup_factor, len, log_cell, mismatch, out_bytes, &nd, out_enc);
+        *n_cells_used = nd;
+        return rc == FRIEDA_ERR_ARG && nd < need ? too_few() : rc;
+    }
+    return rebuild_blob(ctx, len, log_blowup_factor, commitment, mismatch, out_bytes, [&](uint8_t* d_out) {
         rc = reconstruct_pooled(ctx, pool.d_val(), pool.d_idx(), (uint32_t)pool.n, 1, log_cell, L, n, len, d_out, 0, &nd);
         *n_cells_used = nd;
         return rc == FRIEDA_ERR_ARG && nd < need ? too_few() : rc;
     });
     FR_GUARD_END(ctx)
+}
+}  // namespace
+
+int frieda_reconstruct_from_opened_cells(frieda_ctx* ctx, const uint8_t commitment[32], uint32_t log_blowup_factor, size_t len, uint32_t log_cell,
+                                         const uint32_t* cell_index, uint32_t n_cells, const uint32_t* values, const uint8_t* paths,
+                                         uint8_t* out_bytes, uint8_t* out_status, size_t* n_cells_used) {
+    return reconstruct_from_opened_cells(ctx, commitment, log_blowup_factor, len, log_cell, cell_index, n_cells, values, paths, out_bytes, out_status,
+                                         n_cells_used, nullptr);
+}
+int frieda_rebuild_encoded_from_opened_cells(frieda_ctx* ctx, const uint8_t commitment[32], uint32_t log_blowup_factor, size_t len, uint32_t log_cell,
+                                             const uint32_t* cell_index, uint32_t n_cells, const uint32_t* values, const uint8_t* paths,
+                                             uint8_t* out_bytes, uint8_t* out_status, size_t* n_cells_used, frieda_encoded** out_enc) {
+    if (!out_enc) return FRIEDA_ERR_ARG;
+    *out_enc = nullptr;
+    return reconstruct_from_opened_cells(ctx, commitment, log_blowup_factor, len, log_cell, cell_index, n_cells, values, paths, out_bytes, out_status,
+                                         n_cells_used, out_enc);
 }
 
 // ---- the cells of many blobs of one shape in one call ----
@@ -377,12 +403,15 @@ int frieda_verify_cells_blobs_many(frieda_ctx* ctx, const uint8_t* commitments, 
     FR_GUARD_END(ctx)
 }
 
-int frieda_reconstruct_blobs_from_opened_stripes(frieda_ctx* ctx, const uint8_t* commitments, uint32_t n_blobs, uint32_t log_blowup_factor, size_t len,
-                                                 uint32_t log_cell, const uint32_t* stripe_index, uint32_t n_stripes, const uint32_t* values,
-                                                 const uint8_t* paths, uint8_t* out_bytes, uint8_t* out_status, size_t* n_stripes_used) {
-    if (!ctx || !commitments || !n_stripes_used || (len && !out_bytes) || (n_stripes && (!stripe_index || !values || !out_status))) return FRIEDA_ERR_ARG;
+namespace {
+// frieda_reconstruct_blobs_from_opened_stripes (out_encs == nullptr: its tail rebuild_blobs_from_stripes) and
+// frieda_rebuild_encoded_blobs_from_opened_stripes (out_encs[n_blobs], all NULL on entry; out_bytes optional)
+int reconstruct_blobs_from_opened_stripes(frieda_ctx* ctx, const uint8_t* commitments, uint32_t n_blobs, uint32_t log_blowup_factor, size_t len,
+                                          uint32_t log_cell, const uint32_t* stripe_index, uint32_t n_stripes, const uint32_t* values, const uint8_t* paths,
+                                          uint8_t* out_bytes, uint8_t* out_status, size_t* n_stripes_used, frieda_encoded** out_encs) {
+    if (!ctx || !commitments || !n_stripes_used || (len && !out_bytes && !out_encs) || (n_stripes && (!stripe_index || !values || !out_status))) return FRIEDA_ERR_ARG;
     *n_stripes_used = 0;
-    const char* const fn = "reconstruct_blobs_from_opened_stripes: ";
+    const char* const fn = out_encs ? "rebuild_encoded_blobs_from_opened_stripes: " : "reconstruct_blobs_from_opened_stripes: ";
     if (n_blobs == 0 || n_blobs > STRIPES_MAX_BLOBS) return ctx->c.fail(FRIEDA_ERR_ARG, std::string(fn) + "n_blobs out of range (1 .. 256)");
     if (log_blowup_factor > FRIEDA_MAX_LOG_DOMAIN || len > ((size_t)1 << 40)) return ctx->c.fail(FRIEDA_ERR_ARG, std::string(fn) + "shape out of range");
     const uint32_t L = codec_shape(len).log_size, n = L + log_blowup_factor;
@@ -403,10 +432,28 @@ int frieda_reconstruct_blobs_from_opened_stripes(frieda_ctx* ctx, const uint8_t*
     int rc = verify_cells_passes(&ctx->c, commitments, n_blobs, n, log_cell, nullptr, stripe_index, n_stripes * n_blobs, values, paths, out_status, &pool);
     if (rc != FRIEDA_OK) return rc;
     if (pool.n == 0) return too_few();
-    rc = rebuild_blobs_from_stripes(ctx, pool, commitments, n_blobs, log_blowup_factor, len, log_cell, out_bytes, &nd);
+    rc = out_encs ? rebuild_encoded_from_pool(ctx, pool, commitments, n_blobs, log_blowup_factor, len, log_cell, nullptr, out_bytes, &nd, out_encs)
+                  : rebuild_blobs_from_stripes(ctx, pool, commitments, n_blobs, log_blowup_factor, len, log_cell, out_bytes, &nd);
     *n_stripes_used = nd;
     return rc == FRIEDA_ERR_ARG && nd < need ? too_few() : rc;
     FR_GUARD_END(ctx)
+}
+}  // namespace
+
+int frieda_reconstruct_blobs_from_opened_stripes(frieda_ctx* ctx, const uint8_t* commitments, uint32_t n_blobs, uint32_t log_blowup_factor, size_t len,
+                                                 uint32_t log_cell, const uint32_t* stripe_index, uint32_t n_stripes, const uint32_t* values,
+                                                 const uint8_t* paths, uint8_t* out_bytes, uint8_t* out_status, size_t* n_stripes_used) {
+    return reconstruct_blobs_from_opened_stripes(ctx, commitments, n_blobs, log_blowup_factor, len, log_cell, stripe_index, n_stripes, values, paths, out_bytes,
+                                                 out_status, n_stripes_used, nullptr);
+}
+int frieda_rebuild_encoded_blobs_from_opened_stripes(frieda_ctx* ctx, const uint8_t* commitments, uint32_t n_blobs, uint32_t log_blowup_factor,
+                                                     size_t len, uint32_t log_cell, const uint32_t* stripe_index, uint32_t n_stripes,
+                                                     const uint32_t* values, const uint8_t* paths, uint8_t* out_bytes, uint8_t* out_status,
+                                                     size_t* n_stripes_used, frieda_encoded** out_encs) {
+    if (!out_encs) return FRIEDA_ERR_ARG;
+    if (n_blobs >= 1 && n_blobs <= STRIPES_MAX_BLOBS) memset(out_encs, 0, sizeof(frieda_encoded*) * n_blobs);
+    return reconstruct_blobs_from_opened_stripes(ctx, commitments, n_blobs, log_blowup_factor, len, log_cell, stripe_index, n_stripes, values, paths, out_bytes,
+                                                 out_status, n_stripes_used, out_encs);
 }
 
 }  // extern "C"

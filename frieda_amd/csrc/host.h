@@ -15,6 +15,7 @@
 
 #include "../../include/frieda_hip.h"
 #include "channel.h"
+#include "encoded_slab.h"
 #include "field.h"
 #include "kernels.h"
 
@@ -225,11 +226,14 @@ uint32_t job_count(const Ctx* ctx);  // blobs of the job in flight (0: none)
 // them on the device — one allocation of its own (not the context's arena: it survives other calls and release_workspace) holding the
 // 4 evaluation columns, the first-layer tree (leaves-first layout, leaf hashes unwritten, large trees without the two levels above
 // the leaves: `skip_log` is the threshold the tree was BUILT with) and the root.  Proving only reads it.
+// The allocation belongs to a reference-counted slab (encoded_slab.h): the handles of a block (frieda_encode_batch, the
+// frieda_rebuild_encoded_* calls) share one, blob b's share at b * encoded_bytes(n); a lone frieda_encode is the slab of one.
 struct Encoded {
     int device = 0;
     size_t len = 0;
     uint32_t log_blowup = 0, n = 0, L = 0;
     uint32_t skip_log = 0;
+    EncodedSlab* slab = nullptr;  // owner of the allocation `d` points into; this handle holds one reference while d != nullptr
     uint8_t* d = nullptr;  // [evaluation: 4 x 2^n words][tree: merkle_layer_offset(n, 0) + 32 bytes][root: 32 bytes], each from a 256-byte boundary
     size_t bytes = 0, o_tree = 0, o_root = 0;
     uint8_t root[32] = {0};
@@ -239,8 +243,28 @@ struct Encoded {
 size_t encoded_bytes(uint32_t n, size_t* o_tree = nullptr, size_t* o_root = nullptr);  // the size of that allocation for a 2^n domain
 // synchronous (the root comes back); the context's arena holds the blob and the coefficients meanwhile
 int encode_blob(Ctx* ctx, const uint8_t* data, size_t len, bool data_on_device, uint32_t log_blowup, Encoded** out);
-void encoded_release(Encoded& e);  // frees the device allocation
+void encoded_release(Encoded& e);  // drops the handle's reference: the slab is freed (on its device) with its last handle
 void encoded_free(Encoded* e);     // release + delete
+// `count` handles of one shape in one fresh slab (hipMalloc + poison_fresh), blob b's share at b * encoded_bytes(n): every field but the
+// root is set.  Releases whatever it still holds when it leaves scope; publish() hands the handles to the caller.
+struct EncodedBlock {
+    std::vector<Encoded> e;
+    size_t bstride = 0;
+    EncodedBlock() = default;
+    EncodedBlock(const EncodedBlock&) = delete;
+    EncodedBlock& operator=(const EncodedBlock&) = delete;
+    ~EncodedBlock() {
+        for (Encoded& x : e) encoded_release(x);
+    }
+    uint8_t* base() const { return e[0].d; }
+    // FRIEDA_ERR_NOMEM (the context's error set, nothing allocated) when the slab does not fit
+    int alloc(Ctx* ctx, size_t len, uint32_t log_blowup, uint32_t L, uint32_t n, uint32_t count, uint32_t skip_log);
+    // roots[count][32] into the handles, then out[b] = a new frieda_encoded owning handle b; FRIEDA_ERR_NOMEM leaves `out` untouched
+    int publish(const uint8_t* roots, frieda_encoded** out);
+};
+// `count` host blobs of one length (blob b at data + b * data_stride) -> `count` handles in one slab: one upload, the batched launches of
+// commit_batch with the evaluation and the tree kept, one download of the roots, one synchronisation.  Not cut into passes.
+int encode_batch(Ctx* ctx, const uint8_t* data, size_t data_stride, size_t len, uint32_t count, uint32_t log_blowup, frieda_encoded** out_encs);
 // n_seeds proofs of enc's blob, proof i under seeds[i]: the batch machinery with the first layer at stride 0 (the per-seed workspace
 // holds the inner layers, the last layer and the nonce only).  n_seeds > 1 needs the device channel, as every batch does.  Finished by
 // prove_finish_batch (the commitments it writes are n_seeds copies of enc's root).
@@ -328,6 +352,13 @@ const char* cells_args_error(uint32_t log_domain, uint32_t log_cell, const uint3
 // 4 * n_blobs columns, commit_batch, every root against its commitment, out_bytes[n_blobs][len]; *n_distinct also on an error
 int rebuild_blobs_from_stripes(frieda_ctx* ctx, const CellPool& pool, const uint8_t* commitments, uint32_t n_blobs, uint32_t log_blowup_factor, size_t len,
                                uint32_t log_cell, uint8_t* out_bytes, uint32_t* n_distinct);
+// The sibling of rebuild_blob and rebuild_blobs_from_stripes that also returns handles (frieda_rebuild_encoded_*; n_blobs 1: a blob's
+// cells, else the fully accepted stripes of a block): the point reconstruction with its step-5 re-encode landing in a fresh slab, the
+// blob-image check (blob_image.h) on the coefficients, tree_first_layer over the slab (batched over the blobs), every root against its
+// commitment by rebuilt_accept's rule, pack30 + download only when out_bytes is given.  No commit_host / commit_batch: the bytes are
+// never uploaded.  *n_distinct also on an error; out_encs[n_blobs] is written on FRIEDA_OK only.
+int rebuild_encoded_from_pool(frieda_ctx* ctx, const CellPool& pool, const uint8_t* commitments, uint32_t n_blobs, uint32_t log_blowup, size_t len,
+                              uint32_t log_cell, const char* mismatch, uint8_t* out_bytes, uint32_t* n_distinct, frieda_encoded** out_encs);
 
 // transcript pieces shared by prover and verifier (transcript.cpp)
 void channel_mix_felts(Channel& ch, const std::vector<QM31>& felts);

@@ -296,8 +296,9 @@ namespace k {
 // transcript and draws the folding alpha
 // tr_init (optional): the initial transcript of every blob in pinned host memory (blob b at tr_init + b * tr_init_pitch bytes);
 // the finishing kernel reads it from there and initialises the device transcript itself — no copy in the stream
+// d_root (optional): the root is also stored there (blob b's at d_root + b * L.bstride)
 void tree_first_layer(const Launch& L, const uint32_t* cols, size_t stride, uint32_t m, uint8_t* d_layers, DevTranscript* tr,
-                      const DevTranscript* tr_init = nullptr, size_t tr_init_pitch = 0);
+                      const DevTranscript* tr_init = nullptr, size_t tr_init_pitch = 0, uint8_t* d_root = nullptr);
 // Encode + first tree in one call (commit(): src/commit.rs:16-21; FriProver::commit_first_layer: src/proof.rs:48-52): the
 // transform of the 4 coordinate columns with its last pass fused with leaf hashing where the shape allows
 // (circle_evaluate_into_tree), then the rest of the tree.  d_layers non-null: every level above the leaf hashes is kept and the
@@ -518,6 +519,14 @@ struct StripeBundleWalkArgs {
 };
 // one wave per (bundle, blob), LDS as bundle_walk (bundle_walk_lds_bytes); n_bundles * n_blobs < 2^31
 void stripe_bundle_walk(const Launch& L, const StripeBundleWalkArgs& a);
+
+// ---- encoded.hip: what handles built from a rebuild need (frieda_rebuild_encoded_*) ----
+// The blob-image rule (blob_image.h) over the n_words coefficient words of each of n_blobs blobs (blob b at d_coef + b * n_words; n_words a
+// multiple of 4, d_coef 16-byte aligned): d_flags[b] |= 1 where a word of blob b breaks it.  d_flags is zeroed by the caller.
+void blob_image_check(const Launch& L, const uint32_t* d_coef, size_t n_words, size_t len, uint32_t n_blobs, uint32_t* d_flags);
+// Evaluation columns at one stride -> the slab layout of a block of handles: column c of blob b (2^n words at d_ev + (4 b + c) * ev_stride)
+// goes to d_slab + b * bstride + c * 4 * 2^n bytes.  n >= 2; ev_stride a multiple of 4 words, bstride of 16 bytes, both pointers 16-byte aligned.
+void eval_to_slab(const Launch& L, const uint32_t* d_ev, size_t ev_stride, uint32_t n, uint32_t n_blobs, uint8_t* d_slab, size_t bstride);
 
 // ---- opening.hip: Level B openings (frieda_dev_gather*, frieda_merkle_decommit*) ----
 constexpr uint32_t OPEN_BAD_WORD = 0xFFFFFFFFu;   // gathered word of an out-of-range index (device forms only; not a canonical M31)

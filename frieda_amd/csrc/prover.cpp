@@ -15,6 +15,7 @@
 #include <algorithm>
 #include <chrono>
 #include <cstdlib>
+#include <new>
 
 #include <stddef.h>
 
@@ -1122,14 +1123,77 @@ size_t encoded_bytes(uint32_t n, size_t* o_tree, size_t* o_root) {
     return plan.off;
 }
 
+namespace {
+// the slab's injected free (encoded_slab.h): on the slab's device, the caller's current device restored
+void slab_hip_free(void* base, int device) {
+    int cur = 0;
+    const bool sw = hipGetDevice(&cur) == hipSuccess && cur != device;
+    if (sw) (void)hipSetDevice(device);
+    (void)hipFree(base);
+    if (sw) (void)hipSetDevice(cur);
+}
+}  // namespace
+
 void encoded_release(Encoded& e) {
     if (!e.d) return;
-    int cur = 0;
-    const bool sw = hipGetDevice(&cur) == hipSuccess && cur != e.device;
-    if (sw) (void)hipSetDevice(e.device);
-    (void)hipFree(e.d);
-    if (sw) (void)hipSetDevice(cur);
+    if (e.slab) slab_drop(e.slab);
+    e.slab = nullptr;
     e.d = nullptr;
+}
+
+int EncodedBlock::alloc(Ctx* ctx, size_t len, uint32_t log_blowup, uint32_t L, uint32_t n, uint32_t count, uint32_t skip_log) {
+    size_t o_tree = 0, o_root = 0;
+    bstride = encoded_bytes(n, &o_tree, &o_root);
+    e.assign(count, Encoded());  // (before the allocation: nothing to undo when the host is out of memory)
+    uint8_t* base = nullptr;
+    if (hipMalloc((void**)&base, bstride * count) != hipSuccess) {
+        (void)hipGetLastError();
+        e.clear();
+        return ctx->fail(FRIEDA_ERR_NOMEM, "hipMalloc(encoded blob" + std::string(count > 1 ? "s " : " ") + std::to_string(bstride * count) + " B) failed");
+    }
+    EncodedSlab* slab = nullptr;
+    try {
+        slab = slab_create(base, ctx->device, count, slab_hip_free);
+    } catch (...) {
+        (void)hipFree(base);
+        e.clear();
+        throw;
+    }
+    for (uint32_t b = 0; b < count; b++) {
+        Encoded& x = e[b];
+        x.device = ctx->device;
+        x.len = len;
+        x.log_blowup = log_blowup;
+        x.n = n;
+        x.L = L;
+        x.skip_log = skip_log;
+        x.slab = slab;
+        x.d = base + (size_t)b * bstride;
+        x.bytes = bstride;
+        x.o_tree = o_tree;
+        x.o_root = o_root;
+    }
+    FR_HIP(ctx, ctx->poison_fresh(base, bstride * count));
+    return FRIEDA_OK;
+}
+
+int EncodedBlock::publish(const uint8_t* roots, frieda_encoded** out) {
+    std::vector<frieda_encoded*> hs(e.size(), nullptr);
+    for (size_t b = 0; b < e.size(); b++) {
+        hs[b] = new (std::nothrow) frieda_encoded();
+        if (!hs[b]) {
+            for (size_t i = 0; i < b; i++) delete hs[i];
+            return FRIEDA_ERR_NOMEM;
+        }
+    }
+    for (size_t b = 0; b < e.size(); b++) {
+        memcpy(e[b].root, roots + 32 * b, 32);
+        hs[b]->e = e[b];  // the handle holds the reference from here on
+        e[b].d = nullptr;
+        e[b].slab = nullptr;
+        out[b] = hs[b];
+    }
+    return FRIEDA_OK;
 }
 void encoded_free(Encoded* e) {
     if (!e) return;
@@ -1155,20 +1219,14 @@ int encode_blob(Ctx* ctx, const uint8_t* data, size_t len, bool data_on_device, 
     rc = ctx->get_twiddles(sh.n, tw);
     if (rc) return rc;
     std::unique_ptr<Encoded, void (*)(Encoded*)> e(new Encoded(), encoded_free);
-    e->device = ctx->device;
-    e->len = len;
-    e->log_blowup = log_blowup;
-    e->n = sh.n;
-    e->L = sh.L;
-    // a lone launch builds the tree: the threshold of a call of one blob (what k::build_tree applies to a Launch of batch 1)
-    e->skip_log = k::tree_skip_threshold(ctx->tuning, 1);
-    e->bytes = encoded_bytes(sh.n, &e->o_tree, &e->o_root);
-    if (hipMalloc((void**)&e->d, e->bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        e->d = nullptr;
-        return ctx->fail(FRIEDA_ERR_NOMEM, "hipMalloc(encoded blob " + std::to_string(e->bytes) + " B) failed");
+    {
+        // the slab of one.  A lone launch builds the tree: the threshold of a call of one blob (what k::build_tree applies to a Launch of batch 1)
+        EncodedBlock one;
+        rc = one.alloc(ctx, len, log_blowup, sh.L, sh.n, 1, k::tree_skip_threshold(ctx->tuning, 1));
+        if (rc) return rc;
+        *e = one.e[0];
+        one.e.clear();  // (the reference moved to *e)
     }
-    FR_HIP(ctx, ctx->poison_fresh(e->d, e->bytes));
     hipStream_t s = ctx->stream;
     uint8_t* A = ctx->arena;
     const uint8_t* d_data = data;
@@ -1192,6 +1250,65 @@ int encode_blob(Ctx* ctx, const uint8_t* data, size_t len, bool data_on_device, 
     memcpy(e->root, ctx->pinned, 32);
     *out = e.release();
     return FRIEDA_OK;
+}
+
+// commit_batch_begin with everything kept.  The kernels take ONE batch stride for every pointer but the blob's (BlobSource has its own),
+// and what they write — evaluation, tree, root — sits in the slab at encoded_bytes(n) per blob: so the launches run at the slab's
+// stride.  The arena holds the blobs back to back at their own stride and, for the general route, the coefficients at the slab's stride
+// (blob b's 4 * 2^L words at b * bstride: the gaps are address space the call never touches; the fused small route keeps no coefficients).
+int encode_batch(Ctx* ctx, const uint8_t* data, size_t data_stride, size_t len, uint32_t count, uint32_t log_blowup, frieda_encoded** out_encs) {
+    FR_NO_JOB(ctx);
+    if (count == 0 || count > 65535) return ctx->fail(FRIEDA_ERR_ARG, "batch count out of range");
+    if (count > 1 && data_stride < len) return ctx->fail(FRIEDA_ERR_ARG, "batch stride smaller than the blob length");
+    Shape sh;
+    int rc = make_shape(ctx, len, log_blowup, sh);
+    if (rc) return rc;
+    FR_HIP(ctx, hipSetDevice(ctx->device));
+    const bool small = k::small_domain_shape(ctx->tuning, sh.L, sh.n);
+    const size_t bstride = encoded_bytes(sh.n);
+    const size_t dstride = std::max<size_t>(256, (len + 255) & ~(size_t)255);
+    ArenaPlan plan;
+    const size_t o_data = plan.take(dstride * count);
+    const size_t o_coef = plan.take(small ? 0 : bstride * (count - 1) + sizeof(uint32_t) * sh.cs.n_padded);
+    rc = ctx->ensure_arena(plan.off);
+    if (rc) return rc;
+    rc = ensure_pinned(ctx, 32 * (size_t)count + 4096);
+    if (rc) return rc;
+    TwiddleSet tw;
+    rc = ctx->get_twiddles(sh.n, tw);
+    if (rc) return rc;
+    EncodedBlock blk;
+    rc = blk.alloc(ctx, len, log_blowup, sh.L, sh.n, count, k::tree_skip_threshold(ctx->tuning, count));
+    if (rc) return rc;
+    hipStream_t s = ctx->stream;
+    uint8_t* A = ctx->arena;
+    uint8_t* S = blk.base();
+    const size_t o_tree = blk.e[0].o_tree, o_root = blk.e[0].o_root;
+    k::Launch LN = ctx->launch();
+    LN.batch = count;
+    LN.bstride = count > 1 ? bstride : 0;
+    auto run = [&]() -> int {
+        if (len) FR_HIP(ctx, hipMemcpy2DAsync(A + o_data, dstride, data, count > 1 ? data_stride : len, len, count, hipMemcpyHostToDevice, s));
+        uint32_t* eval = reinterpret_cast<uint32_t*>(S);
+        if (small) {
+            k::small_encode_and_first_tree(LN, A + o_data, len, dstride, sh.L, sh.n, tw.d_tw, tw.ds, eval, sh.N, S + o_tree, nullptr, S + o_root, nullptr, nullptr, 0);
+        } else {
+            uint32_t* coef = reinterpret_cast<uint32_t*>(A + o_coef);
+            const k::BlobSource blob{A + o_data, len, dstride, sh.cs.n_padded};
+            k::encode_and_first_tree(LN, coef, (size_t)1 << sh.L, sh.L, sh.n, tw.d_tw, tw.ds, eval, sh.N, S + o_tree, nullptr, S + o_root, nullptr, nullptr, 0, &blob);
+        }
+        FR_HIP(ctx, hipMemcpy2DAsync(ctx->pinned, 32, S + o_root, bstride, 32, count, hipMemcpyDeviceToHost, s));
+        FR_HIP(ctx, hipStreamSynchronize(s));
+        FR_HIP(ctx, hipGetLastError());
+        return FRIEDA_OK;
+    };
+    rc = run();
+    if (rc != FRIEDA_OK) {
+        (void)hipStreamSynchronize(s);  // (before the slab goes)
+        return rc;
+    }
+    rc = blk.publish(static_cast<const uint8_t*>(ctx->pinned), out_encs);
+    return rc == FRIEDA_OK ? rc : ctx->fail(rc, "host allocation failed");
 }
 
 // what prove_begin_impl plans for a prove_seeds job: the per-seed part times n_seeds, then the transcripts, the grind counters and the

@@ -224,9 +224,20 @@ namespace {
 // d_index (optional, then cell_index is not read): the cell list already on the device, outside the arena — no copy of it is made.
 // n_distinct (optional): receives the number of distinct cells offered; the argument checks that need it are then made on that number
 // alone, so that it is reported with the error.
+// sink (optional; ncols = 4 * blobs): where the step-5 evaluation is kept for the handles of a rebuild — the slab layout of host.h, blob b's
+// four columns back to back at slab + b * bstride.  One blob: circle_evaluate writes there directly (its output takes one column stride,
+// and 2^n is the slab's) and erasure_check reads it there.  A block: the 4 * blobs columns need ONE stride and the slab has two (the tree
+// and the root lie between the blobs), so the evaluation lands in the workspace as without a sink and k::eval_to_slab copies it over.
+// prepare: called once, when the distinct cells are known to suffice (every "too few" answer comes before it): allocates the slab and
+// sets slab / bstride — a call that has nothing to rebuild allocates nothing.
+struct EvalSink {
+    uint8_t* slab = nullptr;
+    size_t bstride = 0;
+    std::function<int(EvalSink&)> prepare;
+};
 int interpolate_points(frieda_ctx* ctx, const uint32_t* d_cells, const uint32_t* cell_index, uint32_t n_cells, uint32_t ncols, uint32_t log_cell,
                        uint32_t log_coef, uint32_t log_domain, uint32_t* d_coef, size_t arena_off, const uint32_t* d_index = nullptr,
-                       uint32_t* n_distinct = nullptr) {
+                       uint32_t* n_distinct = nullptr, EvalSink* sink = nullptr) {
     Ctx& c = ctx->c;
     FR_NO_JOB(&c);
     if (log_cell > log_domain || log_coef > log_domain || log_coef < 1 || log_domain < 2 || log_domain + 1 > FRIEDA_MAX_LOG_DOMAIN)
@@ -316,6 +327,10 @@ int interpolate_points(frieda_ctx* ctx, const uint32_t* d_cells, const uint32_t*
     if (s_all < K + 2)
         return c.fail(FRIEDA_ERR_ARG, "points: need at least 2^log_coef + 2 distinct points (the locator polynomial needs two spare samples)");
     if (s_use > s_all) return c.fail(FRIEDA_ERR_ARG, "points: cells of 2^log_cell entries: need 2^(log_coef - log_cell) + 1 distinct cells");
+    if (sink && sink->prepare) {
+        rc = sink->prepare(*sink);
+        if (rc) return rc;
+    }
     const size_t w_stride = al(4 * N) / 4, ev_stride = al(8 * N) / 4, blk_stride = al(4 * K) / 4;
     uint32_t* coef_out = d_coef ? d_coef : reinterpret_cast<uint32_t*>(A);
     const uint32_t* ev_first = nullptr;  // Z * p on the first 2^log_coef entries of D' (step 3)
@@ -410,8 +425,12 @@ int interpolate_points(frieda_ctx* ctx, const uint32_t* d_cells, const uint32_t*
     // 4. that block back to coefficients
     k::circle_interpolate_block(LN, W32(o_blk), blk_stride, ncols, log_coef, n + 1, 0, ts1.d_itw, ts1.ds, coef_out, K);
     // 5. encode again and compare every sample that was offered
-    k::circle_evaluate(LN, coef_out, K, ncols, log_coef, n, ts0.d_tw, ts0.ds, W32(o_w), w_stride);
-    k::erasure_check(LN, d_cells, W32(o_src), W32(o_pos), s_all, ncols, log_cell, W32(o_w), w_stride, W32(o_bad));
+    const bool direct = sink && ncols == 4;
+    uint32_t* ev5 = direct ? reinterpret_cast<uint32_t*>(sink->slab) : W32(o_w);
+    const size_t ev5_stride = direct ? N : w_stride;
+    k::circle_evaluate(LN, coef_out, K, ncols, log_coef, n, ts0.d_tw, ts0.ds, ev5, ev5_stride);
+    k::erasure_check(LN, d_cells, W32(o_src), W32(o_pos), s_all, ncols, log_cell, ev5, ev5_stride, W32(o_bad));
+    if (sink && !direct) k::eval_to_slab(LN, W32(o_w), w_stride, n, ncols / 4, sink->slab, sink->bstride);
     uint32_t bad = 0;
     FR_HIP(&c, hipMemcpyAsync(&bad, A + o_bad, 4, hipMemcpyDeviceToHost, s));
     FR_HIP(&c, hipStreamSynchronize(s));
@@ -488,12 +507,96 @@ int rebuild_blob(frieda_ctx* ctx, size_t len, uint32_t log_blowup, const uint8_t
     return rebuilt_accept(&ctx->c, root, commitment, 1, mismatch, bytes, out_bytes);
 }
 
+// the error of a blob that does not commit.  mismatch: the words of a single blob; null: blob b of a block is named
+static std::string rebuilt_mismatch_text(const char* mismatch, uint32_t b) {
+    return mismatch ? std::string(mismatch) : "the rebuilt blob " + std::to_string(b) + " does not commit to its commitment (wrong len?)";
+}
+
 int rebuilt_accept(Ctx* ctx, const uint8_t* roots, const uint8_t* commitments, uint32_t n_blobs, const char* mismatch, const std::vector<uint8_t>& bytes,
                    uint8_t* out_bytes) {
     for (uint32_t b = 0; b < n_blobs; b++)
         if (memcmp(roots + 32 * (size_t)b, commitments + 32 * (size_t)b, 32) != 0)
-            return ctx->fail(FRIEDA_ERR_ARG, mismatch ? mismatch : "the rebuilt blob " + std::to_string(b) + " does not commit to its commitment (wrong len?)");
+            return ctx->fail(FRIEDA_ERR_ARG, rebuilt_mismatch_text(mismatch, b));
     if (!bytes.empty()) memcpy(out_bytes, bytes.data(), bytes.size());
+    return FRIEDA_OK;
+}
+
+int rebuild_encoded_from_pool(frieda_ctx* ctx, const CellPool& pool, const uint8_t* commitments, uint32_t n_blobs, uint32_t log_blowup, size_t len,
+                              uint32_t log_cell, const char* mismatch, uint8_t* out_bytes, uint32_t* n_distinct, frieda_encoded** out_encs) {
+    if (!ctx || !commitments || !n_distinct || !out_encs || pool.n == 0 || n_blobs == 0 || n_blobs > 256) return FRIEDA_ERR_ARG;
+    Ctx& c = ctx->c;
+    const uint32_t L = codec_shape(len).log_size, n = L + log_blowup;
+    const size_t n_felts = (size_t)4 << L, N = (size_t)1 << n;
+    FR_HIP(&c, hipSetDevice(c.device));
+    // what the call keeps in front of the reconstruction's workspace: the coefficients (blob b's 4 columns are columns 4 b .. 4 b + 3:
+    // n_felts consecutive words), a flag word per blob and, when the bytes are wanted, the packed blobs (blob b at b * stride) — no
+    // allocation of the call's own beside the slab
+    const bool want_bytes = out_bytes && len;
+    const size_t stride = std::max<size_t>(256, (len + 255) & ~(size_t)255);
+    ArenaPlan front;
+    const size_t o_coef = front.take(sizeof(uint32_t) * n_felts * n_blobs), o_flags = front.take(sizeof(uint32_t) * n_blobs);
+    const size_t o_bytes = front.take(want_bytes ? stride * n_blobs : 0);
+    // what comes back: the roots, the image flags and — in ONE contiguous download — the packed blobs, through the pinned block up to
+    // 16 MiB of them (a pageable target costs more than the packing: measured 2.1 ms for 4.2 MB), through a vector of the call beyond.
+    // The rows go to out_bytes once the blobs are accepted: a failed call leaves it untouched.
+    const size_t pin_head = (36 * (size_t)n_blobs + 255) & ~(size_t)255, staged_bytes = want_bytes ? stride * (n_blobs - 1) + len : 0;
+    const bool pin_bytes = staged_bytes <= ((size_t)16 << 20);
+    int rc = ensure_pinned(&c, pin_head + (pin_bytes ? staged_bytes : 0) + 4096);
+    if (rc != FRIEDA_OK) return rc;
+    std::vector<uint8_t> staged(pin_bytes ? 0 : staged_bytes), roots(32 * (size_t)n_blobs);
+    std::vector<uint32_t> flags(n_blobs);
+    const uint8_t* host_bytes = nullptr;
+    EncodedBlock blk;
+    auto run = [&]() -> int {
+        EvalSink sink;
+        sink.prepare = [&](EvalSink& k_) {  // the slab: only once there is something to rebuild
+            const int a = blk.alloc(&c, len, log_blowup, L, n, n_blobs, k::tree_skip_threshold(c.tuning, n_blobs));
+            if (a == FRIEDA_OK) k_.slab = blk.base(), k_.bstride = blk.bstride;
+            return a;
+        };
+        const int r = interpolate_points(ctx, pool.d_val(), nullptr, (uint32_t)pool.n, 4 * n_blobs, log_cell, L, n, nullptr, front.off, pool.d_idx(), n_distinct, &sink);
+        if (r != FRIEDA_OK) return r;
+        uint8_t* S = blk.base();
+        hipStream_t s = c.stream;
+        const uint32_t* coef = reinterpret_cast<const uint32_t*>(c.arena + o_coef);
+        uint32_t* d_flags = reinterpret_cast<uint32_t*>(c.arena + o_flags);
+        FR_HIP(&c, hipMemsetAsync(d_flags, 0, sizeof(uint32_t) * n_blobs, s));
+        k::blob_image_check(c.launch(), coef, n_felts, len, n_blobs, d_flags);
+        k::Launch LN = c.launch();
+        LN.batch = n_blobs;
+        LN.bstride = n_blobs > 1 ? blk.bstride : 0;
+        k::tree_first_layer(LN, reinterpret_cast<const uint32_t*>(S), N, n, S + blk.e[0].o_tree, nullptr, nullptr, 0, S + blk.e[0].o_root);
+        uint8_t* pin = static_cast<uint8_t*>(c.pinned);
+        FR_HIP(&c, hipMemcpy2DAsync(pin, 32, S + blk.e[0].o_root, blk.bstride, 32, n_blobs, hipMemcpyDeviceToHost, s));
+        FR_HIP(&c, hipMemcpyAsync(pin + 32 * (size_t)n_blobs, d_flags, sizeof(uint32_t) * n_blobs, hipMemcpyDeviceToHost, s));
+        if (want_bytes) {
+            uint8_t* d_out = c.arena + o_bytes;
+            for (uint32_t b = 0; b < n_blobs; b++) k::pack30(c.launch(), coef + (size_t)b * n_felts, n_felts, d_out + (size_t)b * stride, len);
+            uint8_t* dst = pin_bytes ? pin + pin_head : staged.data();
+            FR_HIP(&c, hipMemcpyAsync(dst, d_out, staged_bytes, hipMemcpyDeviceToHost, s));
+            host_bytes = dst;
+        }
+        FR_HIP(&c, hipStreamSynchronize(s));
+        FR_HIP(&c, hipGetLastError());
+        memcpy(roots.data(), pin, roots.size());
+        memcpy(flags.data(), pin + 32 * (size_t)n_blobs, sizeof(uint32_t) * n_blobs);
+        return FRIEDA_OK;
+    };
+    rc = run();
+    if (rc != FRIEDA_OK) {
+        (void)hipStreamSynchronize(c.stream);  // (before the slab goes)
+        return rc;
+    }
+    // a blob whose coefficients are no blob's image does not commit, whatever the root of their evaluation is: both cases in
+    // rebuilt_accept's words
+    for (uint32_t b = 0; b < n_blobs; b++)
+        if (flags[b] || memcmp(roots.data() + 32 * (size_t)b, commitments + 32 * (size_t)b, 32) != 0) return c.fail(FRIEDA_ERR_ARG, rebuilt_mismatch_text(mismatch, b));
+    std::vector<frieda_encoded*> encs(n_blobs, nullptr);
+    rc = blk.publish(roots.data(), encs.data());
+    if (rc != FRIEDA_OK) return c.fail(rc, "host allocation failed");
+    if (want_bytes)
+        for (uint32_t b = 0; b < n_blobs; b++) memcpy(out_bytes + (size_t)b * len, host_bytes + (size_t)b * stride, len);
+    memcpy(out_encs, encs.data(), sizeof(frieda_encoded*) * n_blobs);
     return FRIEDA_OK;
 }
 

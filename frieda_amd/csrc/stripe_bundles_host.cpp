@@ -291,13 +291,16 @@ int frieda_verify_stripe_bundles_many(frieda_ctx* ctx, const uint8_t* commitment
     FR_GUARD_END(ctx)
 }
 
-int frieda_reconstruct_blobs_from_stripe_bundles(frieda_ctx* ctx, const uint8_t* commitments, uint32_t n_blobs, uint32_t log_blowup_factor, size_t len,
-                                                 uint32_t log_cell, const uint32_t* stripe_index, const uint32_t* bundle_first, uint32_t n_bundles,
-                                                 const uint32_t* values, const uint8_t* witness, const uint64_t* witness_first, uint8_t* out_bytes,
-                                                 uint8_t* out_status, size_t* n_stripes_used) {
-    if (!ctx || !commitments || !n_stripes_used || (len && !out_bytes)) return FRIEDA_ERR_ARG;
+namespace {
+// frieda_reconstruct_blobs_from_stripe_bundles (out_encs == nullptr: its tail rebuild_blobs_from_stripes) and
+// frieda_rebuild_encoded_blobs_from_stripe_bundles (out_encs[n_blobs], all NULL on entry; out_bytes optional)
+int reconstruct_blobs_from_stripe_bundles(frieda_ctx* ctx, const uint8_t* commitments, uint32_t n_blobs, uint32_t log_blowup_factor, size_t len,
+                                          uint32_t log_cell, const uint32_t* stripe_index, const uint32_t* bundle_first, uint32_t n_bundles,
+                                          const uint32_t* values, const uint8_t* witness, const uint64_t* witness_first, uint8_t* out_bytes,
+                                          uint8_t* out_status, size_t* n_stripes_used, frieda_encoded** out_encs) {
+    if (!ctx || !commitments || !n_stripes_used || (len && !out_bytes && !out_encs)) return FRIEDA_ERR_ARG;
     *n_stripes_used = 0;
-    const char* const fn = "reconstruct_blobs_from_stripe_bundles: ";
+    const char* const fn = out_encs ? "rebuild_encoded_blobs_from_stripe_bundles: " : "reconstruct_blobs_from_stripe_bundles: ";
     if (n_blobs == 0 || n_blobs > SB_REBUILD_MAX_BLOBS) return ctx->c.fail(FRIEDA_ERR_ARG, std::string(fn) + "n_blobs out of range (1 .. 256)");
     if (log_blowup_factor > FRIEDA_MAX_LOG_DOMAIN || len > ((size_t)1 << 40)) return ctx->c.fail(FRIEDA_ERR_ARG, std::string(fn) + "shape out of range");
     const uint32_t L = codec_shape(len).log_size, n = L + log_blowup_factor;
@@ -325,10 +328,30 @@ int frieda_reconstruct_blobs_from_stripe_bundles(frieda_ctx* ctx, const uint8_t*
                                           out_status, &pool);
     if (rc != FRIEDA_OK) return rc;
     if (pool.n == 0) return too_few();
-    rc = rebuild_blobs_from_stripes(ctx, pool, commitments, n_blobs, log_blowup_factor, len, log_cell, out_bytes, &nd);
+    rc = out_encs ? rebuild_encoded_from_pool(ctx, pool, commitments, n_blobs, log_blowup_factor, len, log_cell, nullptr, out_bytes, &nd, out_encs)
+                  : rebuild_blobs_from_stripes(ctx, pool, commitments, n_blobs, log_blowup_factor, len, log_cell, out_bytes, &nd);
     *n_stripes_used = nd;
     return rc == FRIEDA_ERR_ARG && nd < need ? too_few() : rc;
     FR_GUARD_END(ctx)
+}
+}  // namespace
+
+int frieda_reconstruct_blobs_from_stripe_bundles(frieda_ctx* ctx, const uint8_t* commitments, uint32_t n_blobs, uint32_t log_blowup_factor, size_t len,
+                                                 uint32_t log_cell, const uint32_t* stripe_index, const uint32_t* bundle_first, uint32_t n_bundles,
+                                                 const uint32_t* values, const uint8_t* witness, const uint64_t* witness_first, uint8_t* out_bytes,
+                                                 uint8_t* out_status, size_t* n_stripes_used) {
+    return reconstruct_blobs_from_stripe_bundles(ctx, commitments, n_blobs, log_blowup_factor, len, log_cell, stripe_index, bundle_first, n_bundles, values, witness,
+                                                 witness_first, out_bytes, out_status, n_stripes_used, nullptr);
+}
+int frieda_rebuild_encoded_blobs_from_stripe_bundles(frieda_ctx* ctx, const uint8_t* commitments, uint32_t n_blobs, uint32_t log_blowup_factor,
+                                                     size_t len, uint32_t log_cell, const uint32_t* stripe_index, const uint32_t* bundle_first,
+                                                     uint32_t n_bundles, const uint32_t* values, const uint8_t* witness,
+                                                     const uint64_t* witness_first, uint8_t* out_bytes, uint8_t* out_status,
+                                                     size_t* n_stripes_used, frieda_encoded** out_encs) {
+    if (!out_encs) return FRIEDA_ERR_ARG;
+    if (n_blobs >= 1 && n_blobs <= SB_REBUILD_MAX_BLOBS) memset(out_encs, 0, sizeof(frieda_encoded*) * n_blobs);
+    return reconstruct_blobs_from_stripe_bundles(ctx, commitments, n_blobs, log_blowup_factor, len, log_cell, stripe_index, bundle_first, n_bundles, values, witness,
+                                                 witness_first, out_bytes, out_status, n_stripes_used, out_encs);
 }
 
 }  // extern "C"

@@ -1600,12 +1600,12 @@ void merkle_root4(const Launch& L, const uint32_t* c0, const uint32_t* c1, const
 }
 
 void tree_first_layer(const Launch& L, const uint32_t* cols, size_t stride, uint32_t m, uint8_t* layers, DevTranscript* tr,
-                      const DevTranscript* tr_init, size_t tr_init_pitch) {
+                      const DevTranscript* tr_init, size_t tr_init_pitch, uint8_t* d_root) {
     TreeArgs a{};
     a.cols = cols;
     a.col_stride = stride;
     a.skip_a = m >= 1;  // the prover never reads the leaf hashes (plan_merkle_decommit, prover.cpp)
-    build_tree(L, T_LEAF4, a, m, layers, nullptr, nullptr, tr, tr_init, tr_init_pitch);
+    build_tree(L, T_LEAF4, a, m, layers, nullptr, d_root, tr, tr_init, tr_init_pitch);
 }
 
 void fold_and_tree(const Launch& L, bool circle, const uint32_t* src, size_t src_stride, uint32_t src_log, uint32_t n,

@@ -509,6 +509,112 @@ class Context {
         for (size_t b = 0; b < K; b++) blobs[b].assign(out.begin() + b * len, out.begin() + (b + 1) * len);
         return blobs;
     }
+    // ---- encoded handles for a block in one call, and straight from a rebuild (frieda_encode_batch, frieda_rebuild_encoded_*): the
+    // handles of a call share one reference-counted allocation; every Encoded frees its own share's reference ----
+    // blob b at data + b * stride
+    std::vector<Encoded> encode_batch(const uint8_t* data, size_t stride, size_t len, uint32_t count, uint32_t log_blowup_factor) {
+        std::vector<frieda_encoded*> hs(count, nullptr);
+        check(frieda_encode_batch(h_, data, stride, len, count, log_blowup_factor, hs.data()), h_);
+        return adopt(hs);
+    }
+    // what a rebuild_encoded_* call returns: the twin's bytes (empty with want_bytes = false: nothing is packed or downloaded) and the handles
+    struct RebuiltEncoded {
+        std::vector<std::vector<uint8_t>> bytes;
+        std::vector<Encoded> encs;
+    };
+    RebuiltEncoded rebuild_encoded_from_opened_cells(const Commitment& commitment, uint32_t log_blowup_factor, size_t len, uint32_t log_cell,
+                                                     const std::vector<uint32_t>& cell_index, const std::vector<uint32_t>& values,
+                                                     const std::vector<uint8_t>& paths, bool want_bytes = true, std::vector<uint8_t>* out_status = nullptr,
+                                                     size_t* n_cells_used = nullptr) {
+        size_t n_felts = 0, n_padded = 0;
+        uint32_t log_size = 0;
+        check(frieda_codec_shape(len, &n_felts, &n_padded, &log_size));
+        check_cell_shapes("rebuild_encoded_from_opened_cells", log_size + log_blowup_factor, log_cell, cell_index.size(), values.size(), paths.size());
+        std::vector<uint8_t> status(cell_index.size() + 1), out(len + 1);
+        size_t used = 0;
+        frieda_encoded* e = nullptr;
+        const int rc = frieda_rebuild_encoded_from_opened_cells(h_, commitment.data(), log_blowup_factor, len, log_cell, cell_index.data(),
+                                                                (uint32_t)cell_index.size(), values.data(), paths.data(), want_bytes ? out.data() : nullptr,
+                                                                status.data(), &used, &e);
+        return rebuilt(rc, 1, len, want_bytes, out, status, cell_index.size(), used, &e, out_status, n_cells_used);
+    }
+    RebuiltEncoded rebuild_encoded_from_cell_bundles(const Commitment& commitment, uint32_t log_blowup_factor, size_t len, uint32_t log_cell,
+                                                     const std::vector<uint32_t>& cell_index, const std::vector<uint32_t>& bundle_first,
+                                                     const std::vector<uint32_t>& values, const std::vector<uint8_t>& witness,
+                                                     const std::vector<uint64_t>& witness_first, bool want_bytes = true,
+                                                     std::vector<uint8_t>* out_status = nullptr, size_t* n_cells_used = nullptr) {
+        check_stripe_bundle_shapes("rebuild_encoded_from_cell_bundles", 1, log_cell, cell_index, bundle_first, values.size(), witness.size(), &witness_first);
+        const uint32_t nb = (uint32_t)bundle_first.size() - 1;
+        std::vector<uint8_t> status((size_t)nb + 1), out(len + 1);
+        size_t used = 0;
+        frieda_encoded* e = nullptr;
+        const int rc = frieda_rebuild_encoded_from_cell_bundles(h_, commitment.data(), log_blowup_factor, len, log_cell, cell_index.data(), bundle_first.data(), nb,
+                                                                values.data(), witness.data(), witness_first.data(), want_bytes ? out.data() : nullptr,
+                                                                status.data(), &used, &e);
+        return rebuilt(rc, 1, len, want_bytes, out, status, nb, used, &e, out_status, n_cells_used);
+    }
+    RebuiltEncoded rebuild_encoded_blobs_from_opened_stripes(const std::vector<Commitment>& commitments, uint32_t log_blowup_factor, size_t len,
+                                                             uint32_t log_cell, const std::vector<uint32_t>& stripe_index, const std::vector<uint32_t>& values,
+                                                             const std::vector<uint8_t>& paths, bool want_bytes = true,
+                                                             std::vector<uint8_t>* out_status = nullptr, size_t* n_stripes_used = nullptr) {
+        size_t n_felts = 0, n_padded = 0;
+        uint32_t log_size = 0;
+        check(frieda_codec_shape(len, &n_felts, &n_padded, &log_size));
+        const size_t K = commitments.size(), cells = stripe_index.size() * K;
+        if (K == 0) throw Error(FRIEDA_ERR_ARG, "rebuild_encoded_blobs_from_opened_stripes: at least one blob");
+        check_cell_shapes("rebuild_encoded_blobs_from_opened_stripes", log_size + log_blowup_factor, log_cell, cells, values.size(), paths.size());
+        const std::vector<uint8_t> flat = flat_commitments(commitments);
+        std::vector<uint8_t> status(cells + 1), out(len * K + 1);
+        size_t used = 0;
+        std::vector<frieda_encoded*> es(K, nullptr);
+        const int rc = frieda_rebuild_encoded_blobs_from_opened_stripes(h_, flat.data(), (uint32_t)K, log_blowup_factor, len, log_cell, stripe_index.data(),
+                                                                        (uint32_t)stripe_index.size(), values.data(), paths.data(),
+                                                                        want_bytes ? out.data() : nullptr, status.data(), &used, es.data());
+        return rebuilt(rc, K, len, want_bytes, out, status, cells, used, es.data(), out_status, n_stripes_used);
+    }
+    RebuiltEncoded rebuild_encoded_blobs_from_stripe_bundles(const std::vector<Commitment>& commitments, uint32_t log_blowup_factor, size_t len,
+                                                             uint32_t log_cell, const std::vector<uint32_t>& stripe_index,
+                                                             const std::vector<uint32_t>& bundle_first, const std::vector<uint32_t>& values,
+                                                             const std::vector<uint8_t>& witness, const std::vector<uint64_t>& witness_first,
+                                                             bool want_bytes = true, std::vector<uint8_t>* out_status = nullptr,
+                                                             size_t* n_stripes_used = nullptr) {
+        const size_t K = commitments.size();
+        check_stripe_bundle_shapes("rebuild_encoded_blobs_from_stripe_bundles", K, log_cell, stripe_index, bundle_first, values.size(), witness.size(), &witness_first);
+        const std::vector<uint8_t> flat = flat_commitments(commitments);
+        const uint32_t nb = (uint32_t)bundle_first.size() - 1;
+        std::vector<uint8_t> status((size_t)nb * K + 1), out(len * K + 1);
+        size_t used = 0;
+        std::vector<frieda_encoded*> es(K, nullptr);
+        const int rc = frieda_rebuild_encoded_blobs_from_stripe_bundles(h_, flat.data(), (uint32_t)K, log_blowup_factor, len, log_cell, stripe_index.data(),
+                                                                        bundle_first.data(), nb, values.data(), witness.data(), witness_first.data(),
+                                                                        want_bytes ? out.data() : nullptr, status.data(), &used, es.data());
+        return rebuilt(rc, K, len, want_bytes, out, status, (size_t)nb * K, used, es.data(), out_status, n_stripes_used);
+    }
+
+  private:
+    static std::vector<Encoded> adopt(const std::vector<frieda_encoded*>& hs) {
+        std::vector<Encoded> out;
+        out.reserve(hs.size());  // (no throw between here and the last adoption: reserve did the allocating)
+        for (frieda_encoded* h : hs) out.emplace_back(h);
+        return out;
+    }
+    // the shared tail of the rebuild_encoded_* wrappers: statuses and counts out first (also on an error), then the check, then the results
+    RebuiltEncoded rebuilt(int rc, size_t K, size_t len, bool want_bytes, const std::vector<uint8_t>& out, std::vector<uint8_t>& status, size_t n_status,
+                           size_t used, frieda_encoded* const* es, std::vector<uint8_t>* out_status, size_t* n_used) {
+        status.resize(n_status);
+        if (out_status) *out_status = status;
+        if (n_used) *n_used = used;
+        check(rc, h_);
+        RebuiltEncoded r;
+        r.encs = adopt(std::vector<frieda_encoded*>(es, es + K));
+        if (want_bytes) {
+            r.bytes.resize(K);
+            for (size_t b = 0; b < K; b++) r.bytes[b].assign(out.begin() + b * len, out.begin() + (b + 1) * len);
+        }
+        return r;
+    }
+
+  public:
     // Level B openings over caller device buffers (frieda_dev_gather, frieda_dev_gather_hashes, frieda_merkle_decommit)
     // rows[i * ncols + c] = column c at idx[i]
     std::vector<uint32_t> dev_gather(const uint32_t* d_cols, size_t stride, uint32_t ncols, const std::vector<uint64_t>& idx) {

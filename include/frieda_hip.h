@@ -145,7 +145,8 @@ int frieda_commit_and_generate_proof_device(frieda_ctx* ctx, const void* d_data,
  * and takes no context), frieda_open_cell_bundles, frieda_verify_cell_bundles_many, frieda_reconstruct_from_cell_bundles
  * (frieda_cell_bundle_witness_count and frieda_verify_cell_bundles are host-only and take no context), frieda_open_stripe_bundles,
  * frieda_verify_stripe_bundles_many, frieda_reconstruct_blobs_from_stripe_bundles (frieda_verify_stripe_bundles is host-only and takes no
- * context).  Level B calls that only read the twiddle cache and caller buffers stay available.
+ * context), frieda_encode_batch and the four frieda_rebuild_encoded_* calls.  Level B calls that only read the twiddle cache and caller
+ * buffers stay available.
  * A blob passed to _begin_device must stay valid until _finish returns. */
 int frieda_prove_begin(frieda_ctx* ctx, const uint8_t* data, size_t len, const uint64_t* seed, frieda_pcs_config cfg);
 int frieda_prove_begin_device(frieda_ctx* ctx, const void* d_data, size_t len, const uint64_t* seed, frieda_pcs_config cfg);
@@ -513,6 +514,65 @@ int frieda_reconstruct_blobs_from_stripe_bundles(frieda_ctx* ctx, const uint8_t*
                                                  uint32_t log_cell, const uint32_t* stripe_index, const uint32_t* bundle_first, uint32_t n_bundles,
                                                  const uint32_t* values, const uint8_t* witness, const uint64_t* witness_first, uint8_t* out_bytes,
                                                  uint8_t* out_status, size_t* n_stripes_used);
+
+/* ---- encoded handles for a block in one call, and straight from a rebuild ---------------------------------------------------------
+ * Everything a provider serves starts from a frieda_encoded handle.  The calls below make handles without one frieda_encode per blob:
+ * the K handles of a call share ONE allocation in GPU memory, reference-counted: each handle is freed on its own with
+ * frieda_encoded_free (from any thread; two threads may free different handles of one call at once), the allocation goes with the last
+ * one, and frieda_encoded_bytes of a handle is its own share.  A handle made here is indistinguishable from frieda_encode of the same
+ * bytes through every call that takes a handle: the same commitment and shape, byte-identical answers from the openers and
+ * byte-identical proofs from frieda_prove_seeds; it outlives the context that made it, as every handle does.  (The tree-skip threshold
+ * recorded in a handle may differ: the trees of a call of several blobs are built under FRIEDA_TREE_SKIP_LOG, a lone one under
+ * FRIEDA_TREE_SKIP_LONE_LOG; the openers read the threshold from the handle.)  All pointers are host arrays or handles.
+ * What the code saves is one allocation and one latency chain per block instead of K, and per rebuild one encode, one tree and two
+ * transfers.  Measured on one MI355X against what each call replaces, in one run (profiles/r18_encoded_block.txt,
+ * tools/encoded_block_timing.py; records, not gates): frieda_encode_batch 3.00 ms against 6.31 ms for the loop of frieda_encode over 16
+ * blobs of 128 KiB, 0.50 ms against 2.61 ms over 64 blobs of 1 KiB; a block of 16 rebuilt from 513 stripes of 64 entries with its handles
+ * 3.85 ms (stripe bundles 3.57 ms) against 11.47 ms (11.20 ms) for the reconstruct call followed by 16 frieda_encode, 2.76 / 2.49 ms when
+ * the bytes are not wanted; ONE 128 KiB blob rebuilt from 513 cells with its handle 1.00 ms against 1.02 ms (bundles: 1.01 against
+ * 1.05 ms) — level with the pair it replaces when the bytes are wanted, not a gain; 0.89 / 0.90 ms without them.  A 2^24 domain: not measured. */
+/* Provider of a block: count blobs of len bytes each, blob b at data + b * stride (the layout and the argument rules of
+ * frieda_commit_batch: 1 <= count <= 65535, stride >= len when count > 1) -> out_encs[count].  One upload, the batched launches of
+ * frieda_commit_batch with the evaluation and the tree kept, one download of the count roots, one synchronisation.  The fused small-domain
+ * route and the general route are chosen as frieda_encode chooses.  NOT cut into passes: FRIEDA_ERR_NOMEM when the workspace (blobs plus
+ * coefficients) or the allocation of the handles does not fit; ctx stays usable.  Memory: the handles take count * frieda_encoded_bytes;
+ * on the general route (domains above 2^15) the workspace is about as large AGAIN, although the blobs and coefficients fill a fraction
+ * of it: the kernels take one stride per launch for everything they write, so the coefficients sit at the handles' stride (16 blobs of
+ * 128 KiB: 640 MiB of handles and about as much workspace).  The fused small route needs count * len of workspace only.  On any error out_encs is untouched.  FRIEDA_ERR_ARG
+ * while a proof is in flight on ctx. */
+int frieda_encode_batch(frieda_ctx* ctx, const uint8_t* data, size_t stride, size_t len, uint32_t count, uint32_t log_blowup_factor,
+                        frieda_encoded** out_encs);
+/* The node that rebuilds in order to serve: each call below is the reconstruct call named beside it plus handles.  On any input it
+ * returns FRIEDA_OK exactly when that call does on the same arguments, with the same status bytes and the same *n_..._used, and on
+ * FRIEDA_OK the same out_bytes.  (Apart from memory: once the accepted cells are known to suffice, the allocation of the handles is made,
+ * n_blobs * frieda_encoded_bytes, and FRIEDA_ERR_NOMEM is possible where the twin needs less.  A call with too few cells allocates
+ * nothing for handles.)  out_bytes may be NULL here: the caller wants only the handle, and nothing is packed or downloaded.
+ * On FRIEDA_OK out_enc / out_encs[n_blobs] receive handles of the rebuilt blobs; on any error every entry is NULL.
+ * Route: verify and pool as the twin does; the point reconstruction's closing re-encode (the one every offered sample is compared
+ * with) IS the handle's evaluation; the coefficients must be the image of a blob of len bytes (every felt below 2^30, no bit above the
+ * blob's last one, zero padding: otherwise the twin's "does not commit" FRIEDA_ERR_ARG — a committer can publish the root of a
+ * polynomial that is no blob's image); one tree over the evaluation gives the root that must equal the commitment.  The rebuilt bytes
+ * are never uploaded again.  The block calls keep n_blobs <= 256. */
+/* frieda_reconstruct_from_opened_cells + the handle */
+int frieda_rebuild_encoded_from_opened_cells(frieda_ctx* ctx, const uint8_t commitment[32], uint32_t log_blowup_factor, size_t len, uint32_t log_cell,
+                                             const uint32_t* cell_index, uint32_t n_cells, const uint32_t* values, const uint8_t* paths,
+                                             uint8_t* out_bytes, uint8_t* out_status, size_t* n_cells_used, frieda_encoded** out_enc);
+/* frieda_reconstruct_from_cell_bundles + the handle */
+int frieda_rebuild_encoded_from_cell_bundles(frieda_ctx* ctx, const uint8_t commitment[32], uint32_t log_blowup_factor, size_t len, uint32_t log_cell,
+                                             const uint32_t* cell_index, const uint32_t* bundle_first, uint32_t n_bundles, const uint32_t* values,
+                                             const uint8_t* witness, const uint64_t* witness_first, uint8_t* out_bytes, uint8_t* out_status,
+                                             size_t* n_cells_used, frieda_encoded** out_enc);
+/* frieda_reconstruct_blobs_from_opened_stripes + out_encs[n_blobs] */
+int frieda_rebuild_encoded_blobs_from_opened_stripes(frieda_ctx* ctx, const uint8_t* commitments, uint32_t n_blobs, uint32_t log_blowup_factor,
+                                                     size_t len, uint32_t log_cell, const uint32_t* stripe_index, uint32_t n_stripes,
+                                                     const uint32_t* values, const uint8_t* paths, uint8_t* out_bytes, uint8_t* out_status,
+                                                     size_t* n_stripes_used, frieda_encoded** out_encs);
+/* frieda_reconstruct_blobs_from_stripe_bundles + out_encs[n_blobs] */
+int frieda_rebuild_encoded_blobs_from_stripe_bundles(frieda_ctx* ctx, const uint8_t* commitments, uint32_t n_blobs, uint32_t log_blowup_factor,
+                                                     size_t len, uint32_t log_cell, const uint32_t* stripe_index, const uint32_t* bundle_first,
+                                                     uint32_t n_bundles, const uint32_t* values, const uint8_t* witness,
+                                                     const uint64_t* witness_first, uint8_t* out_bytes, uint8_t* out_status,
+                                                     size_t* n_stripes_used, frieda_encoded** out_encs);
 
 /* ---- batch policy: how a stream of equal-length blobs is cut into batched calls ("bytes in flight") -------------------------
  * Every kernel of a batched call covers all its blobs, so the launch / Fiat-Shamir latency chain is paid once per call: small
