@@ -109,6 +109,10 @@ extern "C" {
     pub fn frieda_prove_seeds(ctx: *mut frieda_ctx, enc: *const frieda_encoded, seeds: *const u64, n_seeds: u32, cfg: frieda_pcs_config, out_proofs: *mut *mut frieda_proof) -> c_int;
     pub fn frieda_commit_and_generate_proofs_for_seeds(ctx: *mut frieda_ctx, data: *const u8, len: usize, seeds: *const u64, n_seeds: u32, cfg: frieda_pcs_config, out_commitment: *mut u8, out_proofs: *mut *mut frieda_proof) -> c_int;
     pub fn frieda_seeds_workspace_bytes(len: usize, cfg: frieda_pcs_config, n_seeds: u32) -> usize;
+    pub fn frieda_prove_seeds_blobs_begin(ctx: *mut frieda_ctx, encs: *const *const frieda_encoded, n_blobs: u32, seeds: *const u64, n_seeds: u32, cfg: frieda_pcs_config) -> c_int;
+    pub fn frieda_prove_seeds_blobs_finish(ctx: *mut frieda_ctx, out_proofs: *mut *mut frieda_proof) -> c_int;
+    pub fn frieda_prove_seeds_blobs(ctx: *mut frieda_ctx, encs: *const *const frieda_encoded, n_blobs: u32, seeds: *const u64, n_seeds: u32, cfg: frieda_pcs_config, out_proofs: *mut *mut frieda_proof) -> c_int;
+    pub fn frieda_seeds_blobs_workspace_bytes(len: usize, cfg: frieda_pcs_config, n_blobs: u32, n_seeds: u32) -> usize;
     pub fn frieda_commit_batch(ctx: *mut frieda_ctx, data: *const u8, stride: usize, len: usize, count: u32, log_blowup_factor: u32, out_roots: *mut u8) -> c_int;
     pub fn frieda_commit_batch_device(ctx: *mut frieda_ctx, d_data: *const c_void, stride: usize, len: usize, count: u32, log_blowup_factor: u32, out_roots: *mut u8) -> c_int;
     pub fn frieda_generate_proof(ctx: *mut frieda_ctx, data: *const u8, len: usize, seed: *const u64, cfg: frieda_pcs_config, out: *mut *mut frieda_proof) -> c_int;

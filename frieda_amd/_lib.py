@@ -123,6 +123,10 @@ def lib():
         "frieda_prove_seeds": (C.c_int, [vp, vp, u64p, u32, PcsConfigC, pp]),
         "frieda_commit_and_generate_proofs_for_seeds": (C.c_int, [vp, vp, sz, u64p, u32, PcsConfigC, vp, pp]),
         "frieda_seeds_workspace_bytes": (sz, [sz, PcsConfigC, u32]),
+        "frieda_prove_seeds_blobs_begin": (C.c_int, [vp, vp, u32, u64p, u32, PcsConfigC]),
+        "frieda_prove_seeds_blobs_finish": (C.c_int, [vp, pp]),
+        "frieda_prove_seeds_blobs": (C.c_int, [vp, vp, u32, u64p, u32, PcsConfigC, pp]),
+        "frieda_seeds_blobs_workspace_bytes": (sz, [sz, PcsConfigC, u32, u32]),
         "frieda_commit_batch": (C.c_int, [vp, vp, sz, sz, u32, u32, vp]),
         "frieda_commit_batch_device": (C.c_int, [vp, vp, sz, sz, u32, u32, vp]),
         "frieda_multi_create": (C.c_int, [C.POINTER(C.c_int), u32, pp]),

@@ -371,6 +371,30 @@ class Context:
         self.prove_seeds_begin(encoded, seeds, pcs_config)
         return self.prove_seeds_finish()
 
+    # ---- a block under many seeds: K handles x S seeds in one call ----
+    def prove_seeds_blobs_begin(self, encs, seeds, pcs_config):
+        """Enqueue len(encs) * len(seeds) proofs: every encoded blob of the block under every seed of the one list.  The handles must stay
+        open until prove_seeds_blobs_finish() returns."""
+        encs = list(encs)
+        seeds = [int(x) for x in seeds]
+        handles = (C.c_void_p * max(1, len(encs)))(*[e._handle() for e in encs])
+        arr = (C.c_uint64 * max(1, len(seeds)))(*seeds)
+        _check(self._L.frieda_prove_seeds_blobs_begin(self._h, handles, len(encs), arr, len(seeds), pcs_config._c()), self._h)
+        self._seeds_blobs_in_flight = (len(encs), len(seeds))
+
+    def prove_seeds_blobs_finish(self):
+        n_blobs, n_seeds = getattr(self, "_seeds_blobs_in_flight", (0, 0))
+        self._seeds_blobs_in_flight = (0, 0)
+        count = n_blobs * n_seeds
+        outs = (C.c_void_p * max(1, count))()
+        _check(self._L.frieda_prove_seeds_blobs_finish(self._h, outs), self._h)
+        return [[Proof(C.c_void_p(outs[b * n_seeds + s])) for s in range(n_seeds)] for b in range(n_blobs)]
+
+    def prove_seeds_blobs(self, encs, seeds, pcs_config):
+        """[[Proof]]: proofs[b][s] is prove_seeds(encs[b], [seeds[s]], pcs_config)[0], byte for byte — one call for the whole block."""
+        self.prove_seeds_blobs_begin(encs, seeds, pcs_config)
+        return self.prove_seeds_blobs_finish()
+
     def commit_and_generate_proofs_for_seeds(self, data, seeds, pcs_config):
         """(commitment, [Proof]) for a caller that has every seed at once: encode, prove, free."""
         a = _as_bytes(data)
@@ -1255,6 +1279,12 @@ def seeds_workspace_bytes(length, pcs_config, n_seeds):
     return int(_lib.lib().frieda_seeds_workspace_bytes(length, pcs_config._c(), n_seeds))
 
 
+def seeds_blobs_workspace_bytes(length, pcs_config, n_blobs, n_seeds):
+    """Workspace a prove_seeds_blobs call of n_blobs handles under n_seeds seeds asks of its context, the handles excluded
+    (frieda_seeds_blobs_workspace_bytes); 0: refused shape.  At n_blobs == 1: seeds_workspace_bytes."""
+    return int(_lib.lib().frieda_seeds_blobs_workspace_bytes(length, pcs_config._c(), n_blobs, n_seeds))
+
+
 def batch_plan(length, count, pcs_config=None, in_flight=2, prove=True, ctx=None, log_blowup_factor=None):
     """The library's batch policy (frieda_batch_plan, include/frieda_hip.h "batch policy"): the blob count of each call, in order, for
     `count` equal-length blobs and `in_flight` contexts taking turns.  pcs_config for proofs, log_blowup_factor for commits."""
@@ -1461,6 +1491,12 @@ def open_cells_blobs(ctx, encs, log_cell, blob_index, cell_index):
         ctx._h,
     )
     return values, paths
+
+
+def prove_seeds_blobs(ctx, encs, seeds, pcs_config):
+    """Every encoded blob of a block under every seed of one list in ONE call (frieda_prove_seeds_blobs on `ctx`): a list of
+    len(encs) lists of len(seeds) Proofs."""
+    return ctx.prove_seeds_blobs(encs, seeds, pcs_config)
 
 
 def open_stripes(ctx, encs, log_cell, stripe_index):

@@ -564,6 +564,34 @@ size_t frieda_seeds_workspace_bytes(size_t len, frieda_pcs_config cfg, uint32_t 
     }
 }
 
+// ---- a block of encoded blobs under one seed list ----
+int frieda_prove_seeds_blobs_begin(frieda_ctx* ctx, const frieda_encoded* const* encs, uint32_t n_blobs, const uint64_t* seeds, uint32_t n_seeds,
+                                   frieda_pcs_config cfg) {
+    if (!ctx) return FRIEDA_ERR_ARG;
+    FR_GUARD_BEGIN
+    if (!encs) return ctx->c.fail(FRIEDA_ERR_ARG, "null list of encoded blobs");
+    if (n_blobs == 0 || n_blobs > 65535) return ctx->c.fail(FRIEDA_ERR_ARG, "n_blobs out of range");
+    std::vector<const Encoded*> es(n_blobs);
+    for (uint32_t b = 0; b < n_blobs; b++) es[b] = encs[b] ? &encs[b]->e : nullptr;
+    return prove_seeds_blobs_begin(&ctx->c, es.data(), n_blobs, seeds, n_seeds, cfg);
+    FR_GUARD_END(ctx)
+}
+// (a job is a job: the finish of prove_seeds assembles whatever batch is in flight, and so does this one)
+int frieda_prove_seeds_blobs_finish(frieda_ctx* ctx, frieda_proof** out_proofs) { return frieda_prove_seeds_finish(ctx, out_proofs); }
+int frieda_prove_seeds_blobs(frieda_ctx* ctx, const frieda_encoded* const* encs, uint32_t n_blobs, const uint64_t* seeds, uint32_t n_seeds,
+                             frieda_pcs_config cfg, frieda_proof** out_proofs) {
+    if (!out_proofs) return FRIEDA_ERR_ARG;
+    int rc = frieda_prove_seeds_blobs_begin(ctx, encs, n_blobs, seeds, n_seeds, cfg);
+    return rc != FRIEDA_OK ? rc : frieda_prove_seeds_blobs_finish(ctx, out_proofs);
+}
+size_t frieda_seeds_blobs_workspace_bytes(size_t len, frieda_pcs_config cfg, uint32_t n_blobs, uint32_t n_seeds) {
+    try {
+        return seeds_blobs_workspace_bytes(len, cfg, n_blobs, n_seeds);
+    } catch (...) {
+        return 0;
+    }
+}
+
 int frieda_commit_batch(frieda_ctx* ctx, const uint8_t* data, size_t stride, size_t len, uint32_t count, uint32_t log_blowup_factor,
                         uint8_t* out_roots) {
     if (!ctx || !out_roots || (!data && len) || count == 0) return FRIEDA_ERR_ARG;

@@ -68,6 +68,16 @@ __global__ __launch_bounds__(DC_THREADS) void decommit_kernel(DecommitArgs a) {
     const uint32_t blob = blockIdx.y;
     const size_t boff = (size_t)blob * a.bstride;
     const size_t boff0 = a.first_shared ? 0 : boff;  // layer 0 of a prove_seeds job: the encoded blob every seed shares
+    // ... or, for a block of encoded blobs, the one of this job's row (the job number is uniform: scalar loads)
+    const uint32_t* vals0 = a.vals[0];
+    const uint8_t* tree0 = a.trees[0];
+    uint32_t skip_log0 = a.skip_log0;
+    if (a.blk_table) {
+        const SeedsBlobRow& row = a.blk_table[a.blk_job[blob]];
+        vals0 = row.eval;
+        tree0 = row.tree;
+        skip_log0 = row.skip_log;
+    }
     const DevTranscript* tr = a.tr + blob;
     uint8_t* out = a.out + (size_t)blob * a.out_stride;
     uint32_t* hdr = reinterpret_cast<uint32_t*>(out);
@@ -154,14 +164,14 @@ __global__ __launch_bounds__(DC_THREADS) void decommit_kernel(DecommitArgs a) {
     u32x4* oh = reinterpret_cast<u32x4*>(out + a.hashes_off);
     // Proof.evaluations (src/proof.rs:62-66): the four coordinates at every query
     {
-        const uint32_t* v0 = reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(a.vals[0]) + boff0);
+        const uint32_t* v0 = reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(vals0) + boff0);
         for (uint32_t e = gt; e < 4 * nu; e += gstride) ow[e] = v0[((size_t)(e & 3) << n) + s_u[e >> 2]];
     }
     // fri_witness of layer li: the values at E_{li+1}.  Dense grid (layer, slot, coordinate); empty slots are skipped.
     for (uint32_t e = gt; e < 4 * nu * nl; e += gstride) {
         const uint32_t li = e / (4 * nu), r = e - li * 4 * nu, k = r >> 2, c = r & 3;
         if (k < s_cnt[li + 1]) {
-            const uint32_t* v = reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(a.vals[li]) + (li ? boff : boff0));
+            const uint32_t* v = reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(li ? a.vals[li] : vals0) + (li ? boff : boff0));
             ow[4 * nu + 4 * (s_base[li + 1] + k) + c] = v[((size_t)c << (n - li)) + s_E[li * nu + k]];
         }
     }
@@ -181,24 +191,24 @@ __global__ __launch_bounds__(DC_THREADS) void decommit_kernel(DecommitArgs a) {
                 for (int j = 0; j < 4; j++) {
                     const uint32_t li = li0 + j;
                     // (a level the tree does not hold is re-hashed below, by the thread of the entry's first half)
-                    if (li < li_end && !(n - li >= (li ? a.skip_log : a.skip_log0) && level + 2 >= n - li)) {
-                        const uint8_t* tree = a.trees[li] + (li ? boff : boff0) + (((size_t)64 << (n - li)) - ((size_t)64 << level));
+                    if (li < li_end && !(n - li >= (li ? a.skip_log : skip_log0) && level + 2 >= n - li)) {
+                        const uint8_t* tree = (li ? a.trees[li] : tree0) + (li ? boff : boff0) + (((size_t)64 << (n - li)) - ((size_t)64 << level));
                         v[j] = reinterpret_cast<const u32x4*>(tree + 32 * (size_t)child)[half];
                     }
                 }
 #pragma unroll
                 for (int j = 0; j < 4; j++) {
                     const uint32_t li = li0 + j;
-                    if (li < li_end && !(n - li >= (li ? a.skip_log : a.skip_log0) && level + 2 >= n - li)) oh[2 * (size_t)(s_hoff[li] + (idx - s_base[li + 2])) + half] = v[j];
+                    if (li < li_end && !(n - li >= (li ? a.skip_log : skip_log0) && level + 2 >= n - li)) oh[2 * (size_t)(s_hoff[li] + (idx - s_base[li + 2])) + half] = v[j];
                 }
             }
             // the (at most two) layers in which this entry sits one or two levels above the leaves of a tree that keeps neither
             if (half == 0) {
 #pragma unroll 1
                 for (uint32_t li = (s >= 3 ? s - 3 : 0); li < li_end; li++) {  // level + 2 >= n - li  <=>  li >= s - 3
-                    if (n - li < (li ? a.skip_log : a.skip_log0)) continue;
+                    if (n - li < (li ? a.skip_log : skip_log0)) continue;
                     uint32_t h[8];
-                    node_from_values(reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(a.vals[li]) + (li ? boff : boff0)), n - li, level, child, h);
+                    node_from_values(reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(li ? a.vals[li] : vals0) + (li ? boff : boff0)), n - li, level, child, h);
                     u32x4* o = oh + 2 * (size_t)(s_hoff[li] + (idx - s_base[li + 2]));
                     o[0] = u32x4{h[0], h[1], h[2], h[3]};
                     o[1] = u32x4{h[4], h[5], h[6], h[7]};

@@ -271,6 +271,10 @@ int encode_batch(Ctx* ctx, const uint8_t* data, size_t data_stride, size_t len, 
 int prove_seeds_begin(Ctx* ctx, const Encoded* enc, const uint64_t* seeds, uint32_t n_seeds, frieda_pcs_config cfg);
 // arena bytes prove_seeds_begin asks for (the Encoded excluded); 0: a shape the prover refuses
 size_t seeds_workspace_bytes(size_t len, frieda_pcs_config cfg, uint32_t n_seeds);
+// A block of encoded blobs of one shape under ONE seed list: n_blobs * n_seeds jobs in one launch chain, job b * n_seeds + s = encs[b] under
+// seeds[s].  Finished by prove_finish_batch like every batch.  The handles are only read.
+int prove_seeds_blobs_begin(Ctx* ctx, const Encoded* const* encs, uint32_t n_blobs, const uint64_t* seeds, uint32_t n_seeds, frieda_pcs_config cfg);
+size_t seeds_blobs_workspace_bytes(size_t len, frieda_pcs_config cfg, uint32_t n_blobs, uint32_t n_seeds);
 int commit_batch(Ctx* ctx, const uint8_t* data, size_t data_stride, size_t len, uint32_t count, bool data_on_device, uint32_t log_blowup,
                  uint8_t* out_roots, const uint8_t* const* host_ptrs = nullptr);
 // split form (frieda_commit_many alternates two contexts: the upload of one unit runs under the kernels of the other): _begin

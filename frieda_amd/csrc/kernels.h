@@ -316,22 +316,43 @@ void small_encode_and_first_tree(const Launch& L, const uint8_t* d_data, size_t 
 void encode_and_first_tree(const Launch& L, const uint32_t* d_coef, size_t coef_stride, uint32_t Lc, uint32_t n, const uint32_t* d_tw,
                            DomainScalars ds, uint32_t* d_eval, size_t eval_stride, uint8_t* d_layers, uint8_t* d_scratch, uint8_t* d_root,
                            DevTranscript* tr, const DevTranscript* tr_init = nullptr, size_t tr_init_pitch = 0, const BlobSource* blob = nullptr);
+// A block of encoded blobs proved under one seed list in one call (frieda_prove_seeds_blobs): job y = blob y / n_seeds under seed
+// y % n_seeds.  Everything a job reads of its first layer comes from its blob's row, found through job_row[y] (no division in the kernels;
+// y is workgroup-uniform, so the lookup is scalar loads).  The seed-looped kernel's workgroup y serves the jobs
+// [group_first[y], min(group_first[y] + group, end of that blob's jobs)): a group never straddles two blobs.
+struct SeedsBlobRow {
+    const uint32_t* eval;  // 4 columns of 2^n words
+    const uint8_t* tree;   // the first-layer tree (leaves-first), built with THIS blob's threshold
+    const uint8_t* root;   // 8 words
+    uint32_t skip_log;
+    uint32_t pad;
+};
+struct SeedsBlock {
+    const SeedsBlobRow* table = nullptr;  // n_blobs rows, all of one domain; null: not a block job
+    const uint32_t* job_row = nullptr;    // n_blobs * n_seeds row numbers
+    const uint32_t* group_first = nullptr;  // n_blobs * ceil(n_seeds / group) first jobs (seeds_group > 0 only)
+    uint32_t n_blobs = 0, n_seeds = 0;      // (host side: the launch shapes)
+};
 // fold the layer `src` (log size src_log; circle evaluation or line layer) with the alpha in tr into dst_vals and build the
 // tree of the folded layer in the same launches (leaf hashes not written, as above); finishes with the channel step
 // shared_src (prove_seeds: the blobs of the launch are the seeds of ONE encoded blob): `src` is the same for every blob (stride 0) while
 // dst_vals, d_layers and tr keep the batch stride; seeds_group > 0 with a circle source: the seed-looped kernel (one workgroup folds and
 // hashes for `seeds_group` consecutive seeds from one read of the source) where the launch has the register-subtree shape
+// blk (prove_seeds_blobs, with shared_src and a circle source): job y folds the evaluation of its row; `src` is not read
 void fold_and_tree(const Launch& L, bool circle, const uint32_t* src, size_t src_stride, uint32_t src_log, uint32_t n,
                    const uint32_t* d_itw, DomainScalars ds, uint32_t* dst_vals, uint8_t* d_layers, DevTranscript* tr, bool shared_src = false,
-                   uint32_t seeds_group = 0);
+                   uint32_t seeds_group = 0, const SeedsBlock* blk = nullptr);
 // prove_seeds: the first root exists already (d_root, 8 words, shared by the blobs of the launch): initialise every blob's device transcript
 // from tr_init (pinned host memory, blob b at tr_init + b * tr_init_pitch bytes), mix the root and draw the first alpha
-void channel_after_shared_root(const Launch& L, const uint8_t* d_root, DevTranscript* tr, const DevTranscript* tr_init, size_t tr_init_pitch);
+// blk: job y's root is its row's (d_root is not read)
+void channel_after_shared_root(const Launch& L, const uint8_t* d_root, DevTranscript* tr, const DevTranscript* tr_init, size_t tr_init_pitch,
+                               const SeedsBlock* blk = nullptr);
+// (blk: as fold_and_tree, for a circle source folded inside the tail)
 // all remaining layers (each <= 2048 points) in one workgroup, ending with the last-layer interpolation + mix_felts
 constexpr uint32_t TAIL_LOG = 11;
 void fri_tail(const Launch& L, const uint32_t* src, size_t src_stride, uint32_t src_log, bool src_is_circle, uint32_t n,
               const uint32_t* d_itw, DomainScalars ds, uint32_t last_log, uint32_t last, uint32_t n_layers, uint32_t* const* vals,
-              uint8_t* const* trees, DevTranscript* tr, uint32_t* d_gnext = nullptr, bool shared_src = false);
+              uint8_t* const* trees, DevTranscript* tr, uint32_t* d_gnext = nullptr, bool shared_src = false, const SeedsBlock* blk = nullptr);
 // proof-of-work scan keyed by tr->ch.digest; atomicMin into tr->nonce
 // d_next: L.batch * GRIND_NEXT_STRIDE words of scratch (the per-blob window counters, one 128-byte line each: 2048 workgroups claim
 // windows with atomics, and counters sharing a line serialise in one L2 channel; zeroed here unless next_zeroed: fri_tail did it)
@@ -363,6 +384,9 @@ struct DecommitArgs {
     // prove_seeds: layer 0 (vals[0], trees[0]) belongs to the encoded blob every seed shares — no batch stride, and the threshold its
     // tree was built with.  Everywhere else first_shared = 0 and skip_log0 = skip_log.
     uint32_t first_shared, skip_log0;
+    // prove_seeds_blobs (first_shared set, blk_table non-null): layer 0's values, tree and threshold are those of row blk_job[y] instead
+    const SeedsBlobRow* blk_table;
+    const uint32_t* blk_job;
 };
 void decommit(const Launch& L, const DecommitArgs& a, uint32_t wgs_per_blob);
 

@@ -371,6 +371,11 @@ struct ProveJob {
     // ITS tree was built with; `first` then holds no arena offsets and the per-seed workspace starts at the first inner layer
     const Encoded* enc = nullptr;
     uint32_t first_skip_log = 0;
+    // prove_seeds_blobs: the jobs are n_seeds seeds of each handle of `block`, blob-major (job y = handle y / n_seeds); enc = block[0] stands
+    // for the shape.  Layer 0 of a job is its handle's: the kernels find it through the table `blk` points at (in the arena, uploaded by _begin)
+    std::vector<const Encoded*> block;
+    uint32_t n_seeds = 0;
+    k::SeedsBlock blk{};
     struct Blob {
         Channel ch{};
         std::vector<Hash32> roots;
@@ -536,6 +541,8 @@ static void launch_decommit(Ctx* ctx, const ProveJob& J, const k::Launch& LN) {
     a.first_shared = J.enc ? 1 : 0;
     a.vals[0] = J.enc ? J.enc->eval() : reinterpret_cast<const uint32_t*>(A + J.first.o_vals);
     a.trees[0] = J.enc ? J.enc->tree() : A + J.first.o_tree;
+    a.blk_table = J.blk.table;  // (a block of handles: layer 0 and its threshold per job, from the table)
+    a.blk_job = J.blk.job_row;
     for (uint32_t kx = 0; kx < J.n_inner; kx++) {
         a.vals[1 + kx] = reinterpret_cast<const uint32_t*>(A + J.inner[kx].o_vals);
         a.trees[1 + kx] = A + J.inner[kx].o_tree;
@@ -557,7 +564,8 @@ int prove_begin_batch_ptrs(Ctx* ctx, const uint8_t* const* blobs, size_t len, ui
 
 // `count` blobs of `len` bytes each, blob b at data + b * data_stride (or, host blobs only, at host_ptrs[b]); seeds: null or one per blob
 static int prove_begin_impl(Ctx* ctx, const uint8_t* data, size_t data_stride, size_t len, uint32_t count, bool data_on_device,
-                            const uint64_t* seeds, frieda_pcs_config cfg, const uint8_t* const* host_ptrs, const Encoded* enc);
+                            const uint64_t* seeds, frieda_pcs_config cfg, const uint8_t* const* host_ptrs, const Encoded* enc,
+                            const Encoded* const* block = nullptr, uint32_t n_block = 0);
 
 int prove_begin_batch(Ctx* ctx, const uint8_t* data, size_t data_stride, size_t len, uint32_t count, bool data_on_device,
                       const uint64_t* seeds, frieda_pcs_config cfg, const uint8_t* const* host_ptrs) {
@@ -573,9 +581,44 @@ int prove_seeds_begin(Ctx* ctx, const Encoded* enc, const uint64_t* seeds, uint3
     return prove_begin_impl(ctx, nullptr, 0, enc->len, n_seeds, true, seeds, cfg, nullptr, enc);
 }
 
+// The block form: n_seeds seeds (one list) of each of n_blobs encoded blobs of one shape, n_blobs * n_seeds jobs in one launch chain.
+// One handle is prove_seeds itself.
+int prove_seeds_blobs_begin(Ctx* ctx, const Encoded* const* encs, uint32_t n_blobs, const uint64_t* seeds, uint32_t n_seeds, frieda_pcs_config cfg) {
+    if (!encs) return ctx->fail(FRIEDA_ERR_ARG, "null list of encoded blobs");
+    if (!seeds) return ctx->fail(FRIEDA_ERR_ARG, "null seeds");
+    if (n_blobs == 0 || n_seeds == 0 || (uint64_t)n_blobs * n_seeds > 65535) return ctx->fail(FRIEDA_ERR_ARG, "n_blobs * n_seeds out of range");
+    for (uint32_t b = 0; b < n_blobs; b++) {
+        if (!encs[b] || !encs[b]->d) return ctx->fail(FRIEDA_ERR_ARG, "null encoded blob");
+        if (encs[b]->len != encs[0]->len || encs[b]->log_blowup != encs[0]->log_blowup) return ctx->fail(FRIEDA_ERR_ARG, "the encoded blobs of a block have one length and one blowup");
+        if (encs[b]->device != ctx->device) return ctx->fail(FRIEDA_ERR_ARG, "the encoded blob lives on another device");
+    }
+    if (cfg.log_blowup_factor != encs[0]->log_blowup) return ctx->fail(FRIEDA_ERR_ARG, "log_blowup_factor differs from the one the blobs were encoded with");
+    if (n_blobs == 1) return prove_seeds_begin(ctx, encs[0], seeds, n_seeds, cfg);
+    return prove_begin_impl(ctx, nullptr, 0, encs[0]->len, n_blobs * n_seeds, true, seeds, cfg, nullptr, encs[0], encs, n_blobs);
+}
+
+namespace {
+// the block table of a prove_seeds_blobs call, as the arena and the pinned staging hold it: rows, one row number per job, and (route B)
+// the first job of every seed group
+struct BlockTablePlan {
+    size_t o_job = 0, o_group = 0, bytes = 0;
+    uint32_t groups = 0;
+    BlockTablePlan(uint32_t n_blobs, uint32_t n_seeds, uint32_t group) {
+        ArenaPlan p;
+        p.take(sizeof(k::SeedsBlobRow) * n_blobs);
+        o_job = p.take(sizeof(uint32_t) * (size_t)n_blobs * n_seeds);
+        groups = group ? n_blobs * ((n_seeds + group - 1) / group) : 0;
+        o_group = p.take(sizeof(uint32_t) * groups);
+        bytes = p.off;
+    }
+};
+}  // namespace
+
 // enc non-null: prove_seeds — `count` seeds of one encoded blob (data unused; seeds non-null)
+// block non-null (with enc = block[0]): prove_seeds_blobs — count = n_block * n_seeds jobs, `seeds` holds the n_seeds of the one list
 static int prove_begin_impl(Ctx* ctx, const uint8_t* data, size_t data_stride, size_t len, uint32_t count, bool data_on_device,
-                            const uint64_t* seeds, frieda_pcs_config cfg, const uint8_t* const* host_ptrs, const Encoded* enc) {
+                            const uint64_t* seeds, frieda_pcs_config cfg, const uint8_t* const* host_ptrs, const Encoded* enc,
+                            const Encoded* const* block, uint32_t n_block) {
     const auto t_entry = std::chrono::steady_clock::now();
     FR_NO_JOB(ctx);  // a proof or a commit batch in flight owns the arena and the pinned block
     if (count == 0 || count > 65535) return ctx->fail(FRIEDA_ERR_ARG, "batch count out of range");
@@ -601,6 +644,11 @@ static int prove_begin_impl(Ctx* ctx, const uint8_t* data, size_t data_stride, s
     J.skip_log = k::tree_skip_threshold(ctx->tuning, count);
     J.enc = enc;
     J.first_skip_log = enc ? enc->skip_log : J.skip_log;
+    if (block) {
+        J.block.assign(block, block + n_block);
+        J.n_seeds = count / n_block;
+    }
+    const uint32_t n_seeds = J.n_seeds;
     J.blobs.resize(count);
     const uint32_t n = J.n = sh.n, last_log = J.last_log = last + B;
     const size_t N = J.N = sh.N;
@@ -625,6 +673,11 @@ static int prove_begin_impl(Ctx* ctx, const uint8_t* data, size_t data_stride, s
     J.o_hidx = plan.take(8 * J.max_hashes);
     J.o_wout = plan.take(4 * J.max_words);
     J.o_hout = plan.take(32 * J.max_hashes);
+    // (the table's group part is planned for the largest group count, group 1, whatever FRIEDA_SEEDS_FOLD_GROUP says: the workspace of a
+    // call is a function of its shape alone)
+    const uint32_t blk_group = block ? ctx->tuning.seeds_fold_group : 0;
+    const BlockTablePlan btp(block ? n_block : 0, n_seeds, blk_group), btp_plan(block ? n_block : 0, n_seeds, 1);
+    const size_t o_blk = block ? plan.take(btp_plan.bytes) : 0;
     rc = ctx->ensure_arena(plan.off);
     if (rc) return rc;
     // pinned staging: the transcript summaries of all blobs (header + last-layer polynomial each), or the last layer itself on
@@ -637,10 +690,13 @@ static int prove_begin_impl(Ctx* ctx, const uint8_t* data, size_t data_stride, s
     J.dec_hashes_off = J.dec_words_off + ((4 * (size_t)J.dec_max_words + 15) & ~(size_t)15);
     J.dec_stride = (J.dec_hashes_off + 32 * (size_t)J.dec_max_hashes + 255) & ~(size_t)255;
     J.dec_off = (tr_host_pitch * count + 255) & ~(size_t)255;
-    const size_t pinned_need =
+    size_t pinned_need =
         std::max<size_t>(std::max<size_t>(std::max<size_t>(tr_host_pitch * count, (sizeof(uint32_t) * 4) << last_log),
                                           (4 + 8) * J.max_words + (32 + 8) * J.max_hashes + 512),
                          J.dec_off + J.dec_stride * count);
+    // the block table is staged behind everything else: nothing writes there until the next call on this context
+    const size_t pin_blk = (pinned_need + 255) & ~(size_t)255;
+    if (block) pinned_need = pin_blk + btp.bytes;
     rc = ensure_pinned(ctx, pinned_need);
     if (rc) return rc;
     TwiddleSet tw;
@@ -693,13 +749,33 @@ static int prove_begin_impl(Ctx* ctx, const uint8_t* data, size_t data_stride, s
 
     for (uint32_t b = 0; b < count; b++) {
         J.blobs[b].ch.init();
-        if (seeds) J.blobs[b].ch.mix_u64(seeds[b]);  // src/proof.rs:40-42
+        if (seeds) J.blobs[b].ch.mix_u64(seeds[block ? b % n_seeds : b]);  // src/proof.rs:40-42
         J.blobs[b].roots.assign(1 + n_inner, Hash32{});
     }
     Channel& ch = J.blobs[0].ch;  // (the host-channel path below is single-blob)
 
     auto cols = [&](const FriLayerDev& lay, int c) { return (&lay == &first ? eval : reinterpret_cast<uint32_t*>(A + lay.o_vals)) + ((size_t)c << lay.log); };
     const uint32_t seeds_group = enc ? ctx->tuning.seeds_fold_group : 0;
+    if (block) {
+        // the per-blob table, the row of every job and the first job of every seed group: one upload per call, ahead of every launch
+        uint8_t* hp = static_cast<uint8_t*>(ctx->pinned) + pin_blk;
+        k::SeedsBlobRow* rows = reinterpret_cast<k::SeedsBlobRow*>(hp);
+        uint32_t* job_row = reinterpret_cast<uint32_t*>(hp + btp.o_job);
+        uint32_t* group_first = reinterpret_cast<uint32_t*>(hp + btp.o_group);
+        const uint32_t gpb = blk_group ? (n_seeds + blk_group - 1) / blk_group : 0;  // groups per blob: a short last one, none across two blobs
+        for (uint32_t r = 0; r < n_block; r++) {
+            rows[r] = k::SeedsBlobRow{block[r]->eval(), block[r]->tree(), block[r]->d + block[r]->o_root, block[r]->skip_log, 0};
+            for (uint32_t sd = 0; sd < n_seeds; sd++) job_row[r * n_seeds + sd] = r;
+            for (uint32_t g = 0; g < gpb; g++) group_first[r * gpb + g] = r * n_seeds + g * blk_group;
+        }
+        FR_HIP(ctx, hipMemcpyAsync(A + o_blk, hp, btp.bytes, hipMemcpyHostToDevice, s));
+        J.blk.table = reinterpret_cast<const k::SeedsBlobRow*>(A + o_blk);
+        J.blk.job_row = reinterpret_cast<const uint32_t*>(A + o_blk + btp.o_job);
+        J.blk.group_first = blk_group ? reinterpret_cast<const uint32_t*>(A + o_blk + btp.o_group) : nullptr;
+        J.blk.n_blobs = n_block;
+        J.blk.n_seeds = n_seeds;
+    }
+    const k::SeedsBlock* blk = block ? &J.blk : nullptr;
     std::vector<Hash32>& roots = J.blobs[0].roots;
     std::vector<QM31>& lastv = J.blobs[0].lastv;
     if (dev_channel) {
@@ -720,7 +796,7 @@ static int prove_begin_impl(Ctx* ctx, const uint8_t* data, size_t data_stride, s
         // the encode's last pass runs fused with FriProver::commit_first_layer's leaf hashing (src/proof.rs:48-52); small domains: unpack +
         // encode + first tree in one launch, straight from the blob
         if (enc)  // the first tree and its root exist: only the transcripts' step behind that root — mix_root, first alpha — per seed
-            k::channel_after_shared_root(LN, enc->d + enc->o_root, d_tr, reinterpret_cast<const DevTranscript*>(ctx->pinned), tr_host_pitch);
+            k::channel_after_shared_root(LN, enc->d + enc->o_root, d_tr, reinterpret_cast<const DevTranscript*>(ctx->pinned), tr_host_pitch, blk);
         else if (small)
             k::small_encode_and_first_tree(LN, d_data, len, d_data_stride, sh.L, n, tw.d_tw, tw.ds, eval, N, A + first.o_tree, nullptr, nullptr, d_tr,
                                            reinterpret_cast<const DevTranscript*>(ctx->pinned), tr_host_pitch);
@@ -736,7 +812,7 @@ static int prove_begin_impl(Ctx* ctx, const uint8_t* data, size_t data_stride, s
         const uint32_t tail_run_log = ctx->tuning.tail_run_log;
         while (kx < n_inner && inner[kx].log > tail_run_log) {
             k::fold_and_tree(LN, circle, cols(*cur, 0), (size_t)1 << cur->log, cur->log, n, tw.d_itw, tw.ds, cols(inner[kx], 0),
-                             A + inner[kx].o_tree, d_tr, enc && circle, circle ? seeds_group : 0);
+                             A + inner[kx].o_tree, d_tr, enc && circle, circle ? seeds_group : 0, blk);
             cur = &inner[kx];
             circle = false;
             kx++;
@@ -754,7 +830,7 @@ static int prove_begin_impl(Ctx* ctx, const uint8_t* data, size_t data_stride, s
         ttrees[n_tail - 1] = nullptr;
         uint32_t* d_gnext = reinterpret_cast<uint32_t*>(A + J.o_gnext);
         k::fri_tail(LN, cols(*cur, 0), (size_t)1 << cur->log, cur->log, circle, n, tw.d_itw, tw.ds, last_log, last, n_tail, tvals, ttrees,
-                    d_tr, d_gnext, enc && circle);
+                    d_tr, d_gnext, enc && circle, blk);
         // grind (src/proof.rs:58), keyed by the digest now sitting in the device transcript: first chunk + transcript download
         J.grind_base = 0;
         // first range: 16x the expected search (a miss has probability e^-16; workgroups without work leave at once)
@@ -973,7 +1049,36 @@ int prove_finish_batch(Ctx* ctx, uint8_t* out_commitments, std::vector<ProofData
             }
         } first_full;
         const uint8_t* first_tree_alt = J.enc ? J.enc->tree() : nullptr;
-        if (J.enc && first.log >= J.first_skip_log) {
+        // a block of handles: the same per row of the list, the complete copy built once per DISTINCT blob that needs one (a handle may be
+        // listed more than once) and freed when the call leaves, by whichever path
+        std::vector<DevBuf> block_full(J.block.size());
+        std::vector<const uint8_t*> block_tree(J.block.size(), nullptr);
+        for (size_t r = 0; r < J.block.size(); r++) {
+            const Encoded* e = J.block[r];
+            block_tree[r] = e->tree();
+            if (first.log < e->skip_log) continue;
+            size_t seen = r;
+            for (size_t q = 0; q < r && seen == r; q++)
+                if (J.block[q]->d == e->d) seen = q;
+            if (seen != r) {
+                block_tree[r] = block_tree[seen];
+                continue;
+            }
+            const int arc = block_full[r].alloc(ctx, k::merkle_layer_offset(n, 0) + 32, "poison(complete first-layer tree)");
+            if (arc != FRIEDA_OK) {
+                (void)hipStreamSynchronize(s);  // (the copies built so far are being written)
+                return arc == FRIEDA_ERR_NOMEM ? ctx->fail(FRIEDA_ERR_NOMEM, "no device memory for the complete first-layer tree of the host decommitment") : arc;
+            }
+            const uint32_t* c0 = e->eval();
+            k::merkle_tree4(ctx->launch(), c0, c0 + N, c0 + 2 * N, c0 + 3 * N, n, static_cast<uint8_t*>(block_full[r].p));
+            block_tree[r] = static_cast<const uint8_t*>(block_full[r].p);
+        }
+        // (from here on every exit waits for the stream before the copies go: fail_synced)
+        auto fail_synced = [&](int rc_) {
+            if (!J.block.empty()) (void)hipStreamSynchronize(s);
+            return rc_;
+        };
+        if (J.block.empty() && J.enc && first.log >= J.first_skip_log) {
             if (hipMalloc((void**)&first_full.d, k::merkle_layer_offset(n, 0) + 32) != hipSuccess) {
                 (void)hipGetLastError();
                 return ctx->fail(FRIEDA_ERR_NOMEM, "no device memory for the complete first-layer tree of the host decommitment");
@@ -1034,7 +1139,7 @@ int prove_finish_batch(Ctx* ctx, uint8_t* out_commitments, std::vector<ProofData
             }
         }
         ctx->phase_ms[2] = ms_since(J.t_start);  // queries drawn, openings planned
-        if (g.word_idx.size() > J.max_words || g.hash_idx.size() > J.max_hashes) return ctx->fail(FRIEDA_ERR_INVARIANT, "internal: gather plan overflow");
+        if (g.word_idx.size() > J.max_words || g.hash_idx.size() > J.max_hashes) return fail_synced(ctx->fail(FRIEDA_ERR_INVARIANT, "internal: gather plan overflow"));
         // one upload (word indices then hash indices, staged in pinned memory), one launch, one download
         const size_t nw = g.word_idx.size(), nh = g.hash_idx.size();
         const size_t wbytes = 4 * nw, out_bytes = wbytes + 32 * nh;
@@ -1045,17 +1150,31 @@ int prove_finish_batch(Ctx* ctx, uint8_t* out_commitments, std::vector<ProofData
         // the index and output regions of the arena are laid out back to back (words region, then hashes region), so the
         // hash part may start right behind the words actually used
         k::Launch L1 = ctx->launch();  // the gather works on absolute indices: a single-blob launch
+        // a block of handles: the tagged indices of row r's jobs (consecutive in both lists) are relative to THAT handle — one launch per row
+        // over the row's slices of the lists; the untagged ones go through the arena base as ever
+        auto gather_all = [&](const uint64_t* widx, uint32_t* wout, const uint64_t* hidx_, uint8_t* hout) {
+            if (J.block.empty()) {
+                k::gather(L1, reinterpret_cast<const uint32_t*>(A), widx, nw, wout, hidx_, nh, hout, J.enc ? J.enc->eval() : nullptr, first_tree_alt);
+                return;
+            }
+            for (size_t r = 0; r < J.block.size(); r++) {
+                const size_t j0 = r * J.n_seeds, j1 = j0 + J.n_seeds;
+                const size_t w0 = w_begin[j0], w1 = j1 < count ? w_begin[j1] : nw, h0 = h_begin[j0], h1 = j1 < count ? h_begin[j1] : nh;
+                k::gather(L1, reinterpret_cast<const uint32_t*>(A), widx + w0, w1 - w0, wout + w0, hidx_ + h0, h1 - h0, hout + 32 * h0, J.block[r]->eval(),
+                          block_tree[r]);
+            }
+        };
         if (out_bytes <= ((size_t)1 << 20) && !ctx->tuning.gather_copy) {
             // small openings (the usual case): the kernel reads its index lists from, and writes its results to, the pinned
             // staging block directly over PCIe — one launch instead of copy + launch + copy (each copy costs 10-20 us of setup)
-            k::gather(L1, reinterpret_cast<const uint32_t*>(A), hidx, nw, reinterpret_cast<uint32_t*>(hp), hidx + nw, nh, hp + wbytes,
-                      J.enc ? J.enc->eval() : nullptr, first_tree_alt);
+            gather_all(hidx, reinterpret_cast<uint32_t*>(hp), hidx + nw, hp + wbytes);
         } else {
-            FR_HIP(ctx, hipMemcpyAsync(A + J.o_widx, hidx, 8 * (nw + nh), hipMemcpyHostToDevice, s));
-            k::gather(L1, reinterpret_cast<const uint32_t*>(A), reinterpret_cast<const uint64_t*>(A + J.o_widx), nw,
-                      reinterpret_cast<uint32_t*>(A + J.o_wout), reinterpret_cast<const uint64_t*>(A + J.o_widx) + nw, nh, A + J.o_wout + wbytes,
-                      J.enc ? J.enc->eval() : nullptr, first_tree_alt);
-            FR_HIP(ctx, hipMemcpyAsync(hp, A + J.o_wout, out_bytes, hipMemcpyDeviceToHost, s));
+            if (const hipError_t ce = hipMemcpyAsync(A + J.o_widx, hidx, 8 * (nw + nh), hipMemcpyHostToDevice, s); ce != hipSuccess)
+                return fail_synced(ctx->hip_fail(ce, "hipMemcpyAsync(gather lists)"));
+            gather_all(reinterpret_cast<const uint64_t*>(A + J.o_widx), reinterpret_cast<uint32_t*>(A + J.o_wout),
+                       reinterpret_cast<const uint64_t*>(A + J.o_widx) + nw, A + J.o_wout + wbytes);
+            if (const hipError_t ce = hipMemcpyAsync(hp, A + J.o_wout, out_bytes, hipMemcpyDeviceToHost, s); ce != hipSuccess)
+                return fail_synced(ctx->hip_fail(ce, "hipMemcpyAsync(gathered openings)"));
         }
         FR_HIP(ctx, hipStreamSynchronize(s));
         FR_HIP(ctx, hipGetLastError());
@@ -1339,6 +1458,18 @@ size_t seeds_workspace_bytes(size_t len, frieda_pcs_config cfg, uint32_t n_seeds
     plan.take(8 * mh);
     plan.take(4 * mw);
     plan.take(32 * mh);
+    return plan.off;
+}
+
+// ... and for a prove_seeds_blobs job: the same plan at n_blobs * n_seeds jobs, then the block table (rows, a row number per job, the
+// first job of every seed group at its largest count).  One blob is prove_seeds, table and all
+size_t seeds_blobs_workspace_bytes(size_t len, frieda_pcs_config cfg, uint32_t n_blobs, uint32_t n_seeds) {
+    if (n_blobs == 0 || n_seeds == 0 || (uint64_t)n_blobs * n_seeds > 65535) return 0;
+    const size_t jobs = seeds_workspace_bytes(len, cfg, n_blobs * n_seeds);  // (a multiple of 256)
+    if (n_blobs == 1 || jobs == 0) return jobs;
+    ArenaPlan plan;
+    plan.off = jobs;
+    plan.take(BlockTablePlan(n_blobs, n_seeds, 1).bytes);
     return plan.off;
 }
 

@@ -108,6 +108,12 @@ struct TreeArgs {
                               // decommit.hip re-hashes from the layer's values instead (2.7 % of a 2^24 proof, profiles/r05_skip_levels.txt)
     size_t bstride;           // batch: bytes between consecutive blobs' workspaces (blob = blockIdx.y); tr is an array
     int shared_src;           // FOLD, prove_seeds: `cols` is the one encoded blob every blob (= seed) of the launch folds — no batch stride
+    // FOLD with shared_src, prove_seeds_blobs (blk_table non-null): job y folds the evaluation of row blk_job[y] of the block's table;
+    // blk_group (the seed-looped kernel): the first job of workgroup row y, blk_seeds: seeds per blob
+    const SeedsBlobRow* blk_table;
+    const uint32_t* blk_job;
+    const uint32_t* blk_group;
+    uint32_t blk_seeds;
 };
 
 // the arguments of the blob this workgroup works on
@@ -119,6 +125,13 @@ __device__ __forceinline__ void tree_args_of_blob(TreeArgs& a) {
     a.layers = a.layers + off;
     a.last_out = a.last_out + off;
     a.tr = a.tr + blockIdx.y;
+}
+// the circle fold of a block of encoded blobs: the source columns of job y's blob (y is uniform: scalar loads); the other modes never see a table
+template <int MODE>
+__device__ __forceinline__ void tree_source_of_job(TreeArgs& a) {
+    if constexpr (MODE == 2 /* T_FOLD_CIRCLE */) {
+        if (a.blk_table) a.cols = a.blk_table[a.blk_job[blockIdx.y]].eval;
+    }
 }
 
 namespace {
@@ -141,6 +154,7 @@ __global__ __launch_bounds__(T5_THREADS) void tree5_kernel(TreeArgs a) {
     __shared__ __attribute__((aligned(16))) uint32_t RA[8 * (UNITS + 4)];
     __shared__ __attribute__((aligned(16))) uint32_t RB[8 * (UNITS / 2 + 4)];
     tree_args_of_blob(a);
+    tree_source_of_job<MODE>(a);
     const uint32_t t = threadIdx.x;
     const size_t total_a = (size_t)1 << a.level_a;
     const size_t wg_base = (size_t)blockIdx.x * UNITS;
@@ -212,6 +226,7 @@ __global__ __launch_bounds__(T5_THREADS) void tree5r_kernel(TreeArgs a) {
     __shared__ __attribute__((aligned(16))) uint32_t RC[8 * (256 + 4)];
     __shared__ __attribute__((aligned(16))) uint32_t RD[8 * (128 + 4)];
     tree_args_of_blob(a);
+    tree_source_of_job<MODE>(a);
     uint32_t t_tie = threadIdx.x;
     FR_CLOCK_BEGIN(t_tie)
     const uint32_t t = t_tie;
@@ -348,8 +363,15 @@ __global__ __launch_bounds__(T5_THREADS) void tree5rs_fold_circle_kernel(TreeArg
     const uint32_t t = threadIdx.x;
     const size_t wg_base = (size_t)blockIdx.x * 1024;  // the launcher guarantees 2^level_a >= 1024
     const size_t g0 = wg_base + 4 * t;
-    const uint32_t seed0 = blockIdx.y * group;
-    const uint32_t seed1 = seed0 + group < n_seeds ? seed0 + group : n_seeds;
+    // one blob: n_seeds jobs; a block: the jobs of this group's blob end at (row + 1) * blk_seeds (all uniform: scalar loads)
+    uint32_t seed0 = blockIdx.y * group, job_end = n_seeds;
+    if (a.blk_table) {
+        seed0 = a.blk_group[blockIdx.y];
+        const uint32_t row = a.blk_job[seed0];
+        job_end = (row + 1) * a.blk_seeds;
+        a.cols = a.blk_table[row].eval;
+    }
+    const uint32_t seed1 = seed0 + group < job_end ? seed0 + group : job_end;
     if (TP) tree_prologue_priority();
     uint32_t f0[4][4], e[4][4];  // [pair][coordinate]
     {
@@ -715,6 +737,7 @@ __global__ __launch_bounds__(256) void tree9_kernel(TreeArgs a) {
     __shared__ __attribute__((aligned(16))) uint32_t QQ[2 * QBUF_WORDS];
     latency_kernel_priority();
     tree_args_of_blob(a);
+    tree_source_of_job<MODE>(a);
     const uint32_t t = threadIdx.x, q = t & 3, quad = t >> 2;
     QuadCtx x;
     quad_ctx_init(x, quad, q);
@@ -952,6 +975,9 @@ struct TopArgs {
     // tr_init + b * tr_init_pitch bytes) — the device transcript is initialised from it here instead of by a copy in the stream
     const DevTranscript* tr_init;
     size_t tr_init_pitch;
+    // prove_seeds_blobs, l_in = 0: job y's root is that of row blk_job[y] of the block's table (`in` is not read)
+    const SeedsBlobRow* blk_table;
+    const uint32_t* blk_job;
 };
 
 __global__ __launch_bounds__(WG1_THREADS) void top_kernel(TopArgs a) {
@@ -962,6 +988,7 @@ __global__ __launch_bounds__(WG1_THREADS) void top_kernel(TopArgs a) {
     {
         const size_t off = (size_t)blockIdx.y * a.bstride;
         a.in += off;
+        if (a.blk_table) a.in = a.blk_table[a.blk_job[blockIdx.y]].root;  // (uniform: scalar loads)
         if (a.layers) a.layers += off;
         if (a.root_out) a.root_out += off;
         if (a.tr) a.tr += blockIdx.y;
@@ -1045,6 +1072,9 @@ struct TailArgs {
     size_t bstride;   // batch: bytes between blobs' workspaces (blob = blockIdx.y); tr is an array
     uint32_t* gnext;  // non-null: the grind's per-blob window counters, zeroed here for the grind launch that follows
     int shared_src;   // prove_seeds: `src` is the encoded blob every blob (= seed) of the launch starts from — no batch stride
+    // prove_seeds_blobs (with shared_src): job y starts from the evaluation of row blk_job[y] of the block's table
+    const SeedsBlobRow* blk_table;
+    const uint32_t* blk_job;
 };
 
 __global__ __launch_bounds__(WG1_THREADS) void tail_kernel(TailArgs a) {
@@ -1067,6 +1097,7 @@ __global__ __launch_bounds__(WG1_THREADS) void tail_kernel(TailArgs a) {
     if (t == 4 && a.gnext) a.gnext[blockIdx.y * GRIND_NEXT_STRIDE] = 0;
 
     const uint32_t* src = reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(a.src) + (a.shared_src ? 0 : boff));
+    if (a.blk_table) src = a.blk_table[a.blk_job[blockIdx.y]].eval;  // (uniform: scalar loads)
     size_t src_stride = a.src_stride;
     uint32_t src_log = a.src_log;
     bool circle = a.src_is_circle != 0;
@@ -1426,7 +1457,7 @@ void finish_tree(const Launch& L, const TreeArgs& a, uint32_t m, uint32_t cur, c
         cur = cur - l2;
         cur_ptr = layers ? layers + merkle_layer_offset(m, cur) : b.last_out;
     }
-    TopArgs tp;
+    TopArgs tp{};  // (no block table: the root of a tree built here is the tree's own)
     tp.in = cur_ptr;
     tp.l_in = cur;
     tp.layers = layers;
@@ -1466,7 +1497,8 @@ void build_tree(const Launch& L, int mode, TreeArgs a, uint32_t m, uint8_t* laye
     // level kept, leaf hashes unwritten, 16-byte accesses; any other shape takes route A's kernel, which gives the same words
     if (seeds_group && mode == T_FOLD_CIRCLE && a.shared_src && a.store_all && a.skip_a &&
         tree_kernel_for(*L.tune, a.level_a, L.batch, tree_args_aligned16(a), true) == T_WIDE) {
-        const uint32_t groups = (L.batch + seeds_group - 1) / seeds_group;
+        // (a block: every blob's seeds are cut into groups of their own; a.blk_group has one entry per workgroup row)
+        const uint32_t groups = a.blk_table ? (L.batch / a.blk_seeds) * ((a.blk_seeds + seeds_group - 1) / seeds_group) : (L.batch + seeds_group - 1) / seeds_group;
         const dim3 grid((unsigned)(((size_t)1 << a.level_a) / T5_UNITS), groups);
         lv = T5_LEVELS;
         Scope scope(L, "tree5s_fold_circle", (32.0 * groups / L.batch + 48.0) * (double)((size_t)1 << a.level_a) + node_levels_bytes(a.level_a - 1, lv - 1));
@@ -1610,7 +1642,7 @@ void tree_first_layer(const Launch& L, const uint32_t* cols, size_t stride, uint
 
 void fold_and_tree(const Launch& L, bool circle, const uint32_t* src, size_t src_stride, uint32_t src_log, uint32_t n,
                    const uint32_t* d_itw, DomainScalars ds, uint32_t* dst_vals, uint8_t* layers, DevTranscript* tr, bool shared_src,
-                   uint32_t seeds_group) {
+                   uint32_t seeds_group, const SeedsBlock* blk) {
     const uint32_t m = src_log - 1;
     TreeArgs a{};
     a.cols = src;
@@ -1623,11 +1655,23 @@ void fold_and_tree(const Launch& L, bool circle, const uint32_t* src, size_t src
     a.tr = tr;
     a.skip_a = m >= 1;
     a.shared_src = shared_src ? 1 : 0;
+    if (blk && blk->table && shared_src && circle) {
+        a.blk_table = blk->table;
+        a.blk_job = blk->job_row;
+        a.blk_group = blk->group_first;
+        a.blk_seeds = blk->n_seeds;
+        if (!blk->group_first) seeds_group = 0;
+    }
     build_tree(L, circle ? T_FOLD_CIRCLE : T_FOLD_LINE, a, m, layers, nullptr, nullptr, tr, nullptr, 0, seeds_group);
 }
 
-void channel_after_shared_root(const Launch& L, const uint8_t* d_root, DevTranscript* tr, const DevTranscript* tr_init, size_t tr_init_pitch) {
+void channel_after_shared_root(const Launch& L, const uint8_t* d_root, DevTranscript* tr, const DevTranscript* tr_init, size_t tr_init_pitch,
+                               const SeedsBlock* blk) {
     TopArgs tp{};
+    if (blk && blk->table) {
+        tp.blk_table = blk->table;
+        tp.blk_job = blk->job_row;
+    }
     tp.in = d_root;  // l_in = 0: the 8 words at `in` are the root; bstride 0: the same root for every blob of the launch
     tp.tr = tr;
     tp.tr_init = tr_init;
@@ -1638,8 +1682,12 @@ void channel_after_shared_root(const Launch& L, const uint8_t* d_root, DevTransc
 
 void fri_tail(const Launch& L, const uint32_t* src, size_t src_stride, uint32_t src_log, bool src_is_circle, uint32_t n,
               const uint32_t* d_itw, DomainScalars ds, uint32_t last_log, uint32_t last, uint32_t n_layers, uint32_t* const* vals,
-              uint8_t* const* trees, DevTranscript* tr, uint32_t* d_gnext, bool shared_src) {
+              uint8_t* const* trees, DevTranscript* tr, uint32_t* d_gnext, bool shared_src, const SeedsBlock* blk) {
     TailArgs a{};
+    if (blk && blk->table && shared_src) {
+        a.blk_table = blk->table;
+        a.blk_job = blk->job_row;
+    }
     a.gnext = d_gnext;
     a.shared_src = shared_src ? 1 : 0;
     a.src = src;

@@ -206,6 +206,20 @@ class Context {
         for (frieda_proof* p : ps) out.emplace_back(p);
         return out;
     }
+    // A block under many seeds in ONE call (frieda_prove_seeds_blobs): every handle of `encs` (one shape) under every seed of the one
+    // list; proof b * seeds.size() + s == prove_seeds(*encs[b], {seeds[s]}, cfg)[0] byte for byte.  frieda_seeds_blobs_workspace_bytes sizes
+    // a call; the split form is frieda_prove_seeds_blobs_begin / frieda_prove_seeds_blobs_finish.
+    std::vector<Proof> prove_seeds_blobs(const std::vector<const Encoded*>& encs, const std::vector<uint64_t>& seeds, const PcsConfig& cfg) {
+        std::vector<const frieda_encoded*> hs;
+        hs.reserve(encs.size());
+        for (const Encoded* e : encs) hs.push_back(e ? e->handle() : nullptr);
+        std::vector<frieda_proof*> ps(encs.size() * seeds.size(), nullptr);
+        check(frieda_prove_seeds_blobs(h_, hs.data(), (uint32_t)encs.size(), seeds.data(), (uint32_t)seeds.size(), cfg.c(), ps.data()), h_);
+        std::vector<Proof> out;
+        out.reserve(ps.size());
+        for (frieda_proof* p : ps) out.emplace_back(p);
+        return out;
+    }
     // The reconstructor's half of the README's sampling flow (/root/reference/README.md:56-69): any >= 2^log_coef + 2 distinct
     // (position, value) pairs of the bit-reversed codeword — e.g. pooled from api::verify_samples of proofs with different seeds —
     // give the blob's `len` bytes back (frieda_reconstruct_points_device: no linear system, every pair checked against the result;

@@ -574,6 +574,33 @@ int frieda_rebuild_encoded_blobs_from_stripe_bundles(frieda_ctx* ctx, const uint
                                                      const uint64_t* witness_first, uint8_t* out_bytes, uint8_t* out_status,
                                                      size_t* n_stripes_used, frieda_encoded** out_encs);
 
+/* ---- a block under many seeds: n_blobs handles x n_seeds seeds in one call ---------------------------------------------------
+ * A sampling client verifies one ordinary proof per commitment before it trusts a cell, so a provider of a block of n_blobs blobs
+ * with n_seeds clients owes n_blobs * n_seeds proofs.  frieda_prove_seeds_blobs produces them in ONE launch chain with one wait
+ * instead of a loop of n_blobs frieda_prove_seeds calls.
+ * Result: out_proofs has n_blobs * n_seeds entries, blob-major; out_proofs[b * n_seeds + s] serialises to exactly the bytes of
+ * frieda_prove_seeds(encs[b], &seeds[s], 1, ...), i.e. of frieda_commit_and_generate_proof of blob b under seeds[s].  The one seed
+ * list is shared by all blobs: a client's seed asks for the whole block.  Entries are released with frieda_proof_free.
+ * Arguments: all pointers non-null; 1 <= n_blobs, 1 <= n_seeds, n_blobs * n_seeds <= 65535 (the batch count limit); every handle of
+ * the list has the same len and log_blowup, cfg.log_blowup_factor equals it, and every handle belongs to the device of ctx; a breach
+ * returns FRIEDA_ERR_ARG.  Every other rule of frieda_prove_seeds_begin applies as there.
+ * Handles: from one frieda_encode_batch, from lone frieda_encode calls, from a rebuild, or any mix; encoded under different tree-skip
+ * thresholds; the same handle more than once.  The call only reads them: another context may open cells of them or prove from them
+ * meanwhile.
+ * Channel: more than one job needs the transcript kernels (last layer <= 2^11 points, host-channel policy off), else FRIEDA_ERR_ARG,
+ * as frieda_prove_seeds for two seeds; n_blobs == n_seeds == 1 works under both policies (it IS frieda_prove_seeds).
+ * _begin enqueues without synchronising, _finish waits once; one job per context.  The two finishes frieda_prove_seeds_finish and
+ * frieda_prove_seeds_blobs_finish are one function: each completes whichever proving job is in flight and writes one proof per job.
+ * Memory: the call is NOT cut into passes.  frieda_seeds_blobs_workspace_bytes(len, cfg, n_blobs, n_seeds) is what the call asks of
+ * the context, the handles excluded; 0 for a refused shape; at n_blobs == 1 it equals frieda_seeds_workspace_bytes.  A call too
+ * large for the GPU returns FRIEDA_ERR_NOMEM and leaves ctx usable: cut the seed list or the block. */
+int frieda_prove_seeds_blobs_begin(frieda_ctx* ctx, const frieda_encoded* const* encs, uint32_t n_blobs, const uint64_t* seeds, uint32_t n_seeds,
+                                   frieda_pcs_config cfg);
+int frieda_prove_seeds_blobs_finish(frieda_ctx* ctx, frieda_proof** out_proofs);
+int frieda_prove_seeds_blobs(frieda_ctx* ctx, const frieda_encoded* const* encs, uint32_t n_blobs, const uint64_t* seeds, uint32_t n_seeds,
+                             frieda_pcs_config cfg, frieda_proof** out_proofs);
+size_t frieda_seeds_blobs_workspace_bytes(size_t len, frieda_pcs_config cfg, uint32_t n_blobs, uint32_t n_seeds);
+
 /* ---- batch policy: how a stream of equal-length blobs is cut into batched calls ("bytes in flight") -------------------------
  * Every kernel of a batched call covers all its blobs, so the launch / Fiat-Shamir latency chain is paid once per call: small
  * blobs want many per call, large blobs few (the device workspace grows with the count).  The library's rule — what
