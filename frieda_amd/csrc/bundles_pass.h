@@ -1,4 +1,5 @@
-// bundles_pass.h — the arithmetic of one pass of the bundle verifier (bundles_host.cpp: verify_bundles_passes): which bundles a pass takes,
+// bundles_pass.h — the arithmetic of one pass of the bundle verifier (bundles_host.cpp: verify_bundles_passes, the one driver of cell
+// bundles and stripe bundles, which calls everything here with the factor max(n_blobs, 1)): which bundles a pass takes,
 // where the pieces of its staged image lie, and what it asks of the pinned block and the arena.  No HIP, no context: the cuts run on
 // the CPU against the formulas written out again (tests/cpp/test_bundles_pass.cpp).  cells_pass.h is the same for separate cells.
 //
@@ -13,7 +14,7 @@
 // status word per bundle as it comes back, then the gather table the host builds from the statuses (two words per cell of an accepted
 // bundle).  In the arena behind the image: roots (32 bytes a cell), bad (a word a cell), the status words, the gather table.
 //
-// Stripe bundles (stripe_bundles_host.cpp) run the same arithmetic with a factor n_blobs (default 1: the single-blob form, unchanged):
+// Stripe bundles (stripe_bundles_host.cpp's exports) go through the same driver with a factor n_blobs (default 1: the single-blob form):
 // a bundle's k stripes are cell j of EVERY blob, so it stages its table row and its indices once and its values and its witness n_blobs
 // times, 12 + cells * 4 + n_blobs * (cells * vb + 32 * hashes) bytes with `hashes` counted per blob; roots and bad are per (stripe, blob)
 // cell, there is a status word per (bundle, blob), and the gather table has a row per stripe.

@@ -10,6 +10,11 @@
 // blob_index[i]; the single-blob calls are the same code without blob numbers, and launch the single-blob kernels.  The driver
 // (verify_cells_passes) stages a call through the pinned block and the arena in passes cut by cells_pass.h; with a pool, what a pass
 // accepted — cells, or whole stripes (cell j of every blob) — is gathered into it before the next pass overwrites the staged values.
+//
+// The rebuilds from a pool — the two here and the two from bundles (bundles_host.cpp, stripe_bundles_host.cpp) — share their shape rule
+// (rebuild_shape) and their tail (rebuild_from_pool: the dispatch to rebuild_blob, rebuild_blobs_from_stripes or rebuild_encoded_from_pool,
+// how many entries the reconstruction needs, and the "too few" message); an entry point keeps its argument checks, its verify call and
+// its noun.
 #include <string.h>
 
 #include <algorithm>
@@ -244,6 +249,35 @@ int rebuild_blobs_from_stripes(frieda_ctx* ctx, const CellPool& pool, const uint
     return rebuilt_accept(&ctx->c, roots.data(), commitments, n_blobs, nullptr, bytes, out_bytes);
 }
 
+int rebuild_shape(frieda_ctx* ctx, const char* fn, uint32_t log_blowup_factor, size_t len, uint32_t* L, uint32_t* n) {
+    if (log_blowup_factor > FRIEDA_MAX_LOG_DOMAIN || len > ((size_t)1 << 40)) return ctx->c.fail(FRIEDA_ERR_ARG, std::string(fn) + "shape out of range");
+    *L = codec_shape(len).log_size, *n = *L + log_blowup_factor;
+    if (*L < 1 || *n < 2 || *n + 1 > FRIEDA_MAX_LOG_DOMAIN) return ctx->c.fail(FRIEDA_ERR_ARG, std::string(fn) + "shape out of range");
+    return FRIEDA_OK;
+}
+
+int rebuild_from_pool(frieda_ctx* ctx, const CellPool& pool, const uint8_t* commitments, uint32_t n_blobs, uint32_t log_blowup_factor, size_t len,
+                      uint32_t log_cell, const char* noun, uint8_t* out_bytes, frieda_encoded** out_encs, size_t* n_used) {
+    const uint32_t L = codec_shape(len).log_size, n = L + log_blowup_factor;
+    // what the point reconstruction needs: one cell more than the coefficients fill, or two points more
+    const size_t need = log_cell ? (((size_t)1 << L) >> log_cell) + 1 : ((size_t)1 << L) + 2;
+    uint32_t nd = 0;
+    auto counted = [&](int rc) {  // *n_used on an error too; the reconstruction's "too few" in the caller's words
+        *n_used = nd;
+        if (rc != FRIEDA_ERR_ARG || nd >= need) return rc;
+        return ctx->c.fail(FRIEDA_ERR_ARG, std::to_string(nd) + " " + noun + ", " + std::to_string(need) + " needed");
+    };
+    if (pool.n == 0) return counted(FRIEDA_ERR_ARG);
+    // the single-blob forms name no blob in their mismatch; the block forms name the blob (rebuilt_accept)
+    const char* const mismatch = n_blobs ? nullptr : "the rebuilt blob does not commit to the commitment (wrong len?)";
+    if (out_encs)
+        return counted(rebuild_encoded_from_pool(ctx, pool, commitments, std::max(n_blobs, 1u), log_blowup_factor, len, log_cell, mismatch, out_bytes, &nd, out_encs));
+    if (n_blobs) return counted(rebuild_blobs_from_stripes(ctx, pool, commitments, n_blobs, log_blowup_factor, len, log_cell, out_bytes, &nd));
+    return rebuild_blob(ctx, len, log_blowup_factor, commitments, mismatch, out_bytes, [&](uint8_t* d_out) {
+        return counted(reconstruct_pooled(ctx, pool.d_val(), pool.d_idx(), (uint32_t)pool.n, 1, log_cell, L, n, len, d_out, 0, &nd));
+    });
+}
+
 const char* cells_args_error(uint32_t log_domain, uint32_t log_cell, const uint32_t* cell_index, uint32_t n_cells) {
     if (log_domain > FRIEDA_MAX_LOG_DOMAIN) return "log_domain out of range";
     if (log_cell > log_domain || log_cell > FRIEDA_MAX_LOG_OPEN_CELL) return "log_cell out of range";
@@ -306,34 +340,16 @@ int reconstruct_from_opened_cells(frieda_ctx* ctx, const uint8_t commitment[32],
     if (!ctx || !commitment || !n_cells_used || (len && !out_bytes && !out_enc) || (n_cells && (!cell_index || !values || !out_status))) return FRIEDA_ERR_ARG;
     *n_cells_used = 0;
     const char* const fn = out_enc ? "rebuild_encoded_from_opened_cells: " : "reconstruct_from_opened_cells: ";
-    if (log_blowup_factor > FRIEDA_MAX_LOG_DOMAIN || len > ((size_t)1 << 40)) return ctx->c.fail(FRIEDA_ERR_ARG, std::string(fn) + "shape out of range");
-    const uint32_t L = codec_shape(len).log_size, n = L + log_blowup_factor;
-    if (L < 1 || n < 2 || n + 1 > FRIEDA_MAX_LOG_DOMAIN) return ctx->c.fail(FRIEDA_ERR_ARG, std::string(fn) + "shape out of range");
+    uint32_t L, n;
+    if (const int rc = rebuild_shape(ctx, fn, log_blowup_factor, len, &L, &n)) return rc;
     if (const char* bad = cells_args_error(n, log_cell, cell_index, n_cells)) return ctx->c.fail(FRIEDA_ERR_ARG, std::string(fn) + bad);
     if (n_cells && !paths && log_cell != n) return FRIEDA_ERR_ARG;
     FR_NO_JOB(&ctx->c);
     FR_GUARD_BEGIN
-    const size_t need = log_cell ? (((size_t)1 << L) >> log_cell) + 1 : ((size_t)1 << L) + 2;
-    uint32_t nd = 0;
-    auto too_few = [&]() {
-        return ctx->c.fail(FRIEDA_ERR_ARG, std::to_string(nd) + " distinct accepted cells, " + std::to_string(need) + " needed");
-    };
-    if (n_cells == 0) return too_few();
     CellPool pool;
-    int rc = verify_cells_passes(&ctx->c, commitment, 0, n, log_cell, nullptr, cell_index, n_cells, values, paths, out_status, &pool);
-    if (rc != FRIEDA_OK) return rc;
-    if (pool.n == 0) return too_few();
-    const char* const mismatch = "the rebuilt blob does not commit to the commitment (wrong len?)";
-    if (out_enc) {
-        rc = rebuild_encoded_from_pool(ctx, pool, commitment, 1, log_blowup_factor, len, log_cell, mismatch, out_bytes, &nd, out_enc);
-        *n_cells_used = nd;
-        return rc == FRIEDA_ERR_ARG && nd < need ? too_few() : rc;
-    }
-    return rebuild_blob(ctx, len, log_blowup_factor, commitment, mismatch, out_bytes, [&](uint8_t* d_out) {
-        rc = reconstruct_pooled(ctx, pool.d_val(), pool.d_idx(), (uint32_t)pool.n, 1, log_cell, L, n, len, d_out, 0, &nd);
-        *n_cells_used = nd;
-        return rc == FRIEDA_ERR_ARG && nd < need ? too_few() : rc;
-    });
+    if (n_cells)
+        if (const int rc = verify_cells_passes(&ctx->c, commitment, 0, n, log_cell, nullptr, cell_index, n_cells, values, paths, out_status, &pool)) return rc;
+    return rebuild_from_pool(ctx, pool, commitment, 0, log_blowup_factor, len, log_cell, "distinct accepted cells", out_bytes, out_enc, n_cells_used);
     FR_GUARD_END(ctx)
 }
 }  // namespace
@@ -413,29 +429,21 @@ int reconstruct_blobs_from_opened_stripes(frieda_ctx* ctx, const uint8_t* commit
     *n_stripes_used = 0;
     const char* const fn = out_encs ? "rebuild_encoded_blobs_from_opened_stripes: " : "reconstruct_blobs_from_opened_stripes: ";
     if (n_blobs == 0 || n_blobs > STRIPES_MAX_BLOBS) return ctx->c.fail(FRIEDA_ERR_ARG, std::string(fn) + "n_blobs out of range (1 .. 256)");
-    if (log_blowup_factor > FRIEDA_MAX_LOG_DOMAIN || len > ((size_t)1 << 40)) return ctx->c.fail(FRIEDA_ERR_ARG, std::string(fn) + "shape out of range");
-    const uint32_t L = codec_shape(len).log_size, n = L + log_blowup_factor;
-    if (L < 1 || n < 2 || n + 1 > FRIEDA_MAX_LOG_DOMAIN) return ctx->c.fail(FRIEDA_ERR_ARG, std::string(fn) + "shape out of range");
+    uint32_t L, n;
+    if (const int rc = rebuild_shape(ctx, fn, log_blowup_factor, len, &L, &n)) return rc;
     if (const char* bad = cells_args_error(n, log_cell, stripe_index, n_stripes)) return ctx->c.fail(FRIEDA_ERR_ARG, std::string(fn) + bad);
     if (n_stripes && !paths && log_cell != n) return FRIEDA_ERR_ARG;
     // the staged values are the point reconstruction's sample buffer: at most 2^32 words (its positions are 32-bit)
     if ((uint64_t)n_stripes * n_blobs > (0x100000000ull >> (log_cell + 2))) return ctx->c.fail(FRIEDA_ERR_ARG, std::string(fn) + "more than 2^32 value words");
     FR_NO_JOB(&ctx->c);
     FR_GUARD_BEGIN
-    const size_t need = log_cell ? (((size_t)1 << L) >> log_cell) + 1 : ((size_t)1 << L) + 2;
-    uint32_t nd = 0;
-    auto too_few = [&]() {
-        return ctx->c.fail(FRIEDA_ERR_ARG, std::to_string(nd) + " distinct fully accepted stripes, " + std::to_string(need) + " needed");
-    };
-    if (n_stripes == 0) return too_few();
     CellPool pool;
-    int rc = verify_cells_passes(&ctx->c, commitments, n_blobs, n, log_cell, nullptr, stripe_index, n_stripes * n_blobs, values, paths, out_status, &pool);
-    if (rc != FRIEDA_OK) return rc;
-    if (pool.n == 0) return too_few();
-    rc = out_encs ? rebuild_encoded_from_pool(ctx, pool, commitments, n_blobs, log_blowup_factor, len, log_cell, nullptr, out_bytes, &nd, out_encs)
-                  : rebuild_blobs_from_stripes(ctx, pool, commitments, n_blobs, log_blowup_factor, len, log_cell, out_bytes, &nd);
-    *n_stripes_used = nd;
-    return rc == FRIEDA_ERR_ARG && nd < need ? too_few() : rc;
+    if (n_stripes)
+        if (const int rc = verify_cells_passes(&ctx->c, commitments, n_blobs, n, log_cell, nullptr, stripe_index, n_stripes * n_blobs, values, paths, out_status,
+                                               &pool))
+            return rc;
+    return rebuild_from_pool(ctx, pool, commitments, n_blobs, log_blowup_factor, len, log_cell, "distinct fully accepted stripes", out_bytes, out_encs,
+                             n_stripes_used);
     FR_GUARD_END(ctx)
 }
 }  // namespace

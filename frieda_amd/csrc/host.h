@@ -363,6 +363,39 @@ int rebuild_blobs_from_stripes(frieda_ctx* ctx, const CellPool& pool, const uint
 // never uploaded.  *n_distinct also on an error; out_encs[n_blobs] is written on FRIEDA_OK only.
 int rebuild_encoded_from_pool(frieda_ctx* ctx, const CellPool& pool, const uint8_t* commitments, uint32_t n_blobs, uint32_t log_blowup, size_t len,
                               uint32_t log_cell, const char* mismatch, uint8_t* out_bytes, uint32_t* n_distinct, frieda_encoded** out_encs);
+// The shape rule of the four cell / bundle rebuilds (cells_host.cpp): *L = log2 of the coefficients `len` bytes take, *n = *L + log_blowup_factor,
+// or FRIEDA_ERR_ARG "<fn>shape out of range".
+int rebuild_shape(frieda_ctx* ctx, const char* fn, uint32_t log_blowup_factor, size_t len, uint32_t* L, uint32_t* n);
+// Their one tail, once the verify passes have filled `pool` (a pool nothing was verified into is empty).  n_blobs 0: one blob from its cells
+// (rebuild_blob over reconstruct_pooled, the single-blob mismatch text); n_blobs >= 1: a block from its stripes (rebuild_blobs_from_stripes,
+// the mismatch names the blob).  out_encs non-null: rebuild_encoded_from_pool instead, for either.  *n_used: the distinct entries, on an
+// error too.  Fewer than the reconstruction needs: FRIEDA_ERR_ARG "<d> distinct <noun>, <need> needed".
+int rebuild_from_pool(frieda_ctx* ctx, const CellPool& pool, const uint8_t* commitments, uint32_t n_blobs, uint32_t log_blowup_factor, size_t len,
+                      uint32_t log_cell, const char* noun, uint8_t* out_bytes, frieda_encoded** out_encs, size_t* n_used);
+
+// ---- bundles (bundles_host.cpp serves stripe_bundles_host.cpp too; bundles.hip, stripe_bundles.hip) ----
+// The one pass driver of both bundle forms.  MALFORMED on the host, once per bundle, the rest from the kernels, staged in passes
+// (bundles_pass.h, factor max(n_blobs, 1)).  Uses the arena and the pinned block (callers: FR_NO_JOB).
+//   n_blobs 0        cell bundles: one commitment, in the kernel arguments; bundle_walk; out_status[n_bundles]
+//   n_blobs >= 1     stripe bundles: commitments[n_blobs][32], uploaded once; stripe_bundle_walk (for one blob too); out_status[n_bundles][n_blobs],
+//                    MALFORMED in the bundle's whole row; a pass stages at most 2^30 bytes
+// pool (optional): receives, in the caller's order, the cells (stripes) of the bundles whose status bytes are all ACCEPTED.
+int verify_bundles_passes(Ctx* ctx, const uint8_t* commitments, uint32_t n_blobs, uint32_t log_domain, uint32_t log_cell, const uint32_t* cell_index,
+                          const uint32_t* bundle_first, uint32_t n_bundles, const uint32_t* values, const uint8_t* witness, const uint64_t* witness_first,
+                          uint8_t* out_status, CellPool* pool);
+// The openers' shared pieces.  open_bundles_front: what frieda_open_cell_bundles (n_blobs 1) and frieda_open_stripe_bundles check before they
+// launch — null arguments, shape, structure, the first malformed bundle by name —, wfirst[n_bundles + 1] (hashes per blob), the size query
+// (out_witness null) and cap_hashes against n_blobs * wfirst.  *go: the caller goes on to launch; else the call ends with the returned code.
+int open_bundles_front(frieda_ctx* ctx, const char* fn, uint32_t log_domain, uint32_t n_blobs, uint32_t log_cell, const uint32_t* index,
+                       const uint32_t* bundle_first, uint32_t n_bundles, const uint32_t* out_values, const uint8_t* out_witness, size_t cap_hashes,
+                       uint64_t* out_witness_first, std::vector<uint64_t>& wfirst, bool* go);
+// the bundle table and the per-(bundle, level) witness offsets of an opener's upload, rows[n_bundles] and base[n_bundles][depth].  n_blobs 0:
+// offsets from wfirst[b], no first_hash; n_blobs >= 1: the offsets of blob 0's piece, from n_blobs * wfirst[b], and first_hash = wfirst[b]
+void open_bundles_fill(k::BundleRow* rows, uint64_t* base, uint32_t depth, uint32_t n_blobs, const uint32_t* index, const uint32_t* bundle_first,
+                       uint32_t n_bundles, const uint64_t* wfirst);
+// an opener's end: the launch error, one download of (values | witness) from the arena at a_out to the pinned block behind the upload, one
+// synchronisation, the two copies out
+int open_bundles_finish(Ctx* ctx, size_t in_bytes, size_t a_out, size_t vb, size_t wb, uint32_t* out_values, uint8_t* out_witness);
 
 // transcript pieces shared by prover and verifier (transcript.cpp)
 void channel_mix_felts(Channel& ch, const std::vector<QM31>& felts);

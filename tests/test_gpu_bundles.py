@@ -11,6 +11,7 @@ import pytest
 
 import bundles_util as B
 import cells_util as U
+import stripe_bundles_util as S
 import workspace_rows as W
 from bundles_util import ACCEPTED, MALFORMED, REJECTED
 from cells_util import ERR_ARG, HOST_CASES, POISON
@@ -185,6 +186,26 @@ def flipped_call(n, c, sizes, flips, seed):
     return call.replace(bundles=[idx[first[b]:first[b + 1]] for b in range(len(sizes))], values=values, witness=witness)
 
 
+def staged_bytes(call):
+    """what each bundle of a call stages in a pass (bundles_pass.h): its table row, its indices, its values and its witness"""
+    vb = 16 << call.c
+    return [12 + len(i) * (4 + vb) + 32 * int(w1 - w0) for i, w0, w1 in zip(call.bundles, call.wfirst[:-1], call.wfirst[1:])]
+
+
+def pass_cuts(staged, pass_bytes):
+    """the passes of bundles that stage `staged` bytes each, by the rule of bundles_pass.h written out again: bundles in order while their
+    sum stays within pass_bytes, one bundle always admitted"""
+    cuts, first = [], 0
+    while first < len(staged):
+        end, total = first + 1, staged[first]
+        while end < len(staged) and total + staged[end] <= pass_bytes:
+            total += staged[end]
+            end += 1
+        cuts.append(list(range(first, end)))
+        first = end
+    return cuts
+
+
 @pytest.mark.parametrize("pass_bytes", [0, 30000])
 def test_verify_many_on_random_bit_flips_in_four_passes(gpu_ctx, pass_bytes):
     """120 bundles of 1 .. 9 cells at log_domain 12, log_cell 3, 200 flipped bits; 30000 bytes per pass: at least four passes"""
@@ -202,6 +223,31 @@ def test_verify_many_on_random_bit_flips_in_four_passes(gpu_ctx, pass_bytes):
     finally:
         gpu_ctx._L.frieda_ctx_test_set_verify_pass_bytes(gpu_ctx._h, 0)
     assert dev == host == want.tolist()
+
+
+def test_pass_cuts_beside_a_malformed_and_behind_a_rejected_bundle(gpu_ctx):
+    """8 bundles of 3 .. 7 cells at log_domain 12, log_cell 3 with 4 flipped bits, twice the largest bundle per pass: at least three passes,
+    a MALFORMED bundle (never staged) between the bundles of two passes, a REJECTED bundle as the last of a pass.  The same arrays through
+    the single-blob driver, the stripe driver with one blob and the host verifier: identical status bytes."""
+    n, c = 12, 3
+    call = flipped_call(n, c, [5, 6, 7, 4, 5, 6, 7, 3], 4, seed=38)
+    want = B.independent_status(call)
+    assert {ACCEPTED, REJECTED, MALFORMED} == set(want.tolist())
+    good = [b for b, s in enumerate(want) if s != MALFORMED]
+    staged = [staged_bytes(call)[b] for b in good]
+    pass_bytes = 2 * max(staged)
+    passes = [[good[g] for g in p] for p in pass_cuts(staged, pass_bytes)]
+    assert len(passes) >= 3
+    assert any(a[-1] + 1 < z[0] for a, z in zip(passes[:-1], passes[1:])), "no malformed bundle between two passes"
+    assert any(want[p[-1]] == REJECTED for p in passes), "no rejected bundle at the end of a pass"
+    assert gpu_ctx._L.frieda_ctx_test_set_verify_pass_bytes(gpu_ctx._h, pass_bytes) == 0
+    try:
+        host, dev = both(gpu_ctx, call)
+        rc, block = S.raw_verify(S.assemble([call]), gpu_ctx)
+    finally:
+        gpu_ctx._L.frieda_ctx_test_set_verify_pass_bytes(gpu_ctx._h, 0)
+    assert rc == 0, gpu_ctx._L.frieda_last_error(gpu_ctx._h)
+    assert dev == host == block[:, 0].tolist() == want.tolist()
 
 
 def test_same_bytes_on_a_poisoned_workspace_and_a_callers_stream():
@@ -259,9 +305,11 @@ def raw_reconstruct(ctx, call, blowup, length):
     return rc, (body.tobytes() if rc == 0 else None), status[:nb], used.value
 
 
+@pytest.mark.parametrize("multi_pass", [False, True])
 @pytest.mark.parametrize("c,sizes,extra", [(3, (5, 6, 7), 6), (0, (64, 65, 1), 70)])
-def test_reconstruct_from_cell_bundles(gpu_ctx, c, sizes, extra):
-    """the 1024-byte blob at blowup 4 (2^7 coefficients, 2^11 domain): 17 distinct cells at log_cell 3, 130 points at log_cell 0"""
+def test_reconstruct_from_cell_bundles(gpu_ctx, c, sizes, extra, multi_pass):
+    """the 1024-byte blob at blowup 4 (2^7 coefficients, 2^11 domain): 17 distinct cells at log_cell 3, 130 points at log_cell 0;
+    multi_pass: one byte less per pass than the first two bundles stage, so no pass holds both"""
     data, ev, layers, n, L = U.case(11, 4)
     assert (L, n) == (7, 11) and len(data) == 1024
     need = (1 << (L - c)) + 1 if c else (1 << L) + 2
@@ -273,32 +321,37 @@ def test_reconstruct_from_cell_bundles(gpu_ctx, c, sizes, extra):
     # the fourth bundle: new cells and two that the first bundle already holds
     fourth = np.sort(np.concatenate([perm[cuts[-1]:cuts[-1] + extra], bundles[0][:2]]))
     call = B.build_call(ev, layers, c, bundles)
-    rc, out, st, used = raw_reconstruct(gpu_ctx, call, 4, len(data))
-    assert rc == 0 and out == data and used == sum(sizes) and (st == ACCEPTED).all(), gpu_ctx._L.frieda_last_error(gpu_ctx._h)
+    pass_bytes = sum(staged_bytes(call)[:2]) - 1 if multi_pass else 0
+    assert gpu_ctx._L.frieda_ctx_test_set_verify_pass_bytes(gpu_ctx._h, pass_bytes) == 0
+    try:
+        rc, out, st, used = raw_reconstruct(gpu_ctx, call, 4, len(data))
+        assert rc == 0 and out == data and used == sum(sizes) and (st == ACCEPTED).all(), gpu_ctx._L.frieda_last_error(gpu_ctx._h)
 
-    # one bundle corrupted: too few, the statuses name it, the output keeps its poison
-    t = 1
-    v = call.values.copy()
-    v[int(call.first[t]), 1, 0] ^= 2
-    bad = call.replace(values=v)
-    rc, out, st, used = raw_reconstruct(gpu_ctx, bad, 4, len(data))
-    assert rc == ERR_ARG and st.tolist() == [ACCEPTED, REJECTED, ACCEPTED] and used == sum(sizes) - sizes[t]
-    assert sum(sizes) - sizes[t] < need
+        # one bundle corrupted: too few, the statuses name it, the output keeps its poison
+        t = 1
+        v = call.values.copy()
+        v[int(call.first[t]), 1, 0] ^= 2
+        bad = call.replace(values=v)
+        rc, out, st, used = raw_reconstruct(gpu_ctx, bad, 4, len(data))
+        assert rc == ERR_ARG and st.tolist() == [ACCEPTED, REJECTED, ACCEPTED] and used == sum(sizes) - sizes[t]
+        assert sum(sizes) - sizes[t] < need
 
-    # a fourth good bundle: enough again; its overlap with the first bundle is counted once, the rejected bundle is not used
-    four = B.build_call(ev, layers, c, bundles + [fourth])
-    v4 = four.values.copy()
-    v4[int(four.first[t]), 1, 0] ^= 2
-    rc, out, st, used = raw_reconstruct(gpu_ctx, four.replace(values=v4), 4, len(data))
-    distinct = len(set(np.concatenate([bundles[0], bundles[2], fourth]).tolist()))
-    assert distinct == sum(sizes) - sizes[t] + extra >= need
-    assert rc == 0 and out == data and used == distinct and st.tolist() == [ACCEPTED, REJECTED, ACCEPTED, ACCEPTED]
+        # a fourth good bundle: enough again; its overlap with the first bundle is counted once, the rejected bundle is not used
+        four = B.build_call(ev, layers, c, bundles + [fourth])
+        v4 = four.values.copy()
+        v4[int(four.first[t]), 1, 0] ^= 2
+        rc, out, st, used = raw_reconstruct(gpu_ctx, four.replace(values=v4), 4, len(data))
+        distinct = len(set(np.concatenate([bundles[0], bundles[2], fourth]).tolist()))
+        assert distinct == sum(sizes) - sizes[t] + extra >= need
+        assert rc == 0 and out == data and used == distinct and st.tolist() == [ACCEPTED, REJECTED, ACCEPTED, ACCEPTED]
 
-    # a wrong len (same polynomial size): every bundle verifies, the commitment check fails
-    assert oracle_commit(data[:-1], 4) != call.commitment
-    rc, out, st, used = raw_reconstruct(gpu_ctx, call, 4, len(data) - 1)
-    assert rc == ERR_ARG and (st == ACCEPTED).all() and used == sum(sizes)
-    assert b"commit" in gpu_ctx._L.frieda_last_error(gpu_ctx._h)
+        # a wrong len (same polynomial size): every bundle verifies, the commitment check fails
+        assert oracle_commit(data[:-1], 4) != call.commitment
+        rc, out, st, used = raw_reconstruct(gpu_ctx, call, 4, len(data) - 1)
+        assert rc == ERR_ARG and (st == ACCEPTED).all() and used == sum(sizes)
+        assert b"commit" in gpu_ctx._L.frieda_last_error(gpu_ctx._h)
+    finally:
+        gpu_ctx._L.frieda_ctx_test_set_verify_pass_bytes(gpu_ctx._h, 0)
 
 
 def test_python_surface(gpu_ctx):
