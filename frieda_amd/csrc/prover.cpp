@@ -62,20 +62,106 @@ struct Shape {
     size_t N;
 };
 
-int make_shape(Ctx* ctx, size_t len, uint32_t B, Shape& sh) {
+// why a shape or a configuration is refused (FRIEDA_OK: it is not): an entry point makes ctx->fail(code, text) of it, a sizing function 0
+struct Refusal {
+    int code = FRIEDA_OK;
+    const char* text = "";
+};
+
+Refusal check_shape(size_t len, uint32_t B, Shape& sh) {
     // B arrives unchecked from the caller (a ctypes c_uint32 turns -1 into 0xFFFFFFFF): bound it before any sum is formed
-    if (B > FRIEDA_MAX_LOG_DOMAIN) return ctx->fail(FRIEDA_ERR_ARG, "log_blowup_factor larger than FRIEDA_MAX_LOG_DOMAIN");
-    if (len > ((size_t)1 << 40)) return ctx->fail(FRIEDA_ERR_ARG, "blob larger than 2^40 bytes");
+    if (B > FRIEDA_MAX_LOG_DOMAIN) return {FRIEDA_ERR_ARG, "log_blowup_factor larger than FRIEDA_MAX_LOG_DOMAIN"};
+    if (len > ((size_t)1 << 40)) return {FRIEDA_ERR_ARG, "blob larger than 2^40 bytes"};
     sh.cs = codec_shape(len);
     sh.L = sh.cs.log_size;
     sh.B = B;
     // Coset::half_odds(L + B - 1) panics for L + B == 0 (u32 underflow)
-    if ((uint64_t)sh.L + B < 1) return ctx->fail(FRIEDA_ERR_INVARIANT, "log_size + log_blowup_factor must be >= 1");
-    if ((uint64_t)sh.L + B > FRIEDA_MAX_LOG_DOMAIN) return ctx->fail(FRIEDA_ERR_ARG, "domain larger than FRIEDA_MAX_LOG_DOMAIN");
+    if ((uint64_t)sh.L + B < 1) return {FRIEDA_ERR_INVARIANT, "log_size + log_blowup_factor must be >= 1"};
+    if ((uint64_t)sh.L + B > FRIEDA_MAX_LOG_DOMAIN) return {FRIEDA_ERR_ARG, "domain larger than FRIEDA_MAX_LOG_DOMAIN"};
     sh.n = sh.L + B;
     sh.N = (size_t)1 << sh.n;
+    return {};
+}
+
+int make_shape(Ctx* ctx, size_t len, uint32_t B, Shape& sh) {
+    const Refusal r = check_shape(len, B, sh);
+    return r.code ? ctx->fail(r.code, r.text) : FRIEDA_OK;
+}
+
+// what every prove form checks of the shape and the configuration, in the order the entry points have always reported it
+Refusal check_prove(size_t len, const frieda_pcs_config& cfg, Shape& sh) {
+    const uint32_t last = cfg.log_last_layer_degree_bound;
+    // both arrive unchecked: bound them (the blowup: check_shape's first check) before `last + B` and the shifts that use it are formed
+    if (last > 10) return {FRIEDA_ERR_ARG, "log_last_layer_degree_bound > 10"};
+    const Refusal r = check_shape(len, cfg.log_blowup_factor, sh);
+    if (r.code) return r;
+    // FriProver::commit_last_layer asserts evaluation.len() == last_layer_domain_size: needs L - 1 >= last;
+    // the line domain half_odds(n - 1) needs n >= 2
+    if (sh.n < 2 || sh.L < 1 + last) return {FRIEDA_ERR_INVARIANT, "polynomial too small for the FRI configuration"};
+    if (cfg.n_queries == 0 || cfg.n_queries > 4096) return {FRIEDA_ERR_ARG, "n_queries out of range"};
+    return {};
+}
+
+// `count` blobs of `len` bytes each as a caller hands them over: blob b at data + b * stride, or (host blobs only) at host_ptrs[b]
+struct BlobsIn {
+    const uint8_t* data;
+    size_t stride, len;
+    bool on_device;
+    const uint8_t* const* host_ptrs;
+};
+
+// host blobs -> dst + b * dst_stride on the context's stream.  A pointer table travels as one copy per blob, a strided batch as one 2-D
+// copy, a lone blob as a plain copy — or, lone_as_row (the batch entry points of commit and encode), as a 2-D copy of one row
+int upload_blobs(Ctx* ctx, const BlobsIn& in, uint32_t count, uint8_t* dst, size_t dst_stride, bool lone_as_row = false) {
+    if (!in.len) return FRIEDA_OK;
+    hipStream_t s = ctx->stream;
+    if (in.host_ptrs) {
+        for (uint32_t b = 0; b < count; b++) FR_HIP(ctx, hipMemcpyAsync(dst + (size_t)b * dst_stride, in.host_ptrs[b], in.len, hipMemcpyHostToDevice, s));
+    } else if (count == 1 && !lone_as_row) {
+        FR_HIP(ctx, hipMemcpyAsync(dst, in.data, in.len, hipMemcpyHostToDevice, s));
+    } else {
+        FR_HIP(ctx, hipMemcpy2DAsync(dst, dst_stride, in.data, count > 1 ? in.stride : in.len, in.len, count, hipMemcpyHostToDevice, s));
+    }
     return FRIEDA_OK;
 }
+
+// where the encode step leaves what: null for what the caller does not keep
+struct EncodeDest {
+    uint32_t* coef;  // the general route's unpacked coefficients (workspace; the fused small route keeps none)
+    uint32_t* eval;  // 4 columns of eval_len words: written by the general route in every case, by the small route only together with
+    size_t eval_len;  // the tree (a commit keeps neither)
+    uint8_t *tree, *scratch, *root;  // first-layer tree, leaves-first (prove, encode); root scratch (commit); device root (commit, encode)
+    DevTranscript* tr;  // prove: the device transcripts, and the pinned initial ones at tr_init_pitch
+    const DevTranscript* tr_init;
+    size_t tr_init_pitch;
+};
+
+// the fused small-domain launch or the general encode with its last pass hashing the leaves (kernels.h), for every blob of the launch
+void encode_first_tree(const k::Launch& LN, const Shape& sh, const TwiddleSet& tw, const k::BlobSource& blob, const EncodeDest& d) {
+    if (k::small_domain_shape(*LN.tune, sh.L, sh.n)) {
+        uint32_t* eval = d.tree ? d.eval : nullptr;
+        k::small_encode_and_first_tree(LN, blob.bytes, blob.len, blob.bstride, sh.L, sh.n, tw.d_tw, tw.ds, eval, eval ? d.eval_len : 0, d.tree, d.scratch, d.root, d.tr, d.tr_init, d.tr_init_pitch);
+    } else {  // (the encode unpacks: in its first pass where that pass takes the blob, else by the unpack30 launch — kernels.h BlobSource)
+        k::encode_and_first_tree(LN, d.coef, (size_t)1 << sh.L, sh.L, sh.n, tw.d_tw, tw.ds, d.eval, d.eval_len, d.tree, d.scratch, d.root, d.tr, d.tr_init, d.tr_init_pitch, &blob);
+    }
+}
+
+// the workspace of a commit, per blob (commit_device writes its root where the caller says and asks for the part in front of o_root only)
+struct CommitLayout {
+    size_t o_data, o_coef, o_eval, o_scr, o_root, bstride, N;
+    CommitLayout(const Shape& sh, size_t data_len) : N(sh.N) {  // data_len 0: the blob is on the device already, or in the pinned input block
+        ArenaPlan plan;
+        o_data = plan.take(data_len);
+        o_coef = plan.take(sizeof(uint32_t) * sh.cs.n_padded);
+        o_eval = plan.take(sizeof(uint32_t) * 4 * sh.N);
+        o_scr = plan.take(k::merkle_root_scratch_bytes(sh.n));
+        o_root = plan.take(32);
+        bstride = plan.off;
+    }
+    EncodeDest dest(uint8_t* A, uint8_t* d_root) const {
+        return {reinterpret_cast<uint32_t*>(A + o_coef), reinterpret_cast<uint32_t*>(A + o_eval), N, nullptr, A + o_scr, d_root, nullptr, nullptr, 0};
+    }
+};
 
 // LineEvaluation::interpolate for the last FRI layer (stwo core/poly/line.rs), host side: <= 2^14 points.
 // `v`: evaluations in bit-reversed order on LineDomain(c); returns coefficients in LinePoly's internal order.
@@ -123,34 +209,17 @@ int commit_device(Ctx* ctx, const uint8_t* d_data, size_t len, uint32_t log_blow
     int rc = make_shape(ctx, len, log_blowup, sh);
     if (rc) return rc;
     FR_HIP(ctx, hipSetDevice(ctx->device));
-
-    ArenaPlan plan;
-    size_t o_data = plan.take(data_in_arena ? len : 0);
-    size_t o_coef = plan.take(sizeof(uint32_t) * sh.cs.n_padded);
-    size_t o_eval = plan.take(sizeof(uint32_t) * 4 * sh.N);
-    size_t o_scr = plan.take(k::merkle_root_scratch_bytes(sh.n));
-    (void)o_data;
+    const CommitLayout y(sh, data_in_arena ? len : 0);
     if (!data_in_arena) {
-        rc = ctx->ensure_arena(plan.off);
+        rc = ctx->ensure_arena(y.o_root);
         if (rc) return rc;
-    } else if (plan.off > ctx->arena_bytes) {
+    } else if (y.o_root > ctx->arena_bytes) {
         return ctx->fail(FRIEDA_ERR_ARG, "internal: arena not sized by caller");
     }
     TwiddleSet tw;
     rc = ctx->get_twiddles(sh.n, tw);
     if (rc) return rc;
-
-    uint32_t* coef = reinterpret_cast<uint32_t*>(ctx->arena + o_coef);
-    uint32_t* eval = reinterpret_cast<uint32_t*>(ctx->arena + o_eval);
-    if (k::small_domain_shape(ctx->tuning, sh.L, sh.n)) {
-        k::small_encode_and_first_tree(ctx->launch(), d_data, len, 0, sh.L, sh.n, tw.d_tw, tw.ds, nullptr, 0, nullptr, ctx->arena + o_scr, d_root,
-                                       nullptr, nullptr, 0);
-    } else {
-        // (the encode unpacks: in its first pass where that pass takes the blob, else by the unpack30 launch — kernels.h BlobSource)
-        const k::BlobSource blob{d_data, len, 0, sh.cs.n_padded};
-        k::encode_and_first_tree(ctx->launch(), coef, (size_t)1 << sh.L, sh.L, sh.n, tw.d_tw, tw.ds, eval, sh.N, nullptr, ctx->arena + o_scr, d_root,
-                                 nullptr, nullptr, 0, &blob);
-    }
+    encode_first_tree(ctx->launch(), sh, tw, k::BlobSource{d_data, len, 0, sh.cs.n_padded}, y.dest(ctx->arena, d_root));
     FR_HIP(ctx, hipGetLastError());
     return FRIEDA_OK;
 }
@@ -161,32 +230,23 @@ int commit_host(Ctx* ctx, const uint8_t* data, size_t len, uint32_t log_blowup, 
     int rc = make_shape(ctx, len, log_blowup, sh);
     if (rc) return rc;
     FR_HIP(ctx, hipSetDevice(ctx->device));
-    // same plan as commit_device(data_in_arena = true), plus 32 bytes for the root
-    ArenaPlan plan;
-    size_t o_data = plan.take(len);
-    plan.take(sizeof(uint32_t) * sh.cs.n_padded);
-    plan.take(sizeof(uint32_t) * 4 * sh.N);
-    plan.take(k::merkle_root_scratch_bytes(sh.n));
-    size_t o_root = plan.take(32);
-    rc = ctx->ensure_arena(plan.off);
+    const CommitLayout y(sh, len);  // commit_device(data_in_arena = true) runs on it
+    rc = ctx->ensure_arena(y.bstride);
+    if (rc == FRIEDA_OK) rc = ensure_pinned(ctx, 4096);
     if (rc) return rc;
-    rc = ensure_pinned(ctx, 4096);
-    if (rc) return rc;
-    if (k::small_domain_shape(ctx->tuning, sh.L, sh.n) && len <= SMALL_HOST_IN_BYTES) {
+    const bool in_place = k::small_domain_shape(ctx->tuning, sh.L, sh.n) && len <= SMALL_HOST_IN_BYTES;
+    if (in_place) {
         // no copy commands at all: the kernels read the blob from page-locked host memory and write the root into it
         rc = ensure_pinned_in(ctx);
         if (rc) return rc;
         if (len) memcpy(ctx->pinned_in, data, len);
         rc = commit_device(ctx, static_cast<const uint8_t*>(ctx->pinned_in), len, log_blowup, static_cast<uint8_t*>(ctx->pinned), true);
-        if (rc) return rc;
-        FR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        memcpy(out_root, ctx->pinned, 32);
-        return FRIEDA_OK;
+    } else {
+        rc = upload_blobs(ctx, BlobsIn{data, 0, len, false, nullptr}, 1, ctx->arena + y.o_data, 0);
+        if (rc == FRIEDA_OK) rc = commit_device(ctx, ctx->arena + y.o_data, len, log_blowup, ctx->arena + y.o_root, true);
     }
-    if (len) FR_HIP(ctx, hipMemcpyAsync(ctx->arena + o_data, data, len, hipMemcpyHostToDevice, ctx->stream));
-    rc = commit_device(ctx, ctx->arena + o_data, len, log_blowup, ctx->arena + o_root, true);
     if (rc) return rc;
-    FR_HIP(ctx, hipMemcpyAsync(ctx->pinned, ctx->arena + o_root, 32, hipMemcpyDeviceToHost, ctx->stream));
+    if (!in_place) FR_HIP(ctx, hipMemcpyAsync(ctx->pinned, ctx->arena + y.o_root, 32, hipMemcpyDeviceToHost, ctx->stream));
     FR_HIP(ctx, hipStreamSynchronize(ctx->stream));
     memcpy(out_root, ctx->pinned, 32);
     return FRIEDA_OK;
@@ -220,46 +280,27 @@ int commit_batch_begin(Ctx* ctx, const uint8_t* data, size_t data_stride, size_t
     int rc = make_shape(ctx, len, log_blowup, sh);
     if (rc) return rc;
     FR_HIP(ctx, hipSetDevice(ctx->device));
-    ArenaPlan plan;
-    const size_t o_data = plan.take(data_on_device ? 0 : len);
-    const size_t o_coef = plan.take(sizeof(uint32_t) * sh.cs.n_padded);
-    const size_t o_eval = plan.take(sizeof(uint32_t) * 4 * sh.N);
-    const size_t o_scr = plan.take(k::merkle_root_scratch_bytes(sh.n));
-    const size_t o_root = plan.take(32);
-    const size_t bstride = plan.off;
-    rc = ctx->ensure_arena(bstride * count);
-    if (rc) return rc;
-    rc = ensure_pinned(ctx, 32 * (size_t)count + 4096);
-    if (rc) return rc;
+    const CommitLayout y(sh, data_on_device ? 0 : len);
+    const size_t bstride = y.bstride;
     TwiddleSet tw;
-    rc = ctx->get_twiddles(sh.n, tw);
+    rc = ctx->ensure_arena(bstride * count);
+    if (rc == FRIEDA_OK) rc = ensure_pinned(ctx, 32 * (size_t)count + 4096);
+    if (rc == FRIEDA_OK) rc = ctx->get_twiddles(sh.n, tw);
     if (rc) return rc;
     hipStream_t s = ctx->stream;
     uint8_t* A = ctx->arena;
     k::Launch LN = ctx->launch();
     LN.batch = count;
     LN.bstride = count > 1 ? bstride : 0;
-    const uint8_t* d_data = data;
-    size_t d_stride = data_stride;
-    if (!data_on_device) {
-        if (len && host_ptrs) {  // separate host blobs of one length (frieda_commit_many)
-            for (uint32_t b = 0; b < count; b++) FR_HIP(ctx, hipMemcpyAsync(A + o_data + (size_t)b * bstride, host_ptrs[b], len, hipMemcpyHostToDevice, s));
-        } else if (len) {
-            FR_HIP(ctx, hipMemcpy2DAsync(A + o_data, bstride, data, count > 1 ? data_stride : len, len, count, hipMemcpyHostToDevice, s));
-        }
-        d_data = A + o_data;
-        d_stride = bstride;
+    k::BlobSource blob{data, len, data_stride, sh.cs.n_padded};
+    if (!data_on_device) {  // (host_ptrs: separate host blobs of one length, frieda_commit_many)
+        rc = upload_blobs(ctx, BlobsIn{data, data_stride, len, false, host_ptrs}, count, A + y.o_data, bstride, /*lone_as_row=*/true);
+        if (rc) return rc;
+        blob.bytes = A + y.o_data;
+        blob.bstride = bstride;
     }
-    uint32_t* coef = reinterpret_cast<uint32_t*>(A + o_coef);
-    uint32_t* eval = reinterpret_cast<uint32_t*>(A + o_eval);
-    if (k::small_domain_shape(ctx->tuning, sh.L, sh.n)) {
-        k::small_encode_and_first_tree(LN, d_data, len, d_stride, sh.L, sh.n, tw.d_tw, tw.ds, nullptr, 0, nullptr, A + o_scr, A + o_root, nullptr,
-                                       nullptr, 0);
-    } else {
-        const k::BlobSource blob{d_data, len, d_stride, sh.cs.n_padded};
-        k::encode_and_first_tree(LN, coef, (size_t)1 << sh.L, sh.L, sh.n, tw.d_tw, tw.ds, eval, sh.N, nullptr, A + o_scr, A + o_root, nullptr, nullptr, 0, &blob);
-    }
-    FR_HIP(ctx, hipMemcpy2DAsync(ctx->pinned, 32, A + o_root, bstride, 32, count, hipMemcpyDeviceToHost, s));
+    encode_first_tree(LN, sh, tw, blob, y.dest(A, A + y.o_root));
+    FR_HIP(ctx, hipMemcpy2DAsync(ctx->pinned, 32, A + y.o_root, bstride, 32, count, hipMemcpyDeviceToHost, s));
     FR_HIP(ctx, hipGetLastError());
     ctx->commit_pending = count;
     return FRIEDA_OK;
@@ -345,34 +386,145 @@ size_t plan_merkle_decommit(const std::vector<uint32_t>& positions, const FriLay
 
 }  // namespace
 
+// Capacity of a job's opening lists.  Words: per layer <= 2 positions per query (+ the evaluations).  Hashes: a batch keeps its
+// long-standing loose bound, 2 * queries * (n + 1) per layer; a prove_seeds job — whose point is memory per seed — the exact one: in a
+// tree of 2^m leaves opened at pairs, every level below the root has at most `queries` visited nodes and each emits at most one sibling,
+// the leaf level none: queries * (m - 1) <= queries * (n - li) for layer li.
+size_t opening_max_words(uint32_t n_queries, uint32_t n_inner) { return (size_t)n_queries * 4 * (1 + (n_inner + 1)); }
+size_t opening_max_hashes(uint32_t n_queries, uint32_t n, uint32_t n_inner, bool seeds) {
+    if (!seeds) return (size_t)n_queries * 2 * (size_t)(n + 1) * (n_inner + 1);
+    size_t h = 0;
+    for (uint32_t li = 0; li <= n_inner; li++) h += (size_t)n_queries * (n - li);
+    return h;
+}
+
+namespace {
+// What the jobs of a prove call are.  PLAIN: `count` blobs.  SEEDS (prove_seeds): `count` seeds of ONE encoded blob, enc.  BLOCK
+// (prove_seeds_blobs): n_blobs * n_seeds jobs, blob-major (job y = block[y / n_seeds] under seed y % n_seeds); enc = block[0] stands for the shape
+struct ProveForm {
+    enum Kind { PLAIN, SEEDS, BLOCK } kind = PLAIN;
+    const Encoded* enc = nullptr;
+    const Encoded* const* block = nullptr;
+    uint32_t n_blobs = 0;
+    uint32_t fold_group = 1;  // BLOCK: FRIEDA_SEEDS_FOLD_GROUP of the call (0: route A), for the table as staged; the sizing functions know no context
+};
+
+// the block table of a prove_seeds_blobs call, as the arena and the pinned staging hold it: rows, one row number per job, and (route B)
+// the first job of every seed group
+struct BlockTablePlan {
+    size_t o_job = 0, o_group = 0, bytes = 0;
+    uint32_t group = 0, groups = 0;  // seeds per group (0: no group part), groups in all
+    BlockTablePlan() = default;
+    BlockTablePlan(uint32_t n_blobs, uint32_t n_seeds, uint32_t group_) : group(group_) {
+        ArenaPlan p;
+        p.take(sizeof(k::SeedsBlobRow) * n_blobs);
+        o_job = p.take(sizeof(uint32_t) * (size_t)n_blobs * n_seeds);
+        groups = group ? n_blobs * ((n_seeds + group - 1) / group) : 0;
+        o_group = p.take(sizeof(uint32_t) * groups);
+        bytes = p.off;
+    }
+};
+
+// Where everything of a prove call lives, in the arena and in the pinned staging block: what the call asks ensure_arena / ensure_pinned
+// for, what the job keeps, and what the sizing functions report (frieda_workspace_bytes and through it the batch policy, frieda_seeds_*).
+struct ProveLayout {
+    uint32_t last = 0, last_log = 0, n_inner = 0;  // the last layer's degree bound and size (logs), the number of inner layers
+    // arena, per job (job b's part is job 0's shifted by b * bstride, a multiple of 256).  SEEDS and BLOCK: blob, coefficients, evaluation
+    // and first tree live in the encoded blob — `first` then holds no arena offsets and a job's part begins at the first inner layer
+    size_t o_data = 0, o_coef = 0;
+    FriLayerDev first{};
+    std::vector<FriLayerDev> inner;
+    size_t o_lastv = 0, o_nonce = 0, bstride = 0;
+    // arena, behind the jobs' parts: transcripts, grind window counters (one cache line per job), the index and output lists of the
+    // host-planner fallback's gather (max_words / max_hashes entries over all jobs) and, BLOCK, the table
+    size_t o_tr = 0, o_gnext = 0, o_widx = 0, o_hidx = 0, o_wout = 0, o_hout = 0, o_blk = 0;
+    size_t max_words = 0, max_hashes = 0, arena_bytes = 0;
+    // pinned block: job b's transcript summary (header + last-layer polynomial) at b * tr_host_pitch, or the last layer itself on the
+    // host-channel path; behind the summaries the device openings (decommit.hip), job b's header, words and hashes at dec_off +
+    // b * dec_stride; the fallback writes its results at 0 and stages its index lists at gather_off instead; the block table as staged
+    // and uploaded sits behind everything else, at pin_blk (nothing writes there until the next call on this context)
+    size_t tr_host_pitch = 0, dec_off = 0, dec_stride = 0, dec_words_off = 0, dec_hashes_off = 0, gather_off = 0, pin_blk = 0, pinned_bytes = 0;
+    uint32_t dec_max_words = 0, dec_max_hashes = 0;  // per job
+    BlockTablePlan table;
+};
+
+// pure: no HIP call, no context.  host_len: the blob's bytes when it is uploaded into the arena, 0 for device data and encoded blobs
+ProveLayout prove_layout(const Shape& sh, const frieda_pcs_config& cfg, uint32_t count, size_t host_len, const ProveForm& form) {
+    ProveLayout y;
+    const uint32_t n = sh.n, last = y.last = cfg.log_last_layer_degree_bound, last_log = y.last_log = last + cfg.log_blowup_factor;
+    const uint32_t n_inner = y.n_inner = (n - 1) - last_log;
+    const bool shared_first = form.kind != ProveForm::PLAIN;
+    ArenaPlan plan;
+    y.first.log = n;
+    if (!shared_first) {
+        y.o_data = plan.take(host_len);
+        y.o_coef = plan.take(sizeof(uint32_t) * sh.cs.n_padded);
+        y.first.o_vals = plan.take(sizeof(uint32_t) * 4 * sh.N);
+        y.first.o_tree = plan.take(k::merkle_layer_offset(n, 0) + 32);
+    }
+    y.inner.resize(n_inner);
+    for (uint32_t kx = 0; kx < n_inner; kx++) {
+        const uint32_t lg = n - 1 - kx;
+        y.inner[kx].log = lg;
+        y.inner[kx].o_vals = plan.take(sizeof(uint32_t) * 4 << lg);
+        y.inner[kx].o_tree = plan.take(k::merkle_layer_offset(lg, 0) + 32);
+    }
+    y.o_lastv = plan.take(sizeof(uint32_t) * 4 << last_log);
+    y.o_nonce = plan.take(8);
+    y.bstride = plan.off;
+    plan.off = y.bstride * count;
+    y.o_tr = plan.take(sizeof(DevTranscript) * count);
+    y.o_gnext = plan.take(sizeof(uint32_t) * k::GRIND_NEXT_STRIDE * count);
+    y.max_words = opening_max_words(cfg.n_queries, n_inner) * count;
+    y.max_hashes = opening_max_hashes(cfg.n_queries, n, n_inner, shared_first) * count;
+    y.o_widx = plan.take(8 * y.max_words);
+    y.o_hidx = plan.take(8 * y.max_hashes);
+    y.o_wout = plan.take(4 * y.max_words);
+    y.o_hout = plan.take(32 * y.max_hashes);
+    if (form.kind == ProveForm::BLOCK) {
+        const uint32_t n_seeds = count / form.n_blobs;
+        y.table = BlockTablePlan(form.n_blobs, n_seeds, form.fold_group);
+        // (the table's group part is planned for the largest group count, group 1, whatever FRIEDA_SEEDS_FOLD_GROUP says: the workspace of a
+        // call is a function of its shape alone)
+        y.o_blk = plan.take(BlockTablePlan(form.n_blobs, n_seeds, 1).bytes);
+    }
+    y.arena_bytes = plan.off;
+    y.tr_host_pitch = (offsetof(DevTranscript, last_poly) + ((size_t)16 << last) + 63) & ~(size_t)63;
+    y.dec_max_words = (uint32_t)(y.max_words / count);
+    y.dec_max_hashes = (uint32_t)(y.max_hashes / count);
+    y.dec_words_off = k::DECOMMIT_HEADER_BYTES;
+    y.dec_hashes_off = y.dec_words_off + ((4 * (size_t)y.dec_max_words + 15) & ~(size_t)15);
+    y.dec_stride = (y.dec_hashes_off + 32 * (size_t)y.dec_max_hashes + 255) & ~(size_t)255;
+    y.dec_off = (y.tr_host_pitch * count + 255) & ~(size_t)255;
+    y.gather_off = (4 * y.max_words + 32 * y.max_hashes + 255) & ~(size_t)255;
+    // the largest of: the summaries, the last layer, the fallback's results and lists (gather_off + 8 bytes per index), the device openings
+    y.pinned_bytes = std::max({y.tr_host_pitch * count, (sizeof(uint32_t) * 4) << last_log, (4 + 8) * y.max_words + (32 + 8) * y.max_hashes + 512, y.dec_off + y.dec_stride * count});
+    y.pin_blk = (y.pinned_bytes + 255) & ~(size_t)255;
+    if (form.kind == ProveForm::BLOCK) y.pinned_bytes = y.pin_blk + y.table.bytes;
+    return y;
+}
+
+size_t prove_arena_bytes(size_t len, const frieda_pcs_config& cfg, uint32_t count, const ProveForm& form) {
+    Shape sh;
+    if (check_prove(len, cfg, sh).code) return 0;
+    return prove_layout(sh, cfg, count, 0, form).arena_bytes;
+}
+}  // namespace
+
 // State of a proof between prove_begin (commit phase enqueued) and prove_finish (decommit + assembly).
 struct ProveJob {
     frieda_pcs_config cfg{};
     Shape sh{};
-    uint32_t n = 0, last = 0, last_log = 0, n_inner = 0;
-    size_t N = 0;
-    FriLayerDev first{};
-    std::vector<FriLayerDev> inner;
-    size_t o_lastv = 0, o_nonce = 0, o_tr = 0, o_gnext = 0, o_widx = 0, o_hidx = 0, o_wout = 0, o_hout = 0;
-    size_t max_words = 0, max_hashes = 0, tr_host_pitch = 0;
-    bool dev_channel = false;
-    // openings on the device (decommit.hip): per-blob output regions in the pinned block behind the transcript summaries
-    bool dev_decommit = false;
-    size_t dec_off = 0, dec_stride = 0, dec_words_off = 0, dec_hashes_off = 0;
-    uint32_t dec_max_words = 0, dec_max_hashes = 0;
-    // a batch of `count` blobs of one shape: blob b's workspace is blob 0's shifted by b * bstride bytes; the transcripts
-    // (o_tr) and the gather regions sit behind the workspaces
-    uint32_t count = 1;
-    size_t bstride = 0;
+    uint32_t count = 1;  // a batch of `count` jobs of one shape
+    ProveLayout lay;
+    bool dev_channel = false, dev_decommit = false;  // dev_decommit: openings on the device (decommit.hip), read from the pinned block by _finish
     // the tree-skip threshold the trees of THIS job were built with (k::tree_skip_threshold at begin): the openings — device kernel
     // and host-planner fallback — must use the same one even if frieda_ctx_set_option moved the knob between _begin and _finish
     uint32_t skip_log = 0;
-    // prove_seeds: the `count` blobs are seeds of ONE encoded blob.  Layer 0 (values, tree) is enc's, at stride 0, with the threshold
-    // ITS tree was built with; `first` then holds no arena offsets and the per-seed workspace starts at the first inner layer
+    // SEEDS: layer 0 (values, tree) is enc's, at stride 0, with the threshold ITS tree was built with.  BLOCK: layer 0 of a job is its
+    // handle's, which the kernels find through the table `blk` points at (in the arena, uploaded by _begin)
     const Encoded* enc = nullptr;
     uint32_t first_skip_log = 0;
-    // prove_seeds_blobs: the jobs are n_seeds seeds of each handle of `block`, blob-major (job y = handle y / n_seeds); enc = block[0] stands
-    // for the shape.  Layer 0 of a job is its handle's: the kernels find it through the table `blk` points at (in the arena, uploaded by _begin)
     std::vector<const Encoded*> block;
     uint32_t n_seeds = 0;
     k::SeedsBlock blk{};
@@ -387,75 +539,32 @@ struct ProveJob {
     std::vector<Blob> blobs;
     uint64_t grind_base = 0, grind_chunk = 0;
     std::chrono::steady_clock::time_point t_start;
+
+    // every launch of the job covers the whole batch
+    k::Launch launch(const Ctx* ctx) const {
+        k::Launch LN = ctx->launch();
+        LN.batch = count;
+        LN.bstride = count > 1 ? lay.bstride : 0;
+        return LN;
+    }
+    // column c of a layer: in the workspace, or (layer 0 of an encoded blob) the handle's, only ever read
+    uint32_t* cols(const Ctx* ctx, const FriLayerDev& l, int c) const {
+        uint32_t* v = (enc && &l == &lay.first) ? const_cast<uint32_t*>(enc->eval()) : reinterpret_cast<uint32_t*>(ctx->arena + l.o_vals);
+        return v + ((size_t)c << l.log);
+    }
 };
 
 void ProveJobDeleter::operator()(ProveJob* j) const { delete j; }
 
-namespace {
-// the per-blob part of a proof's workspace (one plan for the prover and for the batch policy, which divides its budget by plan.off)
-// shared_first (prove_seeds): blob, coefficients, evaluation and first tree live in the encoded blob — the per-seed part begins at the inner layers
-void plan_prove_blob(ArenaPlan& plan, const Shape& sh, uint32_t last_log, size_t host_len, size_t& o_data, size_t& o_coef, FriLayerDev& first,
-                     std::vector<FriLayerDev>& inner, size_t& o_lastv, size_t& o_nonce, bool shared_first = false) {
-    const uint32_t n = sh.n, n_inner = (n - 1) - last_log;
-    if (shared_first) {
-        o_data = o_coef = 0;
-        first = FriLayerDev{0, 0, n};
-    } else {
-        o_data = plan.take(host_len);
-        o_coef = plan.take(sizeof(uint32_t) * sh.cs.n_padded);
-        first = FriLayerDev{plan.take(sizeof(uint32_t) * 4 * sh.N), 0, n};
-        first.o_tree = plan.take(k::merkle_layer_offset(n, 0) + 32);
-    }
-    inner.resize(n_inner);
-    for (uint32_t kx = 0; kx < n_inner; kx++) {
-        uint32_t lg = n - 1 - kx;
-        inner[kx].log = lg;
-        inner[kx].o_vals = plan.take(sizeof(uint32_t) * 4 << lg);
-        inner[kx].o_tree = plan.take(k::merkle_layer_offset(lg, 0) + 32);
-    }
-    o_lastv = plan.take(sizeof(uint32_t) * 4 << last_log);
-    o_nonce = plan.take(8);
-}
-}  // namespace
-
-// Capacity of a job's opening lists.  Words: per layer <= 2 positions per query (+ the evaluations).  Hashes: a batch keeps its
-// long-standing loose bound, 2 * queries * (n + 1) per layer; a prove_seeds job — whose point is memory per seed — the exact one: in a
-// tree of 2^m leaves opened at pairs, every level below the root has at most `queries` visited nodes and each emits at most one sibling,
-// the leaf level none: queries * (m - 1) <= queries * (n - li) for layer li.
-size_t opening_max_words(uint32_t n_queries, uint32_t n_inner) { return (size_t)n_queries * 4 * (1 + (n_inner + 1)); }
-size_t opening_max_hashes(uint32_t n_queries, uint32_t n, uint32_t n_inner, bool seeds) {
-    if (!seeds) return (size_t)n_queries * 2 * (size_t)(n + 1) * (n_inner + 1);
-    size_t h = 0;
-    for (uint32_t li = 0; li <= n_inner; li++) h += (size_t)n_queries * (n - li);
-    return h;
-}
-
 // Device workspace one blob of `len` bytes adds to a batched call (what ensure_arena is asked for, per blob): the figure the batch
 // policy (batch_plan below) divides its budget by.  0: the shape is outside what the prover accepts.
 size_t workspace_bytes_per_blob(size_t len, uint32_t log_blowup, uint32_t log_last_layer, bool prove, bool data_on_device) {
-    if (log_blowup > FRIEDA_MAX_LOG_DOMAIN || len > ((size_t)1 << 40)) return 0;
     Shape sh;
-    sh.cs = codec_shape(len);
-    sh.L = sh.cs.log_size;
-    sh.B = log_blowup;
-    if ((uint64_t)sh.L + log_blowup < 1 || (uint64_t)sh.L + log_blowup > FRIEDA_MAX_LOG_DOMAIN) return 0;
-    sh.n = sh.L + log_blowup;
-    sh.N = (size_t)1 << sh.n;
-    ArenaPlan plan;
-    if (!prove) {  // commit_batch_begin's plan
-        plan.take(data_on_device ? 0 : len);
-        plan.take(sizeof(uint32_t) * sh.cs.n_padded);
-        plan.take(sizeof(uint32_t) * 4 * sh.N);
-        plan.take(k::merkle_root_scratch_bytes(sh.n));
-        plan.take(32);
-        return plan.off;
-    }
-    if (log_last_layer > 10 || sh.n < 2 || sh.L < 1 + log_last_layer || log_last_layer + log_blowup > sh.n - 1) return 0;
-    size_t a, b, c, d;
-    FriLayerDev first;
-    std::vector<FriLayerDev> inner;
-    plan_prove_blob(plan, sh, log_last_layer + log_blowup, data_on_device ? 0 : len, a, b, first, inner, c, d);
-    return plan.off;
+    const size_t host_len = data_on_device ? 0 : len;
+    if (!prove) return check_shape(len, log_blowup, sh).code ? 0 : CommitLayout(sh, host_len).bstride;
+    const frieda_pcs_config cfg{0, log_blowup, log_last_layer, 1};  // (a job's own part does not depend on the queries)
+    if (check_prove(len, cfg, sh).code) return 0;
+    return prove_layout(sh, cfg, 1, host_len, ProveForm{}).bstride;
 }
 
 // ---- batch policy (host.h) ----
@@ -511,45 +620,300 @@ static double ms_since(std::chrono::steady_clock::time_point t0) {
 
 // transcript summaries (header + last-layer polynomial) of all blobs -> pinned memory, blob b at b * tr_host_pitch
 static int download_transcripts(Ctx* ctx, const ProveJob& J) {
-    const size_t bytes = offsetof(DevTranscript, last_poly) + ((size_t)16 << J.last);
-    const uint8_t* d_tr = ctx->arena + J.o_tr;
+    const size_t bytes = offsetof(DevTranscript, last_poly) + ((size_t)16 << J.lay.last);
+    const uint8_t* d_tr = ctx->arena + J.lay.o_tr;
     if (J.count == 1) {
         FR_HIP(ctx, hipMemcpyAsync(ctx->pinned, d_tr, bytes, hipMemcpyDeviceToHost, ctx->stream));
     } else {
-        FR_HIP(ctx, hipMemcpy2DAsync(ctx->pinned, J.tr_host_pitch, d_tr, sizeof(DevTranscript), bytes, J.count, hipMemcpyDeviceToHost, ctx->stream));
+        FR_HIP(ctx, hipMemcpy2DAsync(ctx->pinned, J.lay.tr_host_pitch, d_tr, sizeof(DevTranscript), bytes, J.count, hipMemcpyDeviceToHost, ctx->stream));
     }
     return FRIEDA_OK;
 }
 
 // decommit.hip over all blobs of the job: reads the device transcripts (nonce, channel) and the layers, writes the pinned block
-static void launch_decommit(Ctx* ctx, const ProveJob& J, const k::Launch& LN) {
+static void launch_decommit(Ctx* ctx, const ProveJob& J) {
     uint8_t* A = ctx->arena;
+    const ProveLayout& Y = J.lay;
     k::DecommitArgs a{};
-    a.tr = reinterpret_cast<const DevTranscript*>(A + J.o_tr);
-    a.n = J.n;
-    a.n_layers = 1 + J.n_inner;
+    a.tr = reinterpret_cast<const DevTranscript*>(A + Y.o_tr);
+    a.n = J.sh.n;
+    a.n_layers = 1 + J.lay.n_inner;
     a.n_queries = J.cfg.n_queries;
-    a.bstride = J.count > 1 ? J.bstride : 0;
-    a.out = static_cast<uint8_t*>(ctx->pinned) + J.dec_off;
-    a.out_stride = J.dec_stride;
-    a.words_off = J.dec_words_off;
-    a.hashes_off = J.dec_hashes_off;
-    a.max_words = J.dec_max_words;
-    a.max_hashes = J.dec_max_hashes;
+    a.bstride = J.count > 1 ? Y.bstride : 0;
+    a.out = static_cast<uint8_t*>(ctx->pinned) + Y.dec_off;
+    a.out_stride = Y.dec_stride;
+    a.words_off = Y.dec_words_off;
+    a.hashes_off = Y.dec_hashes_off;
+    a.max_words = Y.dec_max_words;
+    a.max_hashes = Y.dec_max_hashes;
     a.skip_log = J.skip_log;
     a.skip_log0 = J.first_skip_log;
     a.first_shared = J.enc ? 1 : 0;
-    a.vals[0] = J.enc ? J.enc->eval() : reinterpret_cast<const uint32_t*>(A + J.first.o_vals);
-    a.trees[0] = J.enc ? J.enc->tree() : A + J.first.o_tree;
+    a.vals[0] = J.cols(ctx, Y.first, 0);
+    a.trees[0] = J.enc ? J.enc->tree() : A + Y.first.o_tree;
     a.blk_table = J.blk.table;  // (a block of handles: layer 0 and its threshold per job, from the table)
     a.blk_job = J.blk.job_row;
-    for (uint32_t kx = 0; kx < J.n_inner; kx++) {
-        a.vals[1 + kx] = reinterpret_cast<const uint32_t*>(A + J.inner[kx].o_vals);
-        a.trees[1 + kx] = A + J.inner[kx].o_tree;
+    for (uint32_t kx = 0; kx < J.lay.n_inner; kx++) {
+        a.vals[1 + kx] = J.cols(ctx, Y.inner[kx], 0);
+        a.trees[1 + kx] = A + Y.inner[kx].o_tree;
     }
     // a lone large proof has ~4000 hashes to fetch: several workgroups share them (each repeats the cheap table set-up)
-    const uint32_t wgs = J.count >= 8 ? 1u : (J.count >= 2 ? 2u : (J.n >= 16 ? 8u : 2u));
-    k::decommit(LN, a, wgs);
+    const uint32_t wgs = J.count >= 8 ? 1u : (J.count >= 2 ? 2u : (J.sh.n >= 16 ? 8u : 2u));
+    k::decommit(J.launch(ctx), a, wgs);
+}
+
+// ---- prove_begin: the pieces, in the order they run ----
+// BLOCK: the per-blob table, the row of every job and the first job of every seed group: one upload per call, ahead of every launch
+static int upload_block_table(Ctx* ctx, ProveJob& J) {
+    const BlockTablePlan& T = J.lay.table;
+    const uint32_t n_block = (uint32_t)J.block.size(), n_seeds = J.n_seeds;
+    uint8_t* hp = static_cast<uint8_t*>(ctx->pinned) + J.lay.pin_blk;
+    k::SeedsBlobRow* rows = reinterpret_cast<k::SeedsBlobRow*>(hp);
+    uint32_t* job_row = reinterpret_cast<uint32_t*>(hp + T.o_job);
+    uint32_t* group_first = reinterpret_cast<uint32_t*>(hp + T.o_group);
+    const uint32_t gpb = T.group ? (n_seeds + T.group - 1) / T.group : 0;  // groups per blob: a short last one, none across two blobs
+    for (uint32_t r = 0; r < n_block; r++) {
+        const Encoded* e = J.block[r];
+        rows[r] = k::SeedsBlobRow{e->eval(), e->tree(), e->d + e->o_root, e->skip_log, 0};
+        for (uint32_t sd = 0; sd < n_seeds; sd++) job_row[r * n_seeds + sd] = r;
+        for (uint32_t g = 0; g < gpb; g++) group_first[r * gpb + g] = r * n_seeds + g * T.group;
+    }
+    uint8_t* d_blk = ctx->arena + J.lay.o_blk;
+    FR_HIP(ctx, hipMemcpyAsync(d_blk, hp, T.bytes, hipMemcpyHostToDevice, ctx->stream));
+    J.blk = k::SeedsBlock{reinterpret_cast<const k::SeedsBlobRow*>(d_blk), reinterpret_cast<const uint32_t*>(d_blk + T.o_job),
+                          T.group ? reinterpret_cast<const uint32_t*>(d_blk + T.o_group) : nullptr, n_block, n_seeds};
+    return FRIEDA_OK;
+}
+
+// Every job's channel with its seed mixed in; device channel: staged as the initial transcripts.  No copy in the stream: the kernel that finishes
+// the first tree reads these few words from the pinned block itself (next written by the transcript download behind the grind, i.e. after it)
+static void init_transcripts(Ctx* ctx, ProveJob& J, const uint64_t* seeds) {
+    for (uint32_t b = 0; b < J.count; b++) {
+        ProveJob::Blob& bl = J.blobs[b];
+        bl.ch.init();
+        if (seeds) bl.ch.mix_u64(seeds[J.block.empty() ? b : b % J.n_seeds]);  // src/proof.rs:40-42
+        bl.roots.assign(1 + J.lay.n_inner, Hash32{});
+        if (!J.dev_channel) continue;
+        DevTranscript* ht = reinterpret_cast<DevTranscript*>(static_cast<uint8_t*>(ctx->pinned) + b * J.lay.tr_host_pitch);
+        memset(ht, 0, offsetof(DevTranscript, last_poly));
+        ht->ch = bl.ch;
+        ht->nonce = ~0ull;
+        ht->draw_bound = ctx->test_draw_bound;
+    }
+}
+
+// the whole commit phase on the device, transcript included, then the first grind range, the transcript download and the openings: enqueued only
+static int enqueue_device_channel(Ctx* ctx, ProveJob& J, const TwiddleSet& tw, const k::BlobSource& blob) {
+    uint8_t* A = ctx->arena;
+    const ProveLayout& Y = J.lay;
+    const k::Launch LN = J.launch(ctx);
+    const Encoded* enc = J.enc;
+    const uint32_t n = J.sh.n, n_inner = J.lay.n_inner;
+    const k::SeedsBlock* blk = J.block.empty() ? nullptr : &J.blk;
+    DevTranscript* d_tr = reinterpret_cast<DevTranscript*>(A + Y.o_tr);
+    const DevTranscript* tr_init = reinterpret_cast<const DevTranscript*>(ctx->pinned);
+    // the encode's last pass runs fused with FriProver::commit_first_layer's leaf hashing (src/proof.rs:48-52); small domains: unpack +
+    // encode + first tree in one launch, straight from the blob.  (prove_begin_impl's `small` asks for more than small_domain_shape — no
+    // host channel, a last layer the tail takes — and on this branch both hold: the two conditions pick the same kernel here)
+    if (enc)  // the first tree and its root exist: only the transcripts' step behind that root — mix_root, first alpha — per seed
+        k::channel_after_shared_root(LN, enc->d + enc->o_root, d_tr, tr_init, Y.tr_host_pitch, blk);
+    else
+        encode_first_tree(LN, J.sh, tw, blob, {reinterpret_cast<uint32_t*>(A + Y.o_coef), J.cols(ctx, Y.first, 0), J.sh.N, A + Y.first.o_tree, nullptr, nullptr, d_tr, tr_init, Y.tr_host_pitch});
+    // FriProver::commit_inner_layers: layers above 2^11 points, one fused fold + tree each
+    const FriLayerDev* cur = &Y.first;
+    bool circle = true;
+    uint32_t kx = 0;
+    // layers of more than 2^TAIL_RUN_LOG points go through the multi-workgroup kernels (a 2^11 layer is faster there than in
+    // the one-workgroup tail); FRIEDA_TAIL_RUN_LOG is a tuning knob
+    const uint32_t tail_run_log = ctx->tuning.tail_run_log;
+    const uint32_t seeds_group = enc ? ctx->tuning.seeds_fold_group : 0;
+    while (kx < n_inner && Y.inner[kx].log > tail_run_log) {
+        k::fold_and_tree(LN, circle, J.cols(ctx, *cur, 0), (size_t)1 << cur->log, cur->log, n, tw.d_itw, tw.ds, J.cols(ctx, Y.inner[kx], 0),
+                         A + Y.inner[kx].o_tree, d_tr, enc && circle, circle ? seeds_group : 0, blk);
+        cur = &Y.inner[kx];
+        circle = false;
+        kx++;
+    }
+    // everything that is left, the last layer's interpolation and mix_felts included, in one workgroup
+    uint32_t* tvals[16];
+    uint8_t* ttrees[16];
+    const uint32_t n_tail = (n_inner - kx) + 1;
+    if (n_tail > 16) return ctx->fail(FRIEDA_ERR_INVARIANT, "internal: tail too long");
+    for (uint32_t i = 0; i + 1 < n_tail; i++) {
+        tvals[i] = J.cols(ctx, Y.inner[kx + i], 0);
+        ttrees[i] = A + Y.inner[kx + i].o_tree;
+    }
+    tvals[n_tail - 1] = reinterpret_cast<uint32_t*>(A + Y.o_lastv);
+    ttrees[n_tail - 1] = nullptr;
+    uint32_t* d_gnext = reinterpret_cast<uint32_t*>(A + Y.o_gnext);
+    k::fri_tail(LN, J.cols(ctx, *cur, 0), (size_t)1 << cur->log, cur->log, circle, n, tw.d_itw, tw.ds, J.lay.last_log, J.lay.last, n_tail, tvals, ttrees, d_tr,
+                d_gnext, enc && circle, blk);
+    // grind (src/proof.rs:58), keyed by the digest now sitting in the device transcript: first chunk + transcript download
+    J.grind_base = 0;
+    // first range: 16x the expected search (a miss has probability e^-16; workgroups without work leave at once)
+    J.grind_chunk = (uint64_t)1 << std::max<uint32_t>(22, std::min<uint32_t>(J.cfg.pow_bits, 36) + 4);
+    if (ctx->tuning.test_grind_first_log) J.grind_chunk = (uint64_t)1 << ctx->tuning.test_grind_first_log;  // test hook: the retry loop runs
+    k::grind_dev(LN, d_tr, d_gnext, J.cfg.pow_bits, J.grind_base, J.grind_chunk, /*next_zeroed=*/true);
+    int rc = download_transcripts(ctx, J);
+    if (rc) return rc;
+    // mix_u64(nonce), query sampling and every opening of the proof, written in proof order into the pinned block
+    J.dev_decommit = J.cfg.n_queries <= k::DECOMMIT_MAX_QUERIES && 1 + n_inner <= k::DECOMMIT_MAX_LAYERS && n <= k::DECOMMIT_MAX_LOG_DOMAIN &&
+                     !ctx->tuning.host_decommit;
+    if (J.dev_decommit) launch_decommit(ctx, J);
+    FR_HIP(ctx, hipGetLastError());
+    ctx->phase_ms[0] = ms_since(J.t_start);  // commit phase fully enqueued
+    return FRIEDA_OK;
+}
+
+// The commit phase of one blob with the channel on the host between the layers (a last layer above 2^11 points, or the host channel
+// policy), a synchronisation per root.  The coefficients are in the arena (unpack30, prove_begin_impl) unless the first layer is an encoded blob's
+static int run_host_channel(Ctx* ctx, ProveJob& J, const TwiddleSet& tw) {
+    uint8_t* A = ctx->arena;
+    hipStream_t s = ctx->stream;
+    const ProveLayout& Y = J.lay;
+    const k::Launch LN = J.launch(ctx);
+    const uint32_t n = J.sh.n, n_inner = J.lay.n_inner, last = J.lay.last, last_log = J.lay.last_log;
+    ProveJob::Blob& bl = J.blobs[0];
+    Channel& ch = bl.ch;
+    auto cols = [&](const FriLayerDev& lay, int c) { return J.cols(ctx, lay, c); };
+    auto fetch_root = [&](const FriLayerDev& lay, Hash32& root) -> int {
+        FR_HIP(ctx, hipMemcpyAsync(ctx->pinned, A + lay.o_tree + k::merkle_layer_offset(lay.log, 0), 32, hipMemcpyDeviceToHost, s));
+        FR_HIP(ctx, hipStreamSynchronize(s));
+        memcpy(root.data(), ctx->pinned, 32);
+        return FRIEDA_OK;
+    };
+    int rc;
+    // ---- FriProver::commit_first_layer ----
+    if (J.enc) {
+        memcpy(bl.roots[0].data(), J.enc->root, 32);  // (prove_seeds, one seed: the commitment was made by encode_blob)
+    } else {
+        k::circle_evaluate(LN, reinterpret_cast<const uint32_t*>(A + Y.o_coef), (size_t)1 << J.sh.L, 4, J.sh.L, n, tw.d_tw, tw.ds, cols(Y.first, 0), J.sh.N);
+        k::merkle_tree4(LN, cols(Y.first, 0), cols(Y.first, 1), cols(Y.first, 2), cols(Y.first, 3), n, A + Y.first.o_tree);
+        rc = fetch_root(Y.first, bl.roots[0]);
+        if (rc) return rc;
+    }
+    uint32_t rw[8];
+    hash_to_words(bl.roots[0].data(), rw);
+    ch.mix_root(rw);
+
+    // ---- FriProver::commit_inner_layers ----
+    QM31 alpha = ch.draw_felt(ctx->test_draw_bound);
+    bl.alphas.assign(1 + n_inner, std::array<uint32_t, 4>{});
+    bl.alphas[0] = {alpha.a, alpha.b, alpha.c, alpha.d};
+    {
+        // LineEvaluation::new_zero then fold_circle_into_line
+        uint32_t* dst = (n_inner > 0) ? cols(Y.inner[0], 0) : reinterpret_cast<uint32_t*>(A + Y.o_lastv);
+        FR_HIP(ctx, hipMemsetAsync(dst, 0, sizeof(uint32_t) * 4 << (n - 1), s));
+        k::fold_circle_into_line(LN, dst, (size_t)1 << (n - 1), cols(Y.first, 0), J.sh.N, n, tw.d_itw, tw.ds, k::Alpha{{alpha.a, alpha.b, alpha.c, alpha.d}});
+    }
+    for (uint32_t kx = 0; kx < n_inner; kx++) {
+        const FriLayerDev& lay = Y.inner[kx];
+        k::merkle_tree4(LN, cols(lay, 0), cols(lay, 1), cols(lay, 2), cols(lay, 3), lay.log, A + lay.o_tree);
+        rc = fetch_root(lay, bl.roots[kx + 1]);
+        if (rc) return rc;
+        hash_to_words(bl.roots[kx + 1].data(), rw);
+        ch.mix_root(rw);
+        alpha = ch.draw_felt(ctx->test_draw_bound);
+        bl.alphas[kx + 1] = {alpha.a, alpha.b, alpha.c, alpha.d};
+        uint32_t* dst = (kx + 1 < n_inner) ? cols(Y.inner[kx + 1], 0) : reinterpret_cast<uint32_t*>(A + Y.o_lastv);
+        k::fold_line(LN, cols(lay, 0), (size_t)1 << lay.log, lay.log, n, tw.d_itw, tw.ds, k::Alpha{{alpha.a, alpha.b, alpha.c, alpha.d}}, dst,
+                     (size_t)1 << (lay.log - 1));
+    }
+
+    // ---- FriProver::commit_last_layer ----
+    std::vector<QM31>& lastv = bl.lastv;
+    const size_t n_lastdom = (size_t)1 << last_log;
+    FR_HIP(ctx, hipMemcpyAsync(ctx->pinned, A + Y.o_lastv, sizeof(uint32_t) * 4 * n_lastdom, hipMemcpyDeviceToHost, s));
+    FR_HIP(ctx, hipStreamSynchronize(s));
+    lastv.assign(n_lastdom, QM31{0, 0, 0, 0});
+    {
+        const uint32_t* h = reinterpret_cast<const uint32_t*>(ctx->pinned);
+        for (size_t i = 0; i < n_lastdom; i++) lastv[i] = {h[i], h[n_lastdom + i], h[2 * n_lastdom + i], h[3 * n_lastdom + i]};
+    }
+    line_interpolate(lastv, line_coset(n, last_log));
+    bit_reverse_vec(lastv, n_lastdom, last_log);  // into_ordered_coefficients
+    const size_t n_poly = (size_t)1 << last;
+    for (size_t i = n_poly; i < n_lastdom; i++)
+        if (!qm_is_zero(lastv[i])) return ctx->fail(FRIEDA_ERR_INVARIANT, "invalid degree");  // assert! upstream
+    lastv.resize(n_poly);
+    bit_reverse_vec(lastv, n_poly, last);  // LinePoly::from_ordered_coefficients
+    channel_mix_felts(ch, lastv);
+    memcpy(bl.digest_before_grind, ch.digest, 32);
+
+    // ---- grind (src/proof.rs:58-59) ----
+    unsigned long long* d_nonce = reinterpret_cast<unsigned long long*>(A + Y.o_nonce);
+    FR_HIP(ctx, hipMemsetAsync(d_nonce, 0xFF, 8, s));
+    uint64_t base = 0, chunk = (uint64_t)1 << 22;
+    for (;;) {
+        k::grind_scan(LN, ch.digest, J.cfg.pow_bits, base, chunk, d_nonce);
+        FR_HIP(ctx, hipMemcpyAsync(ctx->pinned, d_nonce, 8, hipMemcpyDeviceToHost, s));
+        FR_HIP(ctx, hipStreamSynchronize(s));
+        memcpy(&bl.nonce, ctx->pinned, 8);
+        if (bl.nonce != ~0ull) break;
+        base += chunk;
+        if (chunk < ((uint64_t)1 << 28)) chunk <<= 1;
+    }
+    ctx->phase_ms[0] = ms_since(J.t_start);
+    return FRIEDA_OK;
+}
+
+// `count` jobs of one shape (ProveForm); seeds: null or one per blob (PLAIN), one per job (SEEDS), the n_seeds of the one list (BLOCK)
+static int prove_begin_impl(Ctx* ctx, const BlobsIn& in, uint32_t count, const uint64_t* seeds, frieda_pcs_config cfg, ProveForm form) {
+    const auto t_entry = std::chrono::steady_clock::now();
+    FR_NO_JOB(ctx);  // a proof or a commit batch in flight owns the arena and the pinned block
+    if (count == 0 || count > 65535) return ctx->fail(FRIEDA_ERR_ARG, "batch count out of range");
+    if (!form.enc && count > 1 && in.stride < in.len) return ctx->fail(FRIEDA_ERR_ARG, "batch stride smaller than the blob length");
+    std::unique_ptr<ProveJob, ProveJobDeleter> jp(new ProveJob());
+    ProveJob& J = *jp;
+    const Refusal refused = check_prove(in.len, cfg, J.sh);
+    if (refused.code) return ctx->fail(refused.code, refused.text);
+    if (cfg.pow_bits > 48) return ctx->fail(FRIEDA_ERR_ARG, "pow_bits > 48");
+    FR_HIP(ctx, hipSetDevice(ctx->device));
+    J.cfg = cfg;
+    J.count = count;
+    J.skip_log = k::tree_skip_threshold(ctx->tuning, count);
+    J.enc = form.enc;
+    J.first_skip_log = form.enc ? form.enc->skip_log : J.skip_log;
+    if (form.kind == ProveForm::BLOCK) {
+        J.block.assign(form.block, form.block + form.n_blobs);
+        J.n_seeds = count / form.n_blobs;
+        form.fold_group = ctx->tuning.seeds_fold_group;
+    }
+    J.blobs.resize(count);
+    J.lay = prove_layout(J.sh, cfg, count, in.on_device ? 0 : in.len, form);
+    TwiddleSet tw;
+    int rc = ctx->ensure_arena(J.lay.arena_bytes);
+    if (rc == FRIEDA_OK) rc = ensure_pinned(ctx, J.lay.pinned_bytes);
+    if (rc == FRIEDA_OK) rc = ctx->get_twiddles(J.sh.n, tw);
+    if (rc) return rc;
+    J.t_start = std::chrono::steady_clock::now();
+    for (double& v : ctx->phase_ms) v = 0.0;
+    // The whole commit phase runs on the device (transcript included) when the last layer fits the single-workgroup tail;
+    // otherwise (log_last_layer_degree_bound + log_blowup_factor > 11) the channel is evaluated on the host between layers.
+    J.dev_channel = J.lay.last_log <= k::TAIL_LOG && !ctx->host_channel;
+    if (count > 1 && !J.dev_channel) return ctx->fail(FRIEDA_ERR_ARG, "batches need the device channel (last layer <= 2^11 points, host channel policy off)");
+    // ---- encode (src/proof.rs:38,44-50) ----
+    const bool small = k::small_domain_shape(ctx->tuning, J.sh.L, J.sh.n) && !ctx->host_channel && J.lay.last_log <= k::TAIL_LOG;
+    k::BlobSource blob{in.data, in.len, in.stride, J.sh.cs.n_padded};  // device data and encoded blobs stay where they are
+    if (!in.on_device && !J.enc) {
+        // a lone small blob is not copied to the device: the first kernel reads it from page-locked host memory
+        const bool in_place = small && count == 1 && in.len <= SMALL_HOST_IN_BYTES;
+        rc = in_place ? ensure_pinned_in(ctx) : upload_blobs(ctx, in, count, ctx->arena + J.lay.o_data, J.lay.bstride);
+        if (rc) return rc;
+        if (in_place && in.len) memcpy(ctx->pinned_in, in.host_ptrs ? in.host_ptrs[0] : in.data, in.len);
+        blob.bytes = in_place ? static_cast<const uint8_t*>(ctx->pinned_in) : ctx->arena + J.lay.o_data;
+        blob.bstride = in_place ? 0 : J.lay.bstride;
+    }
+    // the device-channel path hands the blob to the encode (kernels.h BlobSource); the host-channel path's plain transform wants coefficients
+    if (!small && !J.enc && !J.dev_channel)
+        k::unpack30(J.launch(ctx), blob.bytes, blob.len, reinterpret_cast<uint32_t*>(ctx->arena + J.lay.o_coef), J.sh.cs.n_padded, blob.bstride);
+    ctx->phase_ms[5] = ms_since(t_entry);  // set-up before the first launch (workspace plan, twiddle lookup, ...) + that launch call
+    init_transcripts(ctx, J, seeds);
+    if (form.kind == ProveForm::BLOCK) rc = upload_block_table(ctx, J);
+    if (rc == FRIEDA_OK) rc = J.dev_channel ? enqueue_device_channel(ctx, J, tw, blob) : run_host_channel(ctx, J, tw);
+    if (rc) return rc;
+    ctx->job = std::move(jp);
+    return FRIEDA_OK;
 }
 
 int prove_begin(Ctx* ctx, const uint8_t* data, size_t len, bool data_on_device, const uint64_t* seed, frieda_pcs_config cfg) {
@@ -563,13 +927,9 @@ int prove_begin_batch_ptrs(Ctx* ctx, const uint8_t* const* blobs, size_t len, ui
 }
 
 // `count` blobs of `len` bytes each, blob b at data + b * data_stride (or, host blobs only, at host_ptrs[b]); seeds: null or one per blob
-static int prove_begin_impl(Ctx* ctx, const uint8_t* data, size_t data_stride, size_t len, uint32_t count, bool data_on_device,
-                            const uint64_t* seeds, frieda_pcs_config cfg, const uint8_t* const* host_ptrs, const Encoded* enc,
-                            const Encoded* const* block = nullptr, uint32_t n_block = 0);
-
 int prove_begin_batch(Ctx* ctx, const uint8_t* data, size_t data_stride, size_t len, uint32_t count, bool data_on_device,
                       const uint64_t* seeds, frieda_pcs_config cfg, const uint8_t* const* host_ptrs) {
-    return prove_begin_impl(ctx, data, data_stride, len, count, data_on_device, seeds, cfg, host_ptrs, nullptr);
+    return prove_begin_impl(ctx, BlobsIn{data, data_stride, len, data_on_device, host_ptrs}, count, seeds, cfg, ProveForm{});
 }
 
 int prove_seeds_begin(Ctx* ctx, const Encoded* enc, const uint64_t* seeds, uint32_t n_seeds, frieda_pcs_config cfg) {
@@ -578,7 +938,7 @@ int prove_seeds_begin(Ctx* ctx, const Encoded* enc, const uint64_t* seeds, uint3
     if (n_seeds == 0 || n_seeds > 65535) return ctx->fail(FRIEDA_ERR_ARG, "n_seeds out of range");
     if (cfg.log_blowup_factor != enc->log_blowup) return ctx->fail(FRIEDA_ERR_ARG, "log_blowup_factor differs from the one the blob was encoded with");
     if (enc->device != ctx->device) return ctx->fail(FRIEDA_ERR_ARG, "the encoded blob lives on another device");
-    return prove_begin_impl(ctx, nullptr, 0, enc->len, n_seeds, true, seeds, cfg, nullptr, enc);
+    return prove_begin_impl(ctx, BlobsIn{nullptr, 0, enc->len, true, nullptr}, n_seeds, seeds, cfg, ProveForm{ProveForm::SEEDS, enc});
 }
 
 // The block form: n_seeds seeds (one list) of each of n_blobs encoded blobs of one shape, n_blobs * n_seeds jobs in one launch chain.
@@ -594,340 +954,7 @@ int prove_seeds_blobs_begin(Ctx* ctx, const Encoded* const* encs, uint32_t n_blo
     }
     if (cfg.log_blowup_factor != encs[0]->log_blowup) return ctx->fail(FRIEDA_ERR_ARG, "log_blowup_factor differs from the one the blobs were encoded with");
     if (n_blobs == 1) return prove_seeds_begin(ctx, encs[0], seeds, n_seeds, cfg);
-    return prove_begin_impl(ctx, nullptr, 0, encs[0]->len, n_blobs * n_seeds, true, seeds, cfg, nullptr, encs[0], encs, n_blobs);
-}
-
-namespace {
-// the block table of a prove_seeds_blobs call, as the arena and the pinned staging hold it: rows, one row number per job, and (route B)
-// the first job of every seed group
-struct BlockTablePlan {
-    size_t o_job = 0, o_group = 0, bytes = 0;
-    uint32_t groups = 0;
-    BlockTablePlan(uint32_t n_blobs, uint32_t n_seeds, uint32_t group) {
-        ArenaPlan p;
-        p.take(sizeof(k::SeedsBlobRow) * n_blobs);
-        o_job = p.take(sizeof(uint32_t) * (size_t)n_blobs * n_seeds);
-        groups = group ? n_blobs * ((n_seeds + group - 1) / group) : 0;
-        o_group = p.take(sizeof(uint32_t) * groups);
-        bytes = p.off;
-    }
-};
-}  // namespace
-
-// enc non-null: prove_seeds — `count` seeds of one encoded blob (data unused; seeds non-null)
-// block non-null (with enc = block[0]): prove_seeds_blobs — count = n_block * n_seeds jobs, `seeds` holds the n_seeds of the one list
-static int prove_begin_impl(Ctx* ctx, const uint8_t* data, size_t data_stride, size_t len, uint32_t count, bool data_on_device,
-                            const uint64_t* seeds, frieda_pcs_config cfg, const uint8_t* const* host_ptrs, const Encoded* enc,
-                            const Encoded* const* block, uint32_t n_block) {
-    const auto t_entry = std::chrono::steady_clock::now();
-    FR_NO_JOB(ctx);  // a proof or a commit batch in flight owns the arena and the pinned block
-    if (count == 0 || count > 65535) return ctx->fail(FRIEDA_ERR_ARG, "batch count out of range");
-    if (!enc && count > 1 && data_stride < len) return ctx->fail(FRIEDA_ERR_ARG, "batch stride smaller than the blob length");
-    const uint32_t B = cfg.log_blowup_factor, last = cfg.log_last_layer_degree_bound;
-    // both arrive unchecked: bound them before `last + B` and the shifts that use it are formed
-    if (last > 10) return ctx->fail(FRIEDA_ERR_ARG, "log_last_layer_degree_bound > 10");
-    if (B > FRIEDA_MAX_LOG_DOMAIN) return ctx->fail(FRIEDA_ERR_ARG, "log_blowup_factor larger than FRIEDA_MAX_LOG_DOMAIN");
-    std::unique_ptr<ProveJob, ProveJobDeleter> jp(new ProveJob());
-    ProveJob& J = *jp;
-    Shape& sh = J.sh;
-    int rc = make_shape(ctx, len, B, sh);
-    if (rc) return rc;
-    // FriProver::commit_last_layer asserts evaluation.len() == last_layer_domain_size: needs L - 1 >= last;
-    // the line domain half_odds(n - 1) needs n >= 2
-    if (sh.n < 2 || sh.L < 1 + last) return ctx->fail(FRIEDA_ERR_INVARIANT, "polynomial too small for the FRI configuration");
-    if (cfg.n_queries == 0 || cfg.n_queries > 4096) return ctx->fail(FRIEDA_ERR_ARG, "n_queries out of range");
-    if (cfg.pow_bits > 48) return ctx->fail(FRIEDA_ERR_ARG, "pow_bits > 48");
-    FR_HIP(ctx, hipSetDevice(ctx->device));
-    J.cfg = cfg;
-    J.last = last;
-    J.count = count;
-    J.skip_log = k::tree_skip_threshold(ctx->tuning, count);
-    J.enc = enc;
-    J.first_skip_log = enc ? enc->skip_log : J.skip_log;
-    if (block) {
-        J.block.assign(block, block + n_block);
-        J.n_seeds = count / n_block;
-    }
-    const uint32_t n_seeds = J.n_seeds;
-    J.blobs.resize(count);
-    const uint32_t n = J.n = sh.n, last_log = J.last_log = last + B;
-    const size_t N = J.N = sh.N;
-    const uint32_t n_inner = J.n_inner = (n - 1) - last_log;
-
-    // ---- workspace plan ----
-    ArenaPlan plan;
-    size_t o_data = 0, o_coef = 0;
-    FriLayerDev& first = J.first;
-    std::vector<FriLayerDev>& inner = J.inner;
-    plan_prove_blob(plan, sh, last_log, data_on_device ? 0 : len, o_data, o_coef, first, inner, J.o_lastv, J.o_nonce, enc != nullptr);
-    const size_t o_lastv = J.o_lastv, o_nonce = J.o_nonce;
-    // everything above is per blob; what follows is shared by the batch
-    const size_t bstride = J.bstride = plan.off;  // a multiple of 256
-    plan.off = bstride * count;
-    const size_t o_tr = J.o_tr = plan.take(sizeof(DevTranscript) * count);
-    J.o_gnext = plan.take(sizeof(uint32_t) * k::GRIND_NEXT_STRIDE * count);  // grind window counters, one cache line per blob
-    // decommit gather: per layer <= 2 positions per query; hashes <= 2 * queries * log per layer
-    J.max_words = opening_max_words(cfg.n_queries, n_inner) * count;
-    J.max_hashes = opening_max_hashes(cfg.n_queries, n, n_inner, enc != nullptr) * count;
-    J.o_widx = plan.take(8 * J.max_words);
-    J.o_hidx = plan.take(8 * J.max_hashes);
-    J.o_wout = plan.take(4 * J.max_words);
-    J.o_hout = plan.take(32 * J.max_hashes);
-    // (the table's group part is planned for the largest group count, group 1, whatever FRIEDA_SEEDS_FOLD_GROUP says: the workspace of a
-    // call is a function of its shape alone)
-    const uint32_t blk_group = block ? ctx->tuning.seeds_fold_group : 0;
-    const BlockTablePlan btp(block ? n_block : 0, n_seeds, blk_group), btp_plan(block ? n_block : 0, n_seeds, 1);
-    const size_t o_blk = block ? plan.take(btp_plan.bytes) : 0;
-    rc = ctx->ensure_arena(plan.off);
-    if (rc) return rc;
-    // pinned staging: the transcript summaries of all blobs (header + last-layer polynomial each), or the last layer itself on
-    // the host-channel path, or the gather lists and results
-    const size_t tr_host_pitch = J.tr_host_pitch = (offsetof(DevTranscript, last_poly) + ((size_t)16 << last) + 63) & ~(size_t)63;
-    // device-side openings: header + words + hashes per blob, behind the transcript summaries
-    J.dec_max_words = (uint32_t)(J.max_words / count);
-    J.dec_max_hashes = (uint32_t)(J.max_hashes / count);
-    J.dec_words_off = k::DECOMMIT_HEADER_BYTES;
-    J.dec_hashes_off = J.dec_words_off + ((4 * (size_t)J.dec_max_words + 15) & ~(size_t)15);
-    J.dec_stride = (J.dec_hashes_off + 32 * (size_t)J.dec_max_hashes + 255) & ~(size_t)255;
-    J.dec_off = (tr_host_pitch * count + 255) & ~(size_t)255;
-    size_t pinned_need =
-        std::max<size_t>(std::max<size_t>(std::max<size_t>(tr_host_pitch * count, (sizeof(uint32_t) * 4) << last_log),
-                                          (4 + 8) * J.max_words + (32 + 8) * J.max_hashes + 512),
-                         J.dec_off + J.dec_stride * count);
-    // the block table is staged behind everything else: nothing writes there until the next call on this context
-    const size_t pin_blk = (pinned_need + 255) & ~(size_t)255;
-    if (block) pinned_need = pin_blk + btp.bytes;
-    rc = ensure_pinned(ctx, pinned_need);
-    if (rc) return rc;
-    TwiddleSet tw;
-    rc = ctx->get_twiddles(n, tw);
-    if (rc) return rc;
-    hipStream_t s = ctx->stream;
-    J.t_start = std::chrono::steady_clock::now();
-    for (double& v : ctx->phase_ms) v = 0.0;
-    k::Launch LN = ctx->launch();  // every launch below covers the whole batch
-    LN.batch = count;
-    LN.bstride = count > 1 ? bstride : 0;
-    uint8_t* A = ctx->arena;
-    // The whole commit phase runs on the device (transcript included) when the last layer fits the single-workgroup tail;
-    // otherwise (log_last_layer_degree_bound + log_blowup_factor > 11) the channel is evaluated on the host between layers.
-    const bool dev_channel = J.dev_channel = last_log <= k::TAIL_LOG && !ctx->host_channel;
-    if (count > 1 && !dev_channel)
-        return ctx->fail(FRIEDA_ERR_ARG, "batches need the device channel (last layer <= 2^11 points, host channel policy off)");
-
-    // ---- encode (src/proof.rs:38,44-50) ----
-    const uint8_t* d_data = data;
-    size_t d_data_stride = data_stride;
-    const bool small = k::small_domain_shape(ctx->tuning, sh.L, n) && !ctx->host_channel && last_log <= k::TAIL_LOG;
-    if (!data_on_device && !enc) {
-        if (small && count == 1 && len <= SMALL_HOST_IN_BYTES) {
-            // a lone small blob is not copied to the device: the first kernel reads it from page-locked host memory
-            rc = ensure_pinned_in(ctx);
-            if (rc) return rc;
-            const uint8_t* src = host_ptrs ? host_ptrs[0] : data;
-            if (len) memcpy(ctx->pinned_in, src, len);
-            d_data = static_cast<const uint8_t*>(ctx->pinned_in);
-            d_data_stride = 0;
-        } else {
-            if (len && host_ptrs) {
-                for (uint32_t b = 0; b < count; b++) FR_HIP(ctx, hipMemcpyAsync(A + o_data + (size_t)b * bstride, host_ptrs[b], len, hipMemcpyHostToDevice, s));
-            } else {
-                if (len && count == 1) FR_HIP(ctx, hipMemcpyAsync(A + o_data, data, len, hipMemcpyHostToDevice, s));
-                if (len && count > 1) FR_HIP(ctx, hipMemcpy2DAsync(A + o_data, bstride, data, data_stride, len, count, hipMemcpyHostToDevice, s));
-            }
-            d_data = A + o_data;
-            d_data_stride = bstride;
-        }
-    }
-    uint32_t* coef = reinterpret_cast<uint32_t*>(A + o_coef);
-    // the first layer's columns: in the workspace, or (prove_seeds) the encoded blob's, only ever read
-    uint32_t* eval = enc ? const_cast<uint32_t*>(enc->eval()) : reinterpret_cast<uint32_t*>(A + first.o_vals);
-    // the device-channel path hands the blob to the encode (kernels.h BlobSource); the host-channel path's plain transform wants coefficients
-    const k::BlobSource blob{d_data, len, d_data_stride, sh.cs.n_padded};
-    if (!small && !enc && !dev_channel) k::unpack30(LN, d_data, len, coef, sh.cs.n_padded, d_data_stride);
-    ctx->phase_ms[5] = ms_since(t_entry);  // set-up before the first launch (workspace plan, twiddle lookup, ...) + that launch call
-
-    for (uint32_t b = 0; b < count; b++) {
-        J.blobs[b].ch.init();
-        if (seeds) J.blobs[b].ch.mix_u64(seeds[block ? b % n_seeds : b]);  // src/proof.rs:40-42
-        J.blobs[b].roots.assign(1 + n_inner, Hash32{});
-    }
-    Channel& ch = J.blobs[0].ch;  // (the host-channel path below is single-blob)
-
-    auto cols = [&](const FriLayerDev& lay, int c) { return (&lay == &first ? eval : reinterpret_cast<uint32_t*>(A + lay.o_vals)) + ((size_t)c << lay.log); };
-    const uint32_t seeds_group = enc ? ctx->tuning.seeds_fold_group : 0;
-    if (block) {
-        // the per-blob table, the row of every job and the first job of every seed group: one upload per call, ahead of every launch
-        uint8_t* hp = static_cast<uint8_t*>(ctx->pinned) + pin_blk;
-        k::SeedsBlobRow* rows = reinterpret_cast<k::SeedsBlobRow*>(hp);
-        uint32_t* job_row = reinterpret_cast<uint32_t*>(hp + btp.o_job);
-        uint32_t* group_first = reinterpret_cast<uint32_t*>(hp + btp.o_group);
-        const uint32_t gpb = blk_group ? (n_seeds + blk_group - 1) / blk_group : 0;  // groups per blob: a short last one, none across two blobs
-        for (uint32_t r = 0; r < n_block; r++) {
-            rows[r] = k::SeedsBlobRow{block[r]->eval(), block[r]->tree(), block[r]->d + block[r]->o_root, block[r]->skip_log, 0};
-            for (uint32_t sd = 0; sd < n_seeds; sd++) job_row[r * n_seeds + sd] = r;
-            for (uint32_t g = 0; g < gpb; g++) group_first[r * gpb + g] = r * n_seeds + g * blk_group;
-        }
-        FR_HIP(ctx, hipMemcpyAsync(A + o_blk, hp, btp.bytes, hipMemcpyHostToDevice, s));
-        J.blk.table = reinterpret_cast<const k::SeedsBlobRow*>(A + o_blk);
-        J.blk.job_row = reinterpret_cast<const uint32_t*>(A + o_blk + btp.o_job);
-        J.blk.group_first = blk_group ? reinterpret_cast<const uint32_t*>(A + o_blk + btp.o_group) : nullptr;
-        J.blk.n_blobs = n_block;
-        J.blk.n_seeds = n_seeds;
-    }
-    const k::SeedsBlock* blk = block ? &J.blk : nullptr;
-    std::vector<Hash32>& roots = J.blobs[0].roots;
-    std::vector<QM31>& lastv = J.blobs[0].lastv;
-    if (dev_channel) {
-        DevTranscript* d_tr = reinterpret_cast<DevTranscript*>(A + o_tr);
-        const size_t hdr = offsetof(DevTranscript, last_poly);
-        {
-            // initial transcripts, staged back to back at tr_host_pitch and copied into the device array in one go
-            for (uint32_t b = 0; b < count; b++) {
-                DevTranscript* ht = reinterpret_cast<DevTranscript*>(static_cast<uint8_t*>(ctx->pinned) + b * tr_host_pitch);
-                memset(ht, 0, hdr);
-                ht->ch = J.blobs[b].ch;
-                ht->nonce = ~0ull;
-                ht->draw_bound = ctx->test_draw_bound;
-            }
-            // no copy in the stream: the kernel that finishes the first tree reads these few words from the pinned block itself
-            // (the block is next written by the transcript download behind the grind, i.e. after that kernel)
-        }
-        // the encode's last pass runs fused with FriProver::commit_first_layer's leaf hashing (src/proof.rs:48-52); small domains: unpack +
-        // encode + first tree in one launch, straight from the blob
-        if (enc)  // the first tree and its root exist: only the transcripts' step behind that root — mix_root, first alpha — per seed
-            k::channel_after_shared_root(LN, enc->d + enc->o_root, d_tr, reinterpret_cast<const DevTranscript*>(ctx->pinned), tr_host_pitch, blk);
-        else if (small)
-            k::small_encode_and_first_tree(LN, d_data, len, d_data_stride, sh.L, n, tw.d_tw, tw.ds, eval, N, A + first.o_tree, nullptr, nullptr, d_tr,
-                                           reinterpret_cast<const DevTranscript*>(ctx->pinned), tr_host_pitch);
-        else
-            k::encode_and_first_tree(LN, coef, (size_t)1 << sh.L, sh.L, n, tw.d_tw, tw.ds, eval, N, A + first.o_tree, nullptr, nullptr, d_tr,
-                                     reinterpret_cast<const DevTranscript*>(ctx->pinned), tr_host_pitch, &blob);
-        // FriProver::commit_inner_layers: layers above 2^11 points, one fused fold + tree each
-        const FriLayerDev* cur = &first;
-        bool circle = true;
-        uint32_t kx = 0;
-        // layers of more than 2^TAIL_RUN_LOG points go through the multi-workgroup kernels (a 2^11 layer is faster there than in
-        // the one-workgroup tail); FRIEDA_TAIL_RUN_LOG is a tuning knob
-        const uint32_t tail_run_log = ctx->tuning.tail_run_log;
-        while (kx < n_inner && inner[kx].log > tail_run_log) {
-            k::fold_and_tree(LN, circle, cols(*cur, 0), (size_t)1 << cur->log, cur->log, n, tw.d_itw, tw.ds, cols(inner[kx], 0),
-                             A + inner[kx].o_tree, d_tr, enc && circle, circle ? seeds_group : 0, blk);
-            cur = &inner[kx];
-            circle = false;
-            kx++;
-        }
-        // everything that is left, the last layer's interpolation and mix_felts included, in one workgroup
-        uint32_t* tvals[16];
-        uint8_t* ttrees[16];
-        const uint32_t n_tail = (n_inner - kx) + 1;
-        if (n_tail > 16) return ctx->fail(FRIEDA_ERR_INVARIANT, "internal: tail too long");
-        for (uint32_t i = 0; i + 1 < n_tail; i++) {
-            tvals[i] = cols(inner[kx + i], 0);
-            ttrees[i] = A + inner[kx + i].o_tree;
-        }
-        tvals[n_tail - 1] = reinterpret_cast<uint32_t*>(A + o_lastv);
-        ttrees[n_tail - 1] = nullptr;
-        uint32_t* d_gnext = reinterpret_cast<uint32_t*>(A + J.o_gnext);
-        k::fri_tail(LN, cols(*cur, 0), (size_t)1 << cur->log, cur->log, circle, n, tw.d_itw, tw.ds, last_log, last, n_tail, tvals, ttrees,
-                    d_tr, d_gnext, enc && circle, blk);
-        // grind (src/proof.rs:58), keyed by the digest now sitting in the device transcript: first chunk + transcript download
-        J.grind_base = 0;
-        // first range: 16x the expected search (a miss has probability e^-16; workgroups without work leave at once)
-        J.grind_chunk = (uint64_t)1 << std::max<uint32_t>(22, std::min<uint32_t>(cfg.pow_bits, 36) + 4);
-        if (ctx->tuning.test_grind_first_log) J.grind_chunk = (uint64_t)1 << ctx->tuning.test_grind_first_log;  // test hook: the retry loop runs
-        k::grind_dev(LN, d_tr, d_gnext, cfg.pow_bits, J.grind_base, J.grind_chunk, /*next_zeroed=*/true);
-        rc = download_transcripts(ctx, J);
-        if (rc) return rc;
-        // mix_u64(nonce), query sampling and every opening of the proof, written in proof order into the pinned block
-        J.dev_decommit = cfg.n_queries <= k::DECOMMIT_MAX_QUERIES && 1 + n_inner <= k::DECOMMIT_MAX_LAYERS && n <= k::DECOMMIT_MAX_LOG_DOMAIN &&
-                         !ctx->tuning.host_decommit;
-        if (J.dev_decommit) launch_decommit(ctx, J, LN);
-        FR_HIP(ctx, hipGetLastError());
-        ctx->phase_ms[0] = ms_since(J.t_start);  // commit phase fully enqueued
-    } else {
-        auto fetch_root = [&](const FriLayerDev& lay, Hash32& root) -> int {
-            FR_HIP(ctx, hipMemcpyAsync(ctx->pinned, A + lay.o_tree + k::merkle_layer_offset(lay.log, 0), 32, hipMemcpyDeviceToHost, s));
-            FR_HIP(ctx, hipStreamSynchronize(s));
-            memcpy(root.data(), ctx->pinned, 32);
-            return FRIEDA_OK;
-        };
-
-        // ---- FriProver::commit_first_layer ----
-        if (enc) {
-            memcpy(roots[0].data(), enc->root, 32);  // (prove_seeds, one seed: the commitment was made by encode_blob)
-        } else {
-            k::circle_evaluate(LN, coef, (size_t)1 << sh.L, 4, sh.L, n, tw.d_tw, tw.ds, eval, N);
-            k::merkle_tree4(LN, cols(first, 0), cols(first, 1), cols(first, 2), cols(first, 3), n, A + first.o_tree);
-            rc = fetch_root(first, roots[0]);
-            if (rc) return rc;
-        }
-        uint32_t rw[8];
-        hash_to_words(roots[0].data(), rw);
-        ch.mix_root(rw);
-
-        // ---- FriProver::commit_inner_layers ----
-        QM31 alpha = ch.draw_felt(ctx->test_draw_bound);
-        J.blobs[0].alphas.assign(1 + n_inner, std::array<uint32_t, 4>{});
-        J.blobs[0].alphas[0] = {alpha.a, alpha.b, alpha.c, alpha.d};
-        {
-            // LineEvaluation::new_zero then fold_circle_into_line
-            uint32_t* dst = (n_inner > 0) ? cols(inner[0], 0) : reinterpret_cast<uint32_t*>(A + o_lastv);
-            FR_HIP(ctx, hipMemsetAsync(dst, 0, sizeof(uint32_t) * 4 << (n - 1), s));
-            k::fold_circle_into_line(LN, dst, (size_t)1 << (n - 1), eval, N, n, tw.d_itw, tw.ds, k::Alpha{{alpha.a, alpha.b, alpha.c, alpha.d}});
-        }
-        for (uint32_t kx = 0; kx < n_inner; kx++) {
-            const FriLayerDev& lay = inner[kx];
-            k::merkle_tree4(LN, cols(lay, 0), cols(lay, 1), cols(lay, 2), cols(lay, 3), lay.log, A + lay.o_tree);
-            rc = fetch_root(lay, roots[kx + 1]);
-            if (rc) return rc;
-            hash_to_words(roots[kx + 1].data(), rw);
-            ch.mix_root(rw);
-            alpha = ch.draw_felt(ctx->test_draw_bound);
-            J.blobs[0].alphas[kx + 1] = {alpha.a, alpha.b, alpha.c, alpha.d};
-            uint32_t* dst = (kx + 1 < n_inner) ? cols(inner[kx + 1], 0) : reinterpret_cast<uint32_t*>(A + o_lastv);
-            k::fold_line(LN, cols(lay, 0), (size_t)1 << lay.log, lay.log, n, tw.d_itw, tw.ds, k::Alpha{{alpha.a, alpha.b, alpha.c, alpha.d}}, dst,
-                         (size_t)1 << (lay.log - 1));
-        }
-
-        // ---- FriProver::commit_last_layer ----
-        const size_t n_lastdom = (size_t)1 << last_log;
-        FR_HIP(ctx, hipMemcpyAsync(ctx->pinned, A + o_lastv, sizeof(uint32_t) * 4 * n_lastdom, hipMemcpyDeviceToHost, s));
-        FR_HIP(ctx, hipStreamSynchronize(s));
-        lastv.assign(n_lastdom, QM31{0, 0, 0, 0});
-        {
-            const uint32_t* h = reinterpret_cast<const uint32_t*>(ctx->pinned);
-            for (size_t i = 0; i < n_lastdom; i++) lastv[i] = {h[i], h[n_lastdom + i], h[2 * n_lastdom + i], h[3 * n_lastdom + i]};
-        }
-        line_interpolate(lastv, line_coset(n, last_log));
-        bit_reverse_vec(lastv, n_lastdom, last_log);  // into_ordered_coefficients
-        const size_t n_poly = (size_t)1 << last;
-        for (size_t i = n_poly; i < n_lastdom; i++)
-            if (!qm_is_zero(lastv[i])) return ctx->fail(FRIEDA_ERR_INVARIANT, "invalid degree");  // assert! upstream
-        lastv.resize(n_poly);
-        bit_reverse_vec(lastv, n_poly, last);  // LinePoly::from_ordered_coefficients
-        channel_mix_felts(ch, lastv);
-        memcpy(J.blobs[0].digest_before_grind, ch.digest, 32);
-
-        // ---- grind (src/proof.rs:58-59) ----
-        unsigned long long* d_nonce = reinterpret_cast<unsigned long long*>(A + o_nonce);
-        {
-            FR_HIP(ctx, hipMemsetAsync(d_nonce, 0xFF, 8, s));
-            uint64_t base = 0, chunk = (uint64_t)1 << 22;
-            for (;;) {
-                k::grind_scan(LN, ch.digest, cfg.pow_bits, base, chunk, d_nonce);
-                FR_HIP(ctx, hipMemcpyAsync(ctx->pinned, d_nonce, 8, hipMemcpyDeviceToHost, s));
-                FR_HIP(ctx, hipStreamSynchronize(s));
-                memcpy(&J.blobs[0].nonce, ctx->pinned, 8);
-                if (J.blobs[0].nonce != ~0ull) break;
-                base += chunk;
-                if (chunk < ((uint64_t)1 << 28)) chunk <<= 1;
-            }
-        }
-        ctx->phase_ms[0] = ms_since(J.t_start);
-    }
-    ctx->job = std::move(jp);
-    return FRIEDA_OK;
+    return prove_begin_impl(ctx, BlobsIn{nullptr, 0, encs[0]->len, true, nullptr}, n_blobs * n_seeds, seeds, cfg, ProveForm{ProveForm::BLOCK, encs[0], encs, n_blobs});
 }
 
 int prove_finish(Ctx* ctx, uint8_t out_commitment[32], ProofData& out) {
@@ -941,269 +968,250 @@ int prove_finish(Ctx* ctx, uint8_t out_commitment[32], ProofData& out) {
 
 uint32_t job_count(const Ctx* ctx) { return ctx->job ? ctx->job->count : 0; }
 
-int prove_finish_batch(Ctx* ctx, uint8_t* out_commitments, std::vector<ProofData>& outs) {
-    if (!ctx->job) return ctx->fail(FRIEDA_ERR_ARG, "no proof in flight on this context");
-    std::unique_ptr<ProveJob, ProveJobDeleter> jp = std::move(ctx->job);  // released on every exit path
-    ProveJob& J = *jp;
-    FR_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
-    k::Launch LN = ctx->launch();
-    LN.batch = J.count;
-    LN.bstride = J.count > 1 ? J.bstride : 0;
-    uint8_t* A = ctx->arena;
-    const frieda_pcs_config cfg = J.cfg;
-    const uint32_t n = J.n, last = J.last, n_inner = J.n_inner, count = J.count;
-    const size_t N = J.N;
-    const FriLayerDev& first = J.first;
-    const std::vector<FriLayerDev>& inner = J.inner;
-
-    if (J.dev_channel) {
-        DevTranscript* d_tr = reinterpret_cast<DevTranscript*>(A + J.o_tr);
-        const size_t n_poly = (size_t)1 << last;
-        auto host_tr = [&](uint32_t b) { return reinterpret_cast<const DevTranscript*>(static_cast<const uint8_t*>(ctx->pinned) + b * J.tr_host_pitch); };
-        for (;;) {
-            FR_HIP(ctx, hipStreamSynchronize(s));
-            bool all_found = true;
-            for (uint32_t b = 0; b < count; b++) {
-                if (host_tr(b)->status & 1u) return ctx->fail(FRIEDA_ERR_INVARIANT, "invalid degree");  // assert! upstream
-                all_found &= host_tr(b)->nonce != ~0ull;
-            }
-            if (all_found) break;
-            // next range for the blobs still searching (the others leave at once: their minimum is below every new nonce)
-            J.grind_base += J.grind_chunk;
-            if (J.grind_chunk < ((uint64_t)1 << 28)) J.grind_chunk <<= 1;
-            k::grind_dev(LN, d_tr, reinterpret_cast<uint32_t*>(A + J.o_gnext), cfg.pow_bits, J.grind_base, J.grind_chunk);
-            int rc = download_transcripts(ctx, J);
-            if (rc) return rc;
-            if (J.dev_decommit) launch_decommit(ctx, J, LN);
-        }
-        FR_HIP(ctx, hipGetLastError());
-        for (uint32_t b = 0; b < count; b++) {
-            const DevTranscript* ht = host_tr(b);
-            ProveJob::Blob& bl = J.blobs[b];
-            if (ht->n_roots != 1 + n_inner || ht->n_last_poly != n_poly) return ctx->fail(FRIEDA_ERR_INVARIANT, "internal: transcript out of step");
-            bl.nonce = ht->nonce;
-            bl.ch = ht->ch;
-            memcpy(bl.digest_before_grind, ht->ch.digest, 32);  // downloaded behind the grind, ahead of the decommit kernel
-            bl.alphas.resize(1 + n_inner);
-            for (uint32_t li = 0; li <= n_inner; li++) {
-                for (int w = 0; w < 8; w++)
-                    for (int bb = 0; bb < 4; bb++) bl.roots[li][4 * w + bb] = (uint8_t)(ht->roots[li][w] >> (8 * bb));
-                bl.alphas[li] = {ht->alphas[li][0], ht->alphas[li][1], ht->alphas[li][2], ht->alphas[li][3]};
-            }
-            bl.lastv.resize(n_poly);
-            for (size_t i = 0; i < n_poly; i++)
-                bl.lastv[i] = {ht->last_poly[4 * i], ht->last_poly[4 * i + 1], ht->last_poly[4 * i + 2], ht->last_poly[4 * i + 3]};
-        }
-    }
-    ctx->phase_ms[1] = ms_since(J.t_start);  // commit phase + grind complete on the device (first synchronise)
-    ctx->last_transcript.roots = J.blobs[0].roots;
-    ctx->last_transcript.alphas = J.blobs[0].alphas;
-    memcpy(ctx->last_transcript.digest_before_grind, J.blobs[0].digest_before_grind, 32);
-
+// ---- prove_finish: the pieces, in the order they run ----
+namespace {
+// a job's openings, however they were made: the evaluations and then every layer's witness values; every layer's hash witness; the list sizes
+struct Openings {
     struct LayerCounts {
         size_t n_witness, n_hashes;
     };
-    std::vector<LayerCounts> counts((size_t)count * (1 + n_inner));
-    std::vector<size_t> n_evals(count);
-    std::vector<const uint32_t*> words_of(count);  // per blob: evaluations, then every layer's witness, in proof order
-    std::vector<const uint8_t*> hashes_of(count);  // per blob: every layer's hash witness, in proof order
+    std::vector<LayerCounts> counts;  // job b's layers at b * (1 + n_inner)
+    std::vector<size_t> n_evals;
+    std::vector<const uint32_t*> words_of;
+    std::vector<const uint8_t*> hashes_of;
+    Openings(uint32_t count, uint32_t n_layers) : counts((size_t)count * n_layers), n_evals(count), words_of(count), hashes_of(count) {}
+};
 
-    // ---- FriProver::decommit ----
-    // Normally the device has already done it (decommit.hip, launched behind the grind): the pinned block holds, per blob, a
-    // header with the list sizes and the openings in proof order.  Otherwise (more than 1024 queries, an opening table too
-    // large for the kernel, FRIEDA_HOST_DECOMMIT) the host draws the queries, plans the openings and runs one gather launch.
-    bool from_device = J.dev_decommit;
-    if (from_device) {
-        for (uint32_t b = 0; b < count && from_device; b++) {
-            const uint8_t* reg = static_cast<const uint8_t*>(ctx->pinned) + J.dec_off + (size_t)b * J.dec_stride;
-            const uint32_t* hdr = reinterpret_cast<const uint32_t*>(reg);
-            if (hdr[0] == k::DECOMMIT_OVERFLOW) {
-                from_device = false;
-                break;
-            }
-            if (hdr[0] != k::DECOMMIT_OK) return ctx->fail(FRIEDA_ERR_INVARIANT, "internal: device decommit out of step with the grind");
-            n_evals[b] = hdr[1];
-            words_of[b] = reinterpret_cast<const uint32_t*>(reg + J.dec_words_off);
-            hashes_of[b] = reg + J.dec_hashes_off;
-            LayerCounts* cnt = &counts[(size_t)b * (1 + n_inner)];
-            // layer li: n_witness = |E_{li+1}|, n_hashes = |E_{li+2}| + ... + |E_n|   (hdr[3 + s] = |E_s|)
-            size_t suffix[40] = {0};  // suffix[s] = |E_s| + ... + |E_n|, s <= n + 1 <= 33
-            for (uint32_t sft = n; sft >= 1; sft--) suffix[sft] = suffix[sft + 1] + hdr[3 + sft];
-            for (uint32_t li = 0; li <= n_inner; li++) {
-                cnt[li].n_witness = hdr[3 + li + 1];
-                cnt[li].n_hashes = li + 2 <= n ? suffix[li + 2] : 0;
-            }
+// The first synchronisation of a proof: commit phase and grind done for every job (a job whose first range held no nonce gets further
+// ones); then the downloaded transcript summaries -> ProveJob::Blob (nonce, channel, roots, alphas, last-layer polynomial)
+int wait_for_transcripts(Ctx* ctx, ProveJob& J) {
+    const k::Launch LN = J.launch(ctx);
+    const uint32_t n_inner = J.lay.n_inner;
+    const size_t n_poly = (size_t)1 << J.lay.last;
+    auto host_transcript = [&](uint32_t b) { return reinterpret_cast<const DevTranscript*>(static_cast<const uint8_t*>(ctx->pinned) + b * J.lay.tr_host_pitch); };
+    for (;;) {
+        FR_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        bool all_found = true;
+        for (uint32_t b = 0; b < J.count; b++) {
+            if (host_transcript(b)->status & 1u) return ctx->fail(FRIEDA_ERR_INVARIANT, "invalid degree");  // assert! upstream
+            all_found &= host_transcript(b)->nonce != ~0ull;
         }
-        ctx->phase_ms[2] = ctx->phase_ms[3] = ms_since(J.t_start);
+        if (all_found) break;
+        // next range for the blobs still searching (the others leave at once: their minimum is below every new nonce)
+        J.grind_base += J.grind_chunk;
+        if (J.grind_chunk < ((uint64_t)1 << 28)) J.grind_chunk <<= 1;
+        k::grind_dev(LN, reinterpret_cast<DevTranscript*>(ctx->arena + J.lay.o_tr), reinterpret_cast<uint32_t*>(ctx->arena + J.lay.o_gnext), J.cfg.pow_bits, J.grind_base, J.grind_chunk);
+        int rc = download_transcripts(ctx, J);
+        if (rc) return rc;
+        if (J.dev_decommit) launch_decommit(ctx, J);
     }
-    if (!from_device) {
-        // The host plans against COMPLETE trees; the large ones were built without the two levels above their leaves (the device
-        // decommitment re-hashes those, tree.hip TreeArgs::skip_bc): rebuild such a tree from its layer's values first (a rare path).
-        // prove_seeds: the encoded blob is only ever read (other contexts may be proving from it), so when ITS tree lacks those levels
-        // a complete copy is built in a temporary allocation (a rare path twice over) and layer 0's hashes are gathered from there
-        struct TempTree {
-            uint8_t* d = nullptr;
-            ~TempTree() {
-                if (d) (void)hipFree(d);
-            }
-        } first_full;
-        const uint8_t* first_tree_alt = J.enc ? J.enc->tree() : nullptr;
-        // a block of handles: the same per row of the list, the complete copy built once per DISTINCT blob that needs one (a handle may be
-        // listed more than once) and freed when the call leaves, by whichever path
-        std::vector<DevBuf> block_full(J.block.size());
-        std::vector<const uint8_t*> block_tree(J.block.size(), nullptr);
-        for (size_t r = 0; r < J.block.size(); r++) {
-            const Encoded* e = J.block[r];
-            block_tree[r] = e->tree();
-            if (first.log < e->skip_log) continue;
-            size_t seen = r;
-            for (size_t q = 0; q < r && seen == r; q++)
-                if (J.block[q]->d == e->d) seen = q;
-            if (seen != r) {
-                block_tree[r] = block_tree[seen];
-                continue;
-            }
-            const int arc = block_full[r].alloc(ctx, k::merkle_layer_offset(n, 0) + 32, "poison(complete first-layer tree)");
-            if (arc != FRIEDA_OK) {
-                (void)hipStreamSynchronize(s);  // (the copies built so far are being written)
-                return arc == FRIEDA_ERR_NOMEM ? ctx->fail(FRIEDA_ERR_NOMEM, "no device memory for the complete first-layer tree of the host decommitment") : arc;
-            }
-            const uint32_t* c0 = e->eval();
-            k::merkle_tree4(ctx->launch(), c0, c0 + N, c0 + 2 * N, c0 + 3 * N, n, static_cast<uint8_t*>(block_full[r].p));
-            block_tree[r] = static_cast<const uint8_t*>(block_full[r].p);
+    FR_HIP(ctx, hipGetLastError());
+    for (uint32_t b = 0; b < J.count; b++) {
+        const DevTranscript* ht = host_transcript(b);
+        ProveJob::Blob& bl = J.blobs[b];
+        if (ht->n_roots != 1 + n_inner || ht->n_last_poly != n_poly) return ctx->fail(FRIEDA_ERR_INVARIANT, "internal: transcript out of step");
+        bl.nonce = ht->nonce;
+        bl.ch = ht->ch;
+        memcpy(bl.digest_before_grind, ht->ch.digest, 32);  // downloaded behind the grind, ahead of the decommit kernel
+        bl.alphas.resize(1 + n_inner);
+        for (uint32_t li = 0; li <= n_inner; li++) {
+            for (int w = 0; w < 8; w++)
+                for (int bb = 0; bb < 4; bb++) bl.roots[li][4 * w + bb] = (uint8_t)(ht->roots[li][w] >> (8 * bb));
+            bl.alphas[li] = {ht->alphas[li][0], ht->alphas[li][1], ht->alphas[li][2], ht->alphas[li][3]};
         }
-        // (from here on every exit waits for the stream before the copies go: fail_synced)
-        auto fail_synced = [&](int rc_) {
-            if (!J.block.empty()) (void)hipStreamSynchronize(s);
-            return rc_;
-        };
-        if (J.block.empty() && J.enc && first.log >= J.first_skip_log) {
-            if (hipMalloc((void**)&first_full.d, k::merkle_layer_offset(n, 0) + 32) != hipSuccess) {
-                (void)hipGetLastError();
-                return ctx->fail(FRIEDA_ERR_NOMEM, "no device memory for the complete first-layer tree of the host decommitment");
-            }
-            FR_HIP(ctx, ctx->poison_fresh(first_full.d, k::merkle_layer_offset(n, 0) + 32));
-            const uint32_t* c0 = J.enc->eval();
-            k::merkle_tree4(ctx->launch(), c0, c0 + N, c0 + 2 * N, c0 + 3 * N, n, first_full.d);
-            first_tree_alt = first_full.d;
+        bl.lastv.resize(n_poly);
+        for (size_t i = 0; i < n_poly; i++)
+            bl.lastv[i] = {ht->last_poly[4 * i], ht->last_poly[4 * i + 1], ht->last_poly[4 * i + 2], ht->last_poly[4 * i + 3]};
+    }
+    return FRIEDA_OK;
+}
+
+// the openings the device wrote behind the grind: per job a header with the list sizes, then the lists in proof order.  `complete` false:
+// a job's table overflowed on the device, the host plans and gathers instead
+int read_device_openings(Ctx* ctx, const ProveJob& J, Openings& op, bool& complete) {
+    const uint32_t n = J.sh.n, n_inner = J.lay.n_inner;
+    complete = true;
+    for (uint32_t b = 0; b < J.count; b++) {
+        const uint8_t* reg = static_cast<const uint8_t*>(ctx->pinned) + J.lay.dec_off + (size_t)b * J.lay.dec_stride;
+        const uint32_t* hdr = reinterpret_cast<const uint32_t*>(reg);
+        if (hdr[0] == k::DECOMMIT_OVERFLOW) {
+            complete = false;
+            return FRIEDA_OK;
         }
-        {
-            k::Launch Lb = ctx->launch();  // single-blob launches
-            for (uint32_t b = 0; b < count; b++) {
-                const size_t boff = (size_t)b * J.bstride;
-                auto rebuild = [&](const FriLayerDev& lay) {
-                    if (lay.log < J.skip_log) return;
-                    const uint32_t* c0 = reinterpret_cast<const uint32_t*>(A + lay.o_vals + boff);
-                    const size_t cs = (size_t)1 << lay.log;
-                    k::merkle_tree4(Lb, c0, c0 + cs, c0 + 2 * cs, c0 + 3 * cs, lay.log, A + lay.o_tree + boff);
-                };
-                if (!J.enc) rebuild(first);
-                for (uint32_t kx = 0; kx < n_inner; kx++) rebuild(inner[kx]);
-            }
+        if (hdr[0] != k::DECOMMIT_OK) return ctx->fail(FRIEDA_ERR_INVARIANT, "internal: device decommit out of step with the grind");
+        op.n_evals[b] = hdr[1];
+        op.words_of[b] = reinterpret_cast<const uint32_t*>(reg + J.lay.dec_words_off);
+        op.hashes_of[b] = reg + J.lay.dec_hashes_off;
+        Openings::LayerCounts* cnt = &op.counts[(size_t)b * (1 + n_inner)];
+        // layer li: n_witness = |E_{li+1}|, n_hashes = |E_{li+2}| + ... + |E_n|   (hdr[3 + s] = |E_s|)
+        size_t suffix[40] = {0};  // suffix[s] = |E_s| + ... + |E_n|, s <= n + 1 <= 33
+        for (uint32_t sft = n; sft >= 1; sft--) suffix[sft] = suffix[sft + 1] + hdr[3 + sft];
+        for (uint32_t li = 0; li <= n_inner; li++) {
+            cnt[li].n_witness = hdr[3 + li + 1];
+            cnt[li].n_hashes = li + 2 <= n ? suffix[li + 2] : 0;
         }
-        static thread_local GatherPlan g;  // capacity is kept from proof to proof
-        g.word_idx.clear();
-        g.hash_idx.clear();
-        std::vector<size_t> w_begin(count), h_begin(count);
+    }
+    return FRIEDA_OK;
+}
+
+// FriProver::decommit by the host (more than 1024 queries, an opening table too large for the kernel, FRIEDA_HOST_DECOMMIT): it draws the
+// queries, plans the openings and runs one gather.  It plans against COMPLETE trees; the large ones were built without the two levels
+// above their leaves (the device decommitment re-hashes those, tree.hip TreeArgs::skip_bc): such a tree is rebuilt from its layer's values
+// first (a rare path).  An encoded blob is only ever read (other contexts may be proving from it): when ITS tree lacks those levels a
+// complete copy is built in a temporary allocation and layer 0's hashes are gathered from there.  One handle is a block of one row
+int host_decommit(Ctx* ctx, ProveJob& J, Openings& op) {
+    hipStream_t s = ctx->stream;
+    uint8_t* A = ctx->arena;
+    const ProveLayout& Y = J.lay;
+    const uint32_t n = J.sh.n, n_inner = J.lay.n_inner, count = J.count;
+    const size_t N = J.sh.N;
+    // the rows of first layers the jobs read: none (the arena's own), the handle, or the block's; job y reads row y / row_jobs
+    const Encoded* const one_row[1] = {J.enc};
+    const Encoded* const* rows = J.block.empty() ? one_row : J.block.data();
+    const size_t n_rows = J.block.empty() ? (J.enc ? 1 : 0) : J.block.size(), row_jobs = J.block.empty() ? count : J.n_seeds;
+    // one complete copy per DISTINCT blob that needs one (a handle may be listed more than once), freed when the call leaves, by whichever path
+    std::vector<DevBuf> row_full(n_rows);
+    std::vector<const uint8_t*> row_tree(n_rows, nullptr);
+    for (size_t r = 0; r < n_rows; r++) {
+        const Encoded* e = rows[r];
+        row_tree[r] = e->tree();
+        if (Y.first.log < e->skip_log) continue;
+        size_t seen = r;
+        for (size_t q = 0; q < r && seen == r; q++)
+            if (rows[q]->d == e->d) seen = q;
+        if (seen != r) {
+            row_tree[r] = row_tree[seen];
+            continue;
+        }
+        const int arc = row_full[r].alloc(ctx, k::merkle_layer_offset(n, 0) + 32, "poison(complete first-layer tree)");
+        if (arc != FRIEDA_OK) {
+            (void)hipStreamSynchronize(s);  // (the copies built so far are being written)
+            return arc == FRIEDA_ERR_NOMEM ? ctx->fail(FRIEDA_ERR_NOMEM, "no device memory for the complete first-layer tree of the host decommitment") : arc;
+        }
+        const uint32_t* c0 = e->eval();
+        k::merkle_tree4(ctx->launch(), c0, c0 + N, c0 + 2 * N, c0 + 3 * N, n, static_cast<uint8_t*>(row_full[r].p));
+        row_tree[r] = static_cast<const uint8_t*>(row_full[r].p);
+    }
+    // (from here on every exit waits for the stream before the copies go: fail_synced)
+    auto fail_synced = [&](int rc_) {
+        if (n_rows) (void)hipStreamSynchronize(s);
+        return rc_;
+    };
+    {
+        k::Launch Lb = ctx->launch();  // single-blob launches
         for (uint32_t b = 0; b < count; b++) {
-            ProveJob::Blob& bl = J.blobs[b];
-            bl.ch.mix_u64(bl.nonce);  // src/proof.rs:59
-            const std::vector<uint32_t> queries = generate_queries(bl.ch, n, cfg.n_queries);
-            n_evals[b] = queries.size();
-            w_begin[b] = g.word_idx.size();
-            h_begin[b] = g.hash_idx.size();
-            const size_t boff = (size_t)b * J.bstride;  // this blob's workspace (a multiple of 256 bytes)
-            auto shifted = [&](FriLayerDev lay) {
-                lay.o_vals += boff;
-                lay.o_tree += boff;
-                return lay;
+            const size_t boff = (size_t)b * Y.bstride;
+            auto rebuild = [&](const FriLayerDev& lay) {
+                if (lay.log < J.skip_log) return;
+                const uint32_t* c0 = reinterpret_cast<const uint32_t*>(A + lay.o_vals + boff);
+                const size_t cs = (size_t)1 << lay.log;
+                k::merkle_tree4(Lb, c0, c0 + cs, c0 + 2 * cs, c0 + 3 * cs, lay.log, A + lay.o_tree + boff);
             };
-            LayerCounts* cnt = &counts[(size_t)b * (1 + n_inner)];
-            // Proof.evaluations (src/proof.rs:62-66)
-            // (prove_seeds: `first` holds offsets 0 — indices relative to the encoded blob's columns / tree, marked GATHER_ALT)
-            const uint64_t tag0 = J.enc ? k::GATHER_ALT : 0;
-            const FriLayerDev lay0 = J.enc ? first : shifted(first);
-            for (uint32_t q : queries)
-                for (int c = 0; c < 4; c++) g.word_idx.push_back((lay0.o_vals / 4 + (size_t)c * N + q) | tag0);
-            {
-                std::vector<uint32_t> pos = plan_witness(queries, lay0, g, cnt[0].n_witness, tag0);
-                cnt[0].n_hashes = plan_merkle_decommit(pos, lay0, g, tag0);
-            }
-            std::vector<uint32_t> lq = fold_queries(queries, 1);
-            for (uint32_t kx = 0; kx < n_inner; kx++) {
-                const FriLayerDev lay = shifted(inner[kx]);
-                std::vector<uint32_t> pos = plan_witness(lq, lay, g, cnt[kx + 1].n_witness);
-                cnt[kx + 1].n_hashes = plan_merkle_decommit(pos, lay, g);
-                lq = fold_queries(lq, 1);
-            }
-        }
-        ctx->phase_ms[2] = ms_since(J.t_start);  // queries drawn, openings planned
-        if (g.word_idx.size() > J.max_words || g.hash_idx.size() > J.max_hashes) return fail_synced(ctx->fail(FRIEDA_ERR_INVARIANT, "internal: gather plan overflow"));
-        // one upload (word indices then hash indices, staged in pinned memory), one launch, one download
-        const size_t nw = g.word_idx.size(), nh = g.hash_idx.size();
-        const size_t wbytes = 4 * nw, out_bytes = wbytes + 32 * nh;
-        uint8_t* hp = reinterpret_cast<uint8_t*>(ctx->pinned);
-        uint64_t* hidx = reinterpret_cast<uint64_t*>(hp + ((4 * J.max_words + 32 * J.max_hashes + 255) & ~(size_t)255));
-        memcpy(hidx, g.word_idx.data(), 8 * nw);
-        memcpy(hidx + nw, g.hash_idx.data(), 8 * nh);
-        // the index and output regions of the arena are laid out back to back (words region, then hashes region), so the
-        // hash part may start right behind the words actually used
-        k::Launch L1 = ctx->launch();  // the gather works on absolute indices: a single-blob launch
-        // a block of handles: the tagged indices of row r's jobs (consecutive in both lists) are relative to THAT handle — one launch per row
-        // over the row's slices of the lists; the untagged ones go through the arena base as ever
-        auto gather_all = [&](const uint64_t* widx, uint32_t* wout, const uint64_t* hidx_, uint8_t* hout) {
-            if (J.block.empty()) {
-                k::gather(L1, reinterpret_cast<const uint32_t*>(A), widx, nw, wout, hidx_, nh, hout, J.enc ? J.enc->eval() : nullptr, first_tree_alt);
-                return;
-            }
-            for (size_t r = 0; r < J.block.size(); r++) {
-                const size_t j0 = r * J.n_seeds, j1 = j0 + J.n_seeds;
-                const size_t w0 = w_begin[j0], w1 = j1 < count ? w_begin[j1] : nw, h0 = h_begin[j0], h1 = j1 < count ? h_begin[j1] : nh;
-                k::gather(L1, reinterpret_cast<const uint32_t*>(A), widx + w0, w1 - w0, wout + w0, hidx_ + h0, h1 - h0, hout + 32 * h0, J.block[r]->eval(),
-                          block_tree[r]);
-            }
-        };
-        if (out_bytes <= ((size_t)1 << 20) && !ctx->tuning.gather_copy) {
-            // small openings (the usual case): the kernel reads its index lists from, and writes its results to, the pinned
-            // staging block directly over PCIe — one launch instead of copy + launch + copy (each copy costs 10-20 us of setup)
-            gather_all(hidx, reinterpret_cast<uint32_t*>(hp), hidx + nw, hp + wbytes);
-        } else {
-            if (const hipError_t ce = hipMemcpyAsync(A + J.o_widx, hidx, 8 * (nw + nh), hipMemcpyHostToDevice, s); ce != hipSuccess)
-                return fail_synced(ctx->hip_fail(ce, "hipMemcpyAsync(gather lists)"));
-            gather_all(reinterpret_cast<const uint64_t*>(A + J.o_widx), reinterpret_cast<uint32_t*>(A + J.o_wout),
-                       reinterpret_cast<const uint64_t*>(A + J.o_widx) + nw, A + J.o_wout + wbytes);
-            if (const hipError_t ce = hipMemcpyAsync(hp, A + J.o_wout, out_bytes, hipMemcpyDeviceToHost, s); ce != hipSuccess)
-                return fail_synced(ctx->hip_fail(ce, "hipMemcpyAsync(gathered openings)"));
-        }
-        FR_HIP(ctx, hipStreamSynchronize(s));
-        FR_HIP(ctx, hipGetLastError());
-        ctx->phase_ms[3] = ms_since(J.t_start);  // gather done (second and last synchronise)
-        for (uint32_t b = 0; b < count; b++) {
-            words_of[b] = reinterpret_cast<const uint32_t*>(hp) + w_begin[b];
-            hashes_of[b] = hp + wbytes + 32 * h_begin[b];
+            if (!J.enc) rebuild(Y.first);
+            for (uint32_t kx = 0; kx < n_inner; kx++) rebuild(Y.inner[kx]);
         }
     }
+    static thread_local GatherPlan g;  // capacity is kept from proof to proof
+    g.word_idx.clear();
+    g.hash_idx.clear();
+    std::vector<size_t> w_begin(count), h_begin(count);
+    for (uint32_t b = 0; b < count; b++) {
+        ProveJob::Blob& bl = J.blobs[b];
+        bl.ch.mix_u64(bl.nonce);  // src/proof.rs:59
+        const std::vector<uint32_t> queries = generate_queries(bl.ch, n, J.cfg.n_queries);
+        op.n_evals[b] = queries.size();
+        w_begin[b] = g.word_idx.size();
+        h_begin[b] = g.hash_idx.size();
+        const size_t boff = (size_t)b * Y.bstride;  // this blob's workspace (a multiple of 256 bytes)
+        auto shifted = [&](FriLayerDev lay) {
+            lay.o_vals += boff;
+            lay.o_tree += boff;
+            return lay;
+        };
+        Openings::LayerCounts* cnt = &op.counts[(size_t)b * (1 + n_inner)];
+        // Proof.evaluations (src/proof.rs:62-66)
+        // (an encoded blob: `first` holds offsets 0 — indices relative to the handle's columns / tree, marked GATHER_ALT)
+        const uint64_t tag0 = J.enc ? k::GATHER_ALT : 0;
+        const FriLayerDev lay0 = J.enc ? Y.first : shifted(Y.first);
+        for (uint32_t q : queries)
+            for (int c = 0; c < 4; c++) g.word_idx.push_back((lay0.o_vals / 4 + (size_t)c * N + q) | tag0);
+        {
+            std::vector<uint32_t> pos = plan_witness(queries, lay0, g, cnt[0].n_witness, tag0);
+            cnt[0].n_hashes = plan_merkle_decommit(pos, lay0, g, tag0);
+        }
+        std::vector<uint32_t> lq = fold_queries(queries, 1);
+        for (uint32_t kx = 0; kx < n_inner; kx++) {
+            const FriLayerDev lay = shifted(Y.inner[kx]);
+            std::vector<uint32_t> pos = plan_witness(lq, lay, g, cnt[kx + 1].n_witness);
+            cnt[kx + 1].n_hashes = plan_merkle_decommit(pos, lay, g);
+            lq = fold_queries(lq, 1);
+        }
+    }
+    ctx->phase_ms[2] = ms_since(J.t_start);  // queries drawn, openings planned
+    if (g.word_idx.size() > Y.max_words || g.hash_idx.size() > Y.max_hashes) return fail_synced(ctx->fail(FRIEDA_ERR_INVARIANT, "internal: gather plan overflow"));
+    // one upload (word indices then hash indices, staged in pinned memory), one launch, one download
+    const size_t nw = g.word_idx.size(), nh = g.hash_idx.size();
+    const size_t wbytes = 4 * nw, out_bytes = wbytes + 32 * nh;
+    uint8_t* hp = reinterpret_cast<uint8_t*>(ctx->pinned);
+    uint64_t* hidx = reinterpret_cast<uint64_t*>(hp + Y.gather_off);
+    memcpy(hidx, g.word_idx.data(), 8 * nw);
+    memcpy(hidx + nw, g.hash_idx.data(), 8 * nh);
+    // the index and output regions of the arena are laid out back to back (words region, then hashes region), so the
+    // hash part may start right behind the words actually used
+    k::Launch L1 = ctx->launch();  // the gather works on absolute indices: a single-blob launch
+    // the tagged indices of row r's jobs (consecutive in both lists) are relative to THAT handle — one launch per row over the row's
+    // slices of the lists (one handle: one launch over the whole lists); the untagged ones go through the arena base as ever
+    auto gather_all = [&](const uint64_t* widx, uint32_t* wout, const uint64_t* hidx_, uint8_t* hout) {
+        if (!n_rows) k::gather(L1, reinterpret_cast<const uint32_t*>(A), widx, nw, wout, hidx_, nh, hout, nullptr, nullptr);
+        for (size_t r = 0; r < n_rows; r++) {
+            const size_t j0 = r * row_jobs, j1 = j0 + row_jobs;
+            const size_t w0 = w_begin[j0], w1 = j1 < count ? w_begin[j1] : nw, h0 = h_begin[j0], h1 = j1 < count ? h_begin[j1] : nh;
+            k::gather(L1, reinterpret_cast<const uint32_t*>(A), widx + w0, w1 - w0, wout + w0, hidx_ + h0, h1 - h0, hout + 32 * h0, rows[r]->eval(), row_tree[r]);
+        }
+    };
+    if (out_bytes <= ((size_t)1 << 20) && !ctx->tuning.gather_copy) {
+        // small openings (the usual case): the kernel reads its index lists from, and writes its results to, the pinned
+        // staging block directly over PCIe — one launch instead of copy + launch + copy (each copy costs 10-20 us of setup)
+        gather_all(hidx, reinterpret_cast<uint32_t*>(hp), hidx + nw, hp + wbytes);
+    } else {
+        if (const hipError_t ce = hipMemcpyAsync(A + Y.o_widx, hidx, 8 * (nw + nh), hipMemcpyHostToDevice, s); ce != hipSuccess)
+            return fail_synced(ctx->hip_fail(ce, "hipMemcpyAsync(gather lists)"));
+        gather_all(reinterpret_cast<const uint64_t*>(A + Y.o_widx), reinterpret_cast<uint32_t*>(A + Y.o_wout),
+                   reinterpret_cast<const uint64_t*>(A + Y.o_widx) + nw, A + Y.o_wout + wbytes);
+        if (const hipError_t ce = hipMemcpyAsync(hp, A + Y.o_wout, out_bytes, hipMemcpyDeviceToHost, s); ce != hipSuccess)
+            return fail_synced(ctx->hip_fail(ce, "hipMemcpyAsync(gathered openings)"));
+    }
+    FR_HIP(ctx, hipStreamSynchronize(s));
+    FR_HIP(ctx, hipGetLastError());
+    ctx->phase_ms[3] = ms_since(J.t_start);  // gather done (second and last synchronise)
+    for (uint32_t b = 0; b < count; b++) {
+        op.words_of[b] = reinterpret_cast<const uint32_t*>(hp) + w_begin[b];
+        op.hashes_of[b] = hp + wbytes + 32 * h_begin[b];
+    }
+    return FRIEDA_OK;
+}
 
-    // ---- assemble the Proofs (src/proof.rs:67-76) ----
+// the Proofs (src/proof.rs:67-76) from the transcripts and the openings
+void assemble_proofs(ProveJob& J, const Openings& op, uint8_t* out_commitments, std::vector<ProofData>& outs) {
+    const uint32_t n_inner = J.lay.n_inner, count = J.count;
     if (outs.size() != count) outs.assign(count, ProofData{});  // else: the caller's (recycled) objects, every field rewritten below
     for (uint32_t b = 0; b < count; b++) {
         ProveJob::Blob& bl = J.blobs[b];
         ProofData& out = outs[b];
-        const LayerCounts* cnt = &counts[(size_t)b * (1 + n_inner)];
-        const uint32_t* wv = words_of[b];
-        const uint8_t* hv = hashes_of[b];
+        const Openings::LayerCounts* cnt = &op.counts[(size_t)b * (1 + n_inner)];
+        const uint32_t* wv = op.words_of[b];
+        const uint8_t* hv = op.hashes_of[b];
         size_t wi = 0, hi = 0;
         auto take_qm = [&]() {
             QM31 q{wv[wi], wv[wi + 1], wv[wi + 2], wv[wi + 3]};
             wi += 4;
             return q;
         };
-        out.pcs_config = cfg;
+        out.pcs_config = J.cfg;
         out.log_size_bound = J.sh.L;
         out.proof_of_work = bl.nonce;
         out.last_layer_poly = std::move(bl.lastv);
-        out.evaluations.resize(n_evals[b]);
+        out.evaluations.resize(op.n_evals[b]);
         for (auto& q : out.evaluations) q = take_qm();
         out.inner_layers.resize(n_inner);
         for (uint32_t li = 0; li <= n_inner; li++) {
@@ -1218,6 +1226,37 @@ int prove_finish_batch(Ctx* ctx, uint8_t* out_commitments, std::vector<ProofData
         }
         memcpy(out_commitments + 32 * (size_t)b, bl.roots[0].data(), 32);
     }
+}
+}  // namespace
+
+int prove_finish_batch(Ctx* ctx, uint8_t* out_commitments, std::vector<ProofData>& outs) {
+    if (!ctx->job) return ctx->fail(FRIEDA_ERR_ARG, "no proof in flight on this context");
+    std::unique_ptr<ProveJob, ProveJobDeleter> jp = std::move(ctx->job);  // released on every exit path
+    ProveJob& J = *jp;
+    FR_HIP(ctx, hipSetDevice(ctx->device));
+    int rc;
+    if (J.dev_channel) {
+        rc = wait_for_transcripts(ctx, J);
+        if (rc) return rc;
+    }
+    ctx->phase_ms[1] = ms_since(J.t_start);  // commit phase + grind complete on the device (first synchronise)
+    ctx->last_transcript.roots = J.blobs[0].roots;
+    ctx->last_transcript.alphas = J.blobs[0].alphas;
+    memcpy(ctx->last_transcript.digest_before_grind, J.blobs[0].digest_before_grind, 32);
+
+    // ---- FriProver::decommit: normally the device has already done it (launched behind the grind) ----
+    Openings op(J.count, 1 + J.lay.n_inner);
+    bool from_device = J.dev_decommit;
+    if (from_device) {
+        rc = read_device_openings(ctx, J, op, from_device);
+        if (rc) return rc;
+        ctx->phase_ms[2] = ctx->phase_ms[3] = ms_since(J.t_start);
+    }
+    if (!from_device) {
+        rc = host_decommit(ctx, J, op);
+        if (rc) return rc;
+    }
+    assemble_proofs(J, op, out_commitments, outs);
     ctx->phase_ms[4] = ms_since(J.t_start);  // proofs assembled
     return FRIEDA_OK;
 }
@@ -1330,12 +1369,10 @@ int encode_blob(Ctx* ctx, const uint8_t* data, size_t len, bool data_on_device, 
     ArenaPlan plan;
     const size_t o_data = plan.take(data_on_device ? 0 : len);
     const size_t o_coef = plan.take(sizeof(uint32_t) * sh.cs.n_padded);
-    rc = ctx->ensure_arena(plan.off);
-    if (rc) return rc;
-    rc = ensure_pinned(ctx, 4096);
-    if (rc) return rc;
     TwiddleSet tw;
-    rc = ctx->get_twiddles(sh.n, tw);
+    rc = ctx->ensure_arena(plan.off);
+    if (rc == FRIEDA_OK) rc = ensure_pinned(ctx, 4096);
+    if (rc == FRIEDA_OK) rc = ctx->get_twiddles(sh.n, tw);
     if (rc) return rc;
     std::unique_ptr<Encoded, void (*)(Encoded*)> e(new Encoded(), encoded_free);
     {
@@ -1350,19 +1387,13 @@ int encode_blob(Ctx* ctx, const uint8_t* data, size_t len, bool data_on_device, 
     uint8_t* A = ctx->arena;
     const uint8_t* d_data = data;
     if (!data_on_device) {
-        if (len) FR_HIP(ctx, hipMemcpyAsync(A + o_data, data, len, hipMemcpyHostToDevice, s));
+        rc = upload_blobs(ctx, BlobsIn{data, 0, len, false, nullptr}, 1, A + o_data, 0);
+        if (rc) return rc;
         d_data = A + o_data;
     }
-    const k::Launch LN = ctx->launch();
-    uint32_t* eval = reinterpret_cast<uint32_t*>(e->d);
-    if (k::small_domain_shape(ctx->tuning, sh.L, sh.n)) {
-        k::small_encode_and_first_tree(LN, d_data, len, 0, sh.L, sh.n, tw.d_tw, tw.ds, eval, sh.N, e->d + e->o_tree, nullptr, e->d + e->o_root, nullptr,
-                                       nullptr, 0);
-    } else {
-        uint32_t* coef = reinterpret_cast<uint32_t*>(A + o_coef);
-        const k::BlobSource blob{d_data, len, 0, sh.cs.n_padded};
-        k::encode_and_first_tree(LN, coef, (size_t)1 << sh.L, sh.L, sh.n, tw.d_tw, tw.ds, eval, sh.N, e->d + e->o_tree, nullptr, e->d + e->o_root, nullptr, nullptr, 0, &blob);
-    }
+    encode_first_tree(ctx->launch(), sh, tw, k::BlobSource{d_data, len, 0, sh.cs.n_padded},
+                      EncodeDest{reinterpret_cast<uint32_t*>(A + o_coef), reinterpret_cast<uint32_t*>(e->d), sh.N, e->d + e->o_tree, nullptr, e->d + e->o_root, nullptr,
+                                 nullptr, 0});
     FR_HIP(ctx, hipMemcpyAsync(ctx->pinned, e->d + e->o_root, 32, hipMemcpyDeviceToHost, s));
     FR_HIP(ctx, hipStreamSynchronize(s));
     FR_HIP(ctx, hipGetLastError());
@@ -1389,12 +1420,10 @@ int encode_batch(Ctx* ctx, const uint8_t* data, size_t data_stride, size_t len, 
     ArenaPlan plan;
     const size_t o_data = plan.take(dstride * count);
     const size_t o_coef = plan.take(small ? 0 : bstride * (count - 1) + sizeof(uint32_t) * sh.cs.n_padded);
-    rc = ctx->ensure_arena(plan.off);
-    if (rc) return rc;
-    rc = ensure_pinned(ctx, 32 * (size_t)count + 4096);
-    if (rc) return rc;
     TwiddleSet tw;
-    rc = ctx->get_twiddles(sh.n, tw);
+    rc = ctx->ensure_arena(plan.off);
+    if (rc == FRIEDA_OK) rc = ensure_pinned(ctx, 32 * (size_t)count + 4096);
+    if (rc == FRIEDA_OK) rc = ctx->get_twiddles(sh.n, tw);
     if (rc) return rc;
     EncodedBlock blk;
     rc = blk.alloc(ctx, len, log_blowup, sh.L, sh.n, count, k::tree_skip_threshold(ctx->tuning, count));
@@ -1407,15 +1436,10 @@ int encode_batch(Ctx* ctx, const uint8_t* data, size_t data_stride, size_t len, 
     LN.batch = count;
     LN.bstride = count > 1 ? bstride : 0;
     auto run = [&]() -> int {
-        if (len) FR_HIP(ctx, hipMemcpy2DAsync(A + o_data, dstride, data, count > 1 ? data_stride : len, len, count, hipMemcpyHostToDevice, s));
-        uint32_t* eval = reinterpret_cast<uint32_t*>(S);
-        if (small) {
-            k::small_encode_and_first_tree(LN, A + o_data, len, dstride, sh.L, sh.n, tw.d_tw, tw.ds, eval, sh.N, S + o_tree, nullptr, S + o_root, nullptr, nullptr, 0);
-        } else {
-            uint32_t* coef = reinterpret_cast<uint32_t*>(A + o_coef);
-            const k::BlobSource blob{A + o_data, len, dstride, sh.cs.n_padded};
-            k::encode_and_first_tree(LN, coef, (size_t)1 << sh.L, sh.L, sh.n, tw.d_tw, tw.ds, eval, sh.N, S + o_tree, nullptr, S + o_root, nullptr, nullptr, 0, &blob);
-        }
+        int urc = upload_blobs(ctx, BlobsIn{data, data_stride, len, false, nullptr}, count, A + o_data, dstride, /*lone_as_row=*/true);
+        if (urc) return urc;
+        encode_first_tree(LN, sh, tw, k::BlobSource{A + o_data, len, dstride, sh.cs.n_padded},
+                          EncodeDest{reinterpret_cast<uint32_t*>(A + o_coef), reinterpret_cast<uint32_t*>(S), sh.N, S + o_tree, nullptr, S + o_root, nullptr, nullptr, 0});
         FR_HIP(ctx, hipMemcpy2DAsync(ctx->pinned, 32, S + o_root, bstride, 32, count, hipMemcpyDeviceToHost, s));
         FR_HIP(ctx, hipStreamSynchronize(s));
         FR_HIP(ctx, hipGetLastError());
@@ -1430,47 +1454,18 @@ int encode_batch(Ctx* ctx, const uint8_t* data, size_t data_stride, size_t len, 
     return rc == FRIEDA_OK ? rc : ctx->fail(rc, "host allocation failed");
 }
 
-// what prove_begin_impl plans for a prove_seeds job: the per-seed part times n_seeds, then the transcripts, the grind counters and the
-// opening lists of the host-planner fallback
+// what prove_begin_impl plans for a prove_seeds job (prove_layout)
 size_t seeds_workspace_bytes(size_t len, frieda_pcs_config cfg, uint32_t n_seeds) {
-    const uint32_t B = cfg.log_blowup_factor, last = cfg.log_last_layer_degree_bound;
-    if (n_seeds == 0 || n_seeds > 65535 || last > 10 || B > FRIEDA_MAX_LOG_DOMAIN || len > ((size_t)1 << 40)) return 0;
-    if (cfg.n_queries == 0 || cfg.n_queries > 4096) return 0;
-    Shape sh;
-    sh.cs = codec_shape(len);
-    sh.L = sh.cs.log_size;
-    sh.B = B;
-    if ((uint64_t)sh.L + B < 1 || (uint64_t)sh.L + B > FRIEDA_MAX_LOG_DOMAIN) return 0;
-    sh.n = sh.L + B;
-    sh.N = (size_t)1 << sh.n;
-    if (sh.n < 2 || sh.L < 1 + last) return 0;
-    const uint32_t n_inner = (sh.n - 1) - (last + B);
-    ArenaPlan plan;
-    size_t a, b, c, d;
-    FriLayerDev first;
-    std::vector<FriLayerDev> inner;
-    plan_prove_blob(plan, sh, last + B, 0, a, b, first, inner, c, d, true);
-    plan.off *= n_seeds;
-    plan.take(sizeof(DevTranscript) * n_seeds);
-    plan.take(sizeof(uint32_t) * k::GRIND_NEXT_STRIDE * n_seeds);
-    const size_t mw = opening_max_words(cfg.n_queries, n_inner) * n_seeds, mh = opening_max_hashes(cfg.n_queries, sh.n, n_inner, true) * n_seeds;
-    plan.take(8 * mw);
-    plan.take(8 * mh);
-    plan.take(4 * mw);
-    plan.take(32 * mh);
-    return plan.off;
+    if (n_seeds == 0 || n_seeds > 65535) return 0;
+    return prove_arena_bytes(len, cfg, n_seeds, ProveForm{ProveForm::SEEDS});
 }
 
 // ... and for a prove_seeds_blobs job: the same plan at n_blobs * n_seeds jobs, then the block table (rows, a row number per job, the
 // first job of every seed group at its largest count).  One blob is prove_seeds, table and all
 size_t seeds_blobs_workspace_bytes(size_t len, frieda_pcs_config cfg, uint32_t n_blobs, uint32_t n_seeds) {
     if (n_blobs == 0 || n_seeds == 0 || (uint64_t)n_blobs * n_seeds > 65535) return 0;
-    const size_t jobs = seeds_workspace_bytes(len, cfg, n_blobs * n_seeds);  // (a multiple of 256)
-    if (n_blobs == 1 || jobs == 0) return jobs;
-    ArenaPlan plan;
-    plan.off = jobs;
-    plan.take(BlockTablePlan(n_blobs, n_seeds, 1).bytes);
-    return plan.off;
+    if (n_blobs == 1) return seeds_workspace_bytes(len, cfg, n_seeds);
+    return prove_arena_bytes(len, cfg, n_blobs * n_seeds, ProveForm{ProveForm::BLOCK, nullptr, nullptr, n_blobs});
 }
 
 }  // namespace frieda

@@ -105,6 +105,82 @@ def test_poison_fills_what_it_reports_and_nothing_the_caller_sees(oracle):
         ctx.close()
 
 
+# ---- a call takes what its sizing function says ---------------------------------------------------------------------------------------------
+MIB = 1 << 20
+
+
+def _arena_after(call):
+    """the arena of a context that has made this one call (the hook's region 0); data and handles come from another context"""
+    import frieda_amd
+
+    ctx = frieda_amd.Context(0)
+    try:
+        call(ctx)
+        return poison(ctx, 0xDEADBEEF, sticky=0)[0]
+    finally:
+        ctx.close()
+
+
+def _rounded(nbytes):
+    """Ctx::ensure_arena's rule"""
+    return (nbytes + MIB - 1) & ~(MIB - 1)
+
+
+def test_a_call_takes_what_its_sizing_function_says(oracle):
+    """The arena of a fresh context after ONE call equals the public sizing function's figure, rounded up to 1 MiB as ensure_arena does:
+    one layout feeds the call and the function.  Device-resident data, as the functions assume; the handles of the seeds forms are
+    encoded on another context (an encode's own arena would hide the call's).  No public function gives a plain batch's total (its
+    shared tail — transcripts, grind counters, opening lists — is not the seeds forms' exact one): for it the per-blob figure bounds the
+    arena from below, and the tail of three 2^12 jobs (about 0.5 MiB) plus the rounding from above."""
+    import frieda_amd
+    from util import DevBuf
+
+    cfg = W.cfg_of(20, 4, 0, 20)
+    small, big = W.BLOBS["ff_then_00"](blob_len_for(12)), W.BLOBS["ff_then_00"](blob_len_for(16))
+    helper = frieda_amd.Context(0)
+    try:
+        stride = (len(small) + 255) & ~255
+        three = np.zeros((3, stride), dtype=np.uint8)
+        three[:, : len(small)] = np.frombuffer(small, dtype=np.uint8)
+        d_three, d_big = DevBuf.from_array(helper, three), DevBuf.from_array(helper, np.frombuffer(big, dtype=np.uint8))
+        want_small = oracle.commit_and_generate_proof(small, 7, oracle.make_config(20, 4, 0, 20))
+
+        def lone(ctx):
+            ctx.prove_begin_device(d_three.ptr, len(small), 7, cfg)
+            root, proof = ctx.prove_finish()
+            assert (root, proof.serialize()) == (want_small[0], want_small[1].serialize())
+
+        ws = frieda_amd.workspace_bytes(len(small), 4, 0)
+        assert _arena_after(lone) == _rounded(ws) > 0
+
+        def batch(ctx):
+            got = ctx.commit_and_generate_proof_batch_device(d_three.ptr, stride, len(small), 3, [7, 7, 7], cfg)
+            assert [(r, p.serialize()) for r, p in got] == [(want_small[0], want_small[1].serialize())] * 3
+
+        assert 3 * ws <= _arena_after(batch) < 3 * ws + 2 * MIB
+
+        with helper.encode(big, 4) as enc:
+            want = [p.serialize() for p in helper.prove_seeds(enc, [5, 6], cfg)]
+            got = _arena_after(lambda ctx: [p.serialize() for p in ctx.prove_seeds(enc, [5, 6], cfg)] == want or pytest.fail("other proofs"))
+            assert got == _rounded(frieda_amd.seeds_workspace_bytes(len(big), cfg, 2)) > 0
+        encs = helper.encode_batch([small, small[::-1]], 4)
+        try:
+            want = [[p.serialize() for p in row] for row in helper.prove_seeds_blobs(encs, [5, 6], cfg)]
+            got = _arena_after(lambda ctx: [[p.serialize() for p in row] for row in ctx.prove_seeds_blobs(encs, [5, 6], cfg)] == want or pytest.fail("other proofs"))
+            assert got == _rounded(frieda_amd.seeds_blobs_workspace_bytes(len(small), cfg, 2, 2)) > 0
+        finally:
+            for e in encs:
+                e.close()
+
+        root_big = oracle.commit(big, 4)
+        got = _arena_after(lambda ctx: ctx.commit_batch_device(d_big.ptr, len(big), len(big), 1, 4) == [root_big] or pytest.fail("other root"))
+        assert got == _rounded(frieda_amd.workspace_bytes(len(big), 4, prove=False)) > 0
+        d_three.free()
+        d_big.free()
+    finally:
+        helper.close()
+
+
 # ---- history beyond the arena ------------------------------------------------------------------------------------------------------------
 PROBE = ("prove/general", "prove/small_fused", "interpolate_points/lines", "verify_cells_many", "reconstruct_from_proof_pairs", "open_cells/small_fused")
 
