@@ -111,6 +111,11 @@ extern "C" {
     pub fn frieda_seeds_workspace_bytes(len: usize, cfg: frieda_pcs_config, n_seeds: u32) -> usize;
     pub fn frieda_prove_seeds_blobs_begin(ctx: *mut frieda_ctx, encs: *const *const frieda_encoded, n_blobs: u32, seeds: *const u64, n_seeds: u32, cfg: frieda_pcs_config) -> c_int;
     pub fn frieda_prove_seeds_blobs_finish(ctx: *mut frieda_ctx, out_proofs: *mut *mut frieda_proof) -> c_int;
+    pub fn frieda_prove_jobs_begin(ctx: *mut frieda_ctx, encs: *const *const frieda_encoded, n_blobs: u32, blob_index: *const u32, seeds: *const u64, n_jobs: u32, cfg: frieda_pcs_config) -> c_int;
+    pub fn frieda_prove_jobs_finish(ctx: *mut frieda_ctx, out_proofs: *mut *mut frieda_proof) -> c_int;
+    pub fn frieda_prove_jobs(ctx: *mut frieda_ctx, encs: *const *const frieda_encoded, n_blobs: u32, blob_index: *const u32, seeds: *const u64, n_jobs: u32, cfg: frieda_pcs_config, out_proofs: *mut *mut frieda_proof) -> c_int;
+    pub fn frieda_prove_jobs_workspace_bytes(len: usize, cfg: frieda_pcs_config, n_blobs: u32, n_jobs: u32) -> usize;
+    pub fn frieda_prove_jobs_plan(ctx: *const frieda_ctx, len: usize, cfg: frieda_pcs_config, n_blobs: u32, n_jobs: u32, jobs_per_pass: *mut u32, n_passes: *mut u32) -> c_int;
     pub fn frieda_prove_seeds_blobs(ctx: *mut frieda_ctx, encs: *const *const frieda_encoded, n_blobs: u32, seeds: *const u64, n_seeds: u32, cfg: frieda_pcs_config, out_proofs: *mut *mut frieda_proof) -> c_int;
     pub fn frieda_seeds_blobs_workspace_bytes(len: usize, cfg: frieda_pcs_config, n_blobs: u32, n_seeds: u32) -> usize;
     pub fn frieda_commit_batch(ctx: *mut frieda_ctx, data: *const u8, stride: usize, len: usize, count: u32, log_blowup_factor: u32, out_roots: *mut u8) -> c_int;

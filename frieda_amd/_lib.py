@@ -126,6 +126,11 @@ def lib():
         "frieda_prove_seeds_blobs_begin": (C.c_int, [vp, vp, u32, u64p, u32, PcsConfigC]),
         "frieda_prove_seeds_blobs_finish": (C.c_int, [vp, pp]),
         "frieda_prove_seeds_blobs": (C.c_int, [vp, vp, u32, u64p, u32, PcsConfigC, pp]),
+        "frieda_prove_jobs_begin": (C.c_int, [vp, vp, u32, C.POINTER(u32), u64p, u32, PcsConfigC]),
+        "frieda_prove_jobs_finish": (C.c_int, [vp, pp]),
+        "frieda_prove_jobs": (C.c_int, [vp, vp, u32, C.POINTER(u32), u64p, u32, PcsConfigC, pp]),
+        "frieda_prove_jobs_workspace_bytes": (sz, [sz, PcsConfigC, u32, u32]),
+        "frieda_prove_jobs_plan": (C.c_int, [vp, sz, PcsConfigC, u32, u32, C.POINTER(u32), C.POINTER(u32)]),
         "frieda_seeds_blobs_workspace_bytes": (sz, [sz, PcsConfigC, u32, u32]),
         "frieda_commit_batch": (C.c_int, [vp, vp, sz, sz, u32, u32, vp]),
         "frieda_commit_batch_device": (C.c_int, [vp, vp, sz, sz, u32, u32, vp]),

@@ -395,6 +395,38 @@ class Context:
         self.prove_seeds_blobs_begin(encs, seeds, pcs_config)
         return self.prove_seeds_blobs_finish()
 
+    # ---- any list of (blob, seed) jobs over a block of handles ----
+    @staticmethod
+    def _jobs_arrays(encs, jobs):
+        encs = list(encs)
+        jobs = [(int(b), int(s)) for b, s in jobs]
+        handles = (C.c_void_p * max(1, len(encs)))(*[e._handle() for e in encs])
+        bidx = (C.c_uint32 * max(1, len(jobs)))(*[b for b, _ in jobs])
+        seeds = (C.c_uint64 * max(1, len(jobs)))(*[s for _, s in jobs])
+        return len(encs), len(jobs), handles, bidx, seeds
+
+    def prove_jobs_begin(self, encs, jobs, pcs_config):
+        """Enqueue one proof per job of `jobs`, a list of (blob_index, seed): encs[blob_index] under seed, all in one pass.  The handles
+        must stay open until prove_jobs_finish() returns."""
+        n_blobs, n_jobs, handles, bidx, seeds = self._jobs_arrays(encs, jobs)
+        _check(self._L.frieda_prove_jobs_begin(self._h, handles, n_blobs, bidx, seeds, n_jobs, pcs_config._c()), self._h)
+        self._jobs_in_flight = n_jobs
+
+    def prove_jobs_finish(self):
+        count = getattr(self, "_jobs_in_flight", 0)
+        self._jobs_in_flight = 0
+        outs = (C.c_void_p * max(1, count))()
+        _check(self._L.frieda_prove_jobs_finish(self._h, outs), self._h)
+        return [Proof(C.c_void_p(outs[i])) for i in range(count)]
+
+    def prove_jobs(self, encs, jobs, pcs_config):
+        """[Proof] in the caller's order: proof j is prove_seeds(encs[jobs[j][0]], [jobs[j][1]], pcs_config)[0], byte for byte.  The call
+        cuts itself into passes (prove_jobs_plan)."""
+        n_blobs, n_jobs, handles, bidx, seeds = self._jobs_arrays(encs, jobs)
+        outs = (C.c_void_p * max(1, n_jobs))()
+        _check(self._L.frieda_prove_jobs(self._h, handles, n_blobs, bidx, seeds, n_jobs, pcs_config._c(), outs), self._h)
+        return [Proof(C.c_void_p(outs[i])) for i in range(n_jobs)]
+
     def commit_and_generate_proofs_for_seeds(self, data, seeds, pcs_config):
         """(commitment, [Proof]) for a caller that has every seed at once: encode, prove, free."""
         a = _as_bytes(data)
@@ -1285,6 +1317,21 @@ def seeds_blobs_workspace_bytes(length, pcs_config, n_blobs, n_seeds):
     return int(_lib.lib().frieda_seeds_blobs_workspace_bytes(length, pcs_config._c(), n_blobs, n_seeds))
 
 
+def prove_jobs_workspace_bytes(length, pcs_config, n_blobs, n_jobs):
+    """Workspace one pass of n_jobs jobs over n_blobs handles asks of its context, the handles excluded (frieda_prove_jobs_workspace_bytes);
+    0: refused shape.  At n_blobs == 1: seeds_workspace_bytes; at (K, K * S): seeds_blobs_workspace_bytes(K, S)."""
+    return int(_lib.lib().frieda_prove_jobs_workspace_bytes(length, pcs_config._c(), n_blobs, n_jobs))
+
+
+def prove_jobs_plan(length, pcs_config, n_blobs, n_jobs, ctx=None):
+    """(jobs_per_pass, n_passes): how prove_jobs cuts n_jobs jobs over n_blobs handles into passes (frieda_prove_jobs_plan); ctx None:
+    the default options."""
+    per, n = C.c_uint32(0), C.c_uint32(0)
+    h = ctx._h if ctx is not None else None
+    _check(_lib.lib().frieda_prove_jobs_plan(h, length, pcs_config._c(), n_blobs, n_jobs, C.byref(per), C.byref(n)))
+    return int(per.value), int(n.value)
+
+
 def batch_plan(length, count, pcs_config=None, in_flight=2, prove=True, ctx=None, log_blowup_factor=None):
     """The library's batch policy (frieda_batch_plan, include/frieda_hip.h "batch policy"): the blob count of each call, in order, for
     `count` equal-length blobs and `in_flight` contexts taking turns.  pcs_config for proofs, log_blowup_factor for commits."""
@@ -1491,6 +1538,12 @@ def open_cells_blobs(ctx, encs, log_cell, blob_index, cell_index):
         ctx._h,
     )
     return values, paths
+
+
+def prove_jobs(ctx, encs, jobs, pcs_config):
+    """Any list of (blob_index, seed) jobs over a block of encoded blobs in ONE call (frieda_prove_jobs on `ctx`): a flat list of Proof
+    in the caller's order."""
+    return ctx.prove_jobs(encs, jobs, pcs_config)
 
 
 def prove_seeds_blobs(ctx, encs, seeds, pcs_config):

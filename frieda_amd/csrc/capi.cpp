@@ -8,6 +8,7 @@
 #include <new>
 
 #include "host.h"
+#include "prove_jobs_plan.h"
 #include "../../include/frieda_hip_testing.h"
 
 using namespace frieda;
@@ -589,6 +590,100 @@ size_t frieda_seeds_blobs_workspace_bytes(size_t len, frieda_pcs_config cfg, uin
         return seeds_blobs_workspace_bytes(len, cfg, n_blobs, n_seeds);
     } catch (...) {
         return 0;
+    }
+}
+
+// ---- any list of (handle, seed) jobs ----
+namespace {
+// the handles as the host code takes them; FRIEDA_ERR_ARG for what cannot be a list at all
+int jobs_handles(frieda_ctx* ctx, const frieda_encoded* const* encs, uint32_t n_blobs, std::vector<const Encoded*>& es) {
+    if (!encs) return ctx->c.fail(FRIEDA_ERR_ARG, "null list of encoded blobs");
+    if (n_blobs == 0) return ctx->c.fail(FRIEDA_ERR_ARG, "n_blobs or n_jobs is 0");
+    es.resize(n_blobs);
+    for (uint32_t b = 0; b < n_blobs; b++) es[b] = encs[b] ? &encs[b]->e : nullptr;
+    return FRIEDA_OK;
+}
+}  // namespace
+
+int frieda_prove_jobs_begin(frieda_ctx* ctx, const frieda_encoded* const* encs, uint32_t n_blobs, const uint32_t* blob_index, const uint64_t* seeds,
+                            uint32_t n_jobs, frieda_pcs_config cfg) {
+    if (!ctx) return FRIEDA_ERR_ARG;
+    FR_GUARD_BEGIN
+    std::vector<const Encoded*> es;
+    int rc = jobs_handles(ctx, encs, n_blobs, es);
+    return rc != FRIEDA_OK ? rc : prove_jobs_begin(&ctx->c, es.data(), n_blobs, blob_index, seeds, n_jobs, cfg);
+    FR_GUARD_END(ctx)
+}
+// (a job is a job: see frieda_prove_seeds_blobs_finish; the proofs come back in the caller's order)
+int frieda_prove_jobs_finish(frieda_ctx* ctx, frieda_proof** out_proofs) { return frieda_prove_seeds_finish(ctx, out_proofs); }
+
+// The synchronous form: the sorted list cut into passes (prove_jobs_plan.h), every pass one _pass_begin and the one finish; a pass the
+// device cannot hold halves the passes that follow
+int frieda_prove_jobs(frieda_ctx* ctx, const frieda_encoded* const* encs, uint32_t n_blobs, const uint32_t* blob_index, const uint64_t* seeds,
+                      uint32_t n_jobs, frieda_pcs_config cfg, frieda_proof** out_proofs) {
+    if (!ctx || !out_proofs) return FRIEDA_ERR_ARG;
+    for (uint32_t j = 0; j < n_jobs; j++) out_proofs[j] = nullptr;
+    FR_GUARD_BEGIN
+    std::vector<const Encoded*> es;
+    int rc = jobs_handles(ctx, encs, n_blobs, es);
+    if (rc == FRIEDA_OK) rc = prove_jobs_check(&ctx->c, es.data(), n_blobs, blob_index, seeds, n_jobs, cfg);
+    if (rc != FRIEDA_OK) return rc;
+    std::vector<uint32_t> order, sorted_blob;
+    std::vector<uint64_t> sorted_seeds;
+    prove_jobs_sorted(blob_index, seeds, n_jobs, n_blobs, order, sorted_blob, sorted_seeds);
+    uint32_t per_pass = prove_jobs_per_pass_under(es[0]->len, cfg, n_blobs, n_jobs, prove_jobs_limit(ctx->c.tuning));
+    std::vector<frieda_proof*> pass;
+    auto give_up = [&](int status) {
+        for (uint32_t j = 0; j < n_jobs; j++) {
+            frieda_proof_free(out_proofs[j]);
+            out_proofs[j] = nullptr;
+        }
+        return status;
+    };
+    uint64_t done = 0;
+    while (done < n_jobs) {
+        const uint64_t left = n_jobs - done, n_passes = prove_jobs_n_passes(left, per_pass);
+        for (uint64_t i = 0; i < n_passes; i++) {
+            const uint32_t np = prove_jobs_pass_size(left, n_passes, i);
+            const uint32_t* pb = sorted_blob.data() + done;
+            uint32_t distinct = 1;
+            for (uint32_t y = 1; y < np; y++) distinct += pb[y] != pb[y - 1];
+            pass.assign(np, nullptr);
+            rc = prove_jobs_pass_begin(&ctx->c, es.data(), pb, sorted_seeds.data() + done, np, distinct, nullptr, cfg);
+            if (rc == FRIEDA_OK) rc = frieda_prove_seeds_finish(ctx, pass.data());
+            if (rc == FRIEDA_ERR_NOMEM && per_pass > 1 && np > 1) {
+                per_pass = std::max<uint32_t>(1, std::min(per_pass, np) / 2);
+                break;  // (the passes are cut again over what is left)
+            }
+            if (rc != FRIEDA_OK) return give_up(rc);
+            for (uint32_t y = 0; y < np; y++) out_proofs[order[done + y]] = pass[y];
+            done += np;
+        }
+    }
+    return FRIEDA_OK;
+    FR_GUARD_END(ctx)
+}
+
+size_t frieda_prove_jobs_workspace_bytes(size_t len, frieda_pcs_config cfg, uint32_t n_blobs, uint32_t n_jobs) {
+    try {
+        return prove_jobs_workspace_bytes(len, cfg, n_blobs, n_jobs);
+    } catch (...) {
+        return 0;
+    }
+}
+
+int frieda_prove_jobs_plan(const frieda_ctx* ctx, size_t len, frieda_pcs_config cfg, uint32_t n_blobs, uint32_t n_jobs, uint32_t* jobs_per_pass,
+                           uint32_t* n_passes) {
+    if (!jobs_per_pass || !n_passes) return FRIEDA_ERR_ARG;
+    *jobs_per_pass = *n_passes = 0;
+    try {
+        const uint32_t per = prove_jobs_per_pass_under(len, cfg, n_blobs, n_jobs, prove_jobs_limit(ctx ? ctx->c.tuning : k::tuning_defaults()));
+        if (!per) return FRIEDA_ERR_ARG;
+        *jobs_per_pass = per;
+        *n_passes = (uint32_t)prove_jobs_n_passes(n_jobs, per);
+        return FRIEDA_OK;
+    } catch (...) {
+        return FRIEDA_ERR_NOMEM;
     }
 }
 

@@ -275,6 +275,22 @@ size_t seeds_workspace_bytes(size_t len, frieda_pcs_config cfg, uint32_t n_seeds
 // seeds[s].  Finished by prove_finish_batch like every batch.  The handles are only read.
 int prove_seeds_blobs_begin(Ctx* ctx, const Encoded* const* encs, uint32_t n_blobs, const uint64_t* seeds, uint32_t n_seeds, frieda_pcs_config cfg);
 size_t seeds_blobs_workspace_bytes(size_t len, frieda_pcs_config cfg, uint32_t n_blobs, uint32_t n_seeds);
+// Any list of (handle, seed) jobs over encoded blobs of one shape (frieda_prove_jobs; prove_jobs_plan.h): job j = encs[blob_index[j]]
+// under seeds[j].  The jobs run sorted by blob — the rectangle above is the list that is sorted as it stands — and the one finish writes
+// proof j to the caller's slot j.  _check: the argument rules of a whole call; _pass_begin: `n` <= 65535 SORTED jobs in one launch chain,
+// the table holding the distinct blobs they name and the arena planned for plan_blobs rows (1: prove_seeds), proof y to out_slot[y]
+// (null: y); _begin: check, sort, one pass of everything planned for n_blobs rows.
+int prove_jobs_check(Ctx* ctx, const Encoded* const* encs, uint32_t n_blobs, const uint32_t* blob_index, const uint64_t* seeds, uint64_t n_jobs, frieda_pcs_config cfg);
+void prove_jobs_sorted(const uint32_t* blob_index, const uint64_t* seeds, size_t n_jobs, uint32_t n_blobs, std::vector<uint32_t>& order,
+                       std::vector<uint32_t>& sorted_blob, std::vector<uint64_t>& sorted_seeds);
+int prove_jobs_pass_begin(Ctx* ctx, const Encoded* const* encs, const uint32_t* sorted_blob, const uint64_t* sorted_seeds, uint32_t n, uint32_t plan_blobs,
+                          const uint32_t* out_slot, frieda_pcs_config cfg);
+int prove_jobs_begin(Ctx* ctx, const Encoded* const* encs, uint32_t n_blobs, const uint32_t* blob_index, const uint64_t* seeds, uint32_t n_jobs, frieda_pcs_config cfg);
+size_t prove_jobs_workspace_bytes(size_t len, frieda_pcs_config cfg, uint32_t n_blobs, uint32_t n_jobs);
+// the most jobs a pass takes under `limit` bytes (0: a refused shape), and the limit of a context: the batch policy's budget, or the
+// test hook's arena limit when that is smaller
+uint32_t prove_jobs_per_pass_under(size_t len, frieda_pcs_config cfg, uint32_t n_blobs, uint64_t n_jobs, uint64_t limit);
+uint64_t prove_jobs_limit(const k::Tuning& t);
 int commit_batch(Ctx* ctx, const uint8_t* data, size_t data_stride, size_t len, uint32_t count, bool data_on_device, uint32_t log_blowup,
                  uint8_t* out_roots, const uint8_t* const* host_ptrs = nullptr);
 // split form (frieda_commit_many alternates two contexts: the upload of one unit runs under the kernels of the other): _begin

@@ -316,10 +316,11 @@ void small_encode_and_first_tree(const Launch& L, const uint8_t* d_data, size_t 
 void encode_and_first_tree(const Launch& L, const uint32_t* d_coef, size_t coef_stride, uint32_t Lc, uint32_t n, const uint32_t* d_tw,
                            DomainScalars ds, uint32_t* d_eval, size_t eval_stride, uint8_t* d_layers, uint8_t* d_scratch, uint8_t* d_root,
                            DevTranscript* tr, const DevTranscript* tr_init = nullptr, size_t tr_init_pitch = 0, const BlobSource* blob = nullptr);
-// A block of encoded blobs proved under one seed list in one call (frieda_prove_seeds_blobs): job y = blob y / n_seeds under seed
-// y % n_seeds.  Everything a job reads of its first layer comes from its blob's row, found through job_row[y] (no division in the kernels;
-// y is workgroup-uniform, so the lookup is scalar loads).  The seed-looped kernel's workgroup y serves the jobs
-// [group_first[y], min(group_first[y] + group, end of that blob's jobs)): a group never straddles two blobs.
+// Jobs over a block of encoded blobs in one call (frieda_prove_jobs; frieda_prove_seeds_blobs is its rectangle): the jobs are sorted by
+// blob, job y is row job_row[y] under its own seed.  Everything a job reads of its first layer comes from its blob's row, found through
+// job_row[y] (no division in the kernels; y is workgroup-uniform, so the lookup is scalar loads).  The seed-looped kernel's workgroup y
+// serves the jobs of groups[y]: first job in the low 16 bits, job count in the high 16 (a launch has at most 65535 jobs); a group holds
+// at most FRIEDA_SEEDS_FOLD_GROUP consecutive jobs of ONE blob (prove_jobs_plan.h).
 struct SeedsBlobRow {
     const uint32_t* eval;  // 4 columns of 2^n words
     const uint8_t* tree;   // the first-layer tree (leaves-first), built with THIS blob's threshold
@@ -329,9 +330,9 @@ struct SeedsBlobRow {
 };
 struct SeedsBlock {
     const SeedsBlobRow* table = nullptr;  // n_blobs rows, all of one domain; null: not a block job
-    const uint32_t* job_row = nullptr;    // n_blobs * n_seeds row numbers
-    const uint32_t* group_first = nullptr;  // n_blobs * ceil(n_seeds / group) first jobs (seeds_group > 0 only)
-    uint32_t n_blobs = 0, n_seeds = 0;      // (host side: the launch shapes)
+    const uint32_t* job_row = nullptr;    // a row number per job
+    const uint32_t* groups = nullptr;     // n_groups entries (seeds_group > 0 only)
+    uint32_t n_blobs = 0, n_groups = 0;   // (host side: the launch shapes)
 };
 // fold the layer `src` (log size src_log; circle evaluation or line layer) with the alpha in tr into dst_vals and build the
 // tree of the folded layer in the same launches (leaf hashes not written, as above); finishes with the channel step

@@ -21,6 +21,7 @@
 
 #include "dev_transcript.h"
 #include "host.h"
+#include "prove_jobs_plan.h"
 
 namespace frieda {
 
@@ -400,26 +401,31 @@ size_t opening_max_hashes(uint32_t n_queries, uint32_t n, uint32_t n_inner, bool
 
 namespace {
 // What the jobs of a prove call are.  PLAIN: `count` blobs.  SEEDS (prove_seeds): `count` seeds of ONE encoded blob, enc.  BLOCK
-// (prove_seeds_blobs): n_blobs * n_seeds jobs, blob-major (job y = block[y / n_seeds] under seed y % n_seeds); enc = block[0] stands for the shape
+// (prove_jobs, and prove_seeds_blobs as its rectangle): `count` jobs sorted by blob, one seed each, over the n_blobs rows of `block`
+// (prove_jobs_plan.h: job y is row job_row[y], row r's jobs are [row_first[r], row_first[r + 1])); enc = block[0] stands for the shape
 struct ProveForm {
     enum Kind { PLAIN, SEEDS, BLOCK } kind = PLAIN;
     const Encoded* enc = nullptr;
     const Encoded* const* block = nullptr;
     uint32_t n_blobs = 0;
-    uint32_t fold_group = 1;  // BLOCK: FRIEDA_SEEDS_FOLD_GROUP of the call (0: route A), for the table as staged; the sizing functions know no context
+    uint32_t plan_blobs = 0;  // the rows the ARENA is planned for, >= n_blobs (frieda_prove_jobs_begin sizes by the handles it was given)
+    const uint32_t* job_row = nullptr;
+    const uint32_t* row_first = nullptr;
+    const uint32_t* groups = nullptr;  // the seed-looped fold's group entries as staged, n_groups of them (route A: none); the sizing
+    uint32_t n_groups = 0;             // functions know no context and plan the arena for the most a list can have, one per job
+    const uint32_t* out_slot = nullptr;  // null: proof y goes to slot y
 };
 
-// the block table of a prove_seeds_blobs call, as the arena and the pinned staging hold it: rows, one row number per job, and (route B)
-// the first job of every seed group
+// the block table of a BLOCK call, as the arena and the pinned staging hold it: rows, one row number per job, and (route B) an entry
+// per group of jobs
 struct BlockTablePlan {
     size_t o_job = 0, o_group = 0, bytes = 0;
-    uint32_t group = 0, groups = 0;  // seeds per group (0: no group part), groups in all
+    uint32_t groups = 0;  // (0: no group part)
     BlockTablePlan() = default;
-    BlockTablePlan(uint32_t n_blobs, uint32_t n_seeds, uint32_t group_) : group(group_) {
+    BlockTablePlan(uint32_t n_blobs, uint32_t n_jobs, uint32_t n_groups) : groups(n_groups) {
         ArenaPlan p;
         p.take(sizeof(k::SeedsBlobRow) * n_blobs);
-        o_job = p.take(sizeof(uint32_t) * (size_t)n_blobs * n_seeds);
-        groups = group ? n_blobs * ((n_seeds + group - 1) / group) : 0;
+        o_job = p.take(sizeof(uint32_t) * (size_t)n_jobs);
         o_group = p.take(sizeof(uint32_t) * groups);
         bytes = p.off;
     }
@@ -482,11 +488,10 @@ ProveLayout prove_layout(const Shape& sh, const frieda_pcs_config& cfg, uint32_t
     y.o_wout = plan.take(4 * y.max_words);
     y.o_hout = plan.take(32 * y.max_hashes);
     if (form.kind == ProveForm::BLOCK) {
-        const uint32_t n_seeds = count / form.n_blobs;
-        y.table = BlockTablePlan(form.n_blobs, n_seeds, form.fold_group);
-        // (the table's group part is planned for the largest group count, group 1, whatever FRIEDA_SEEDS_FOLD_GROUP says: the workspace of a
-        // call is a function of its shape alone)
-        y.o_blk = plan.take(BlockTablePlan(form.n_blobs, n_seeds, 1).bytes);
+        y.table = BlockTablePlan(form.n_blobs, count, form.n_groups);
+        // (the table's group part is planned for the largest group count, a group per job, whatever FRIEDA_SEEDS_FOLD_GROUP and the list
+        // say: the workspace of a call is a function of its shape alone)
+        y.o_blk = plan.take(BlockTablePlan(form.plan_blobs, count, count).bytes);
     }
     y.arena_bytes = plan.off;
     y.tr_host_pitch = (offsetof(DevTranscript, last_poly) + ((size_t)16 << last) + 63) & ~(size_t)63;
@@ -522,11 +527,12 @@ struct ProveJob {
     // and host-planner fallback — must use the same one even if frieda_ctx_set_option moved the knob between _begin and _finish
     uint32_t skip_log = 0;
     // SEEDS: layer 0 (values, tree) is enc's, at stride 0, with the threshold ITS tree was built with.  BLOCK: layer 0 of a job is its
-    // handle's, which the kernels find through the table `blk` points at (in the arena, uploaded by _begin)
+    // handle's, which the kernels find through the table `blk` points at (in the arena, uploaded by _begin); row r's jobs are
+    // [row_first[r], row_first[r + 1]); proof y is written to the caller's slot out_slot[y] (empty: slot y)
     const Encoded* enc = nullptr;
     uint32_t first_skip_log = 0;
     std::vector<const Encoded*> block;
-    uint32_t n_seeds = 0;
+    std::vector<uint32_t> row_first, out_slot;
     k::SeedsBlock blk{};
     struct Blob {
         Channel ch{};
@@ -663,25 +669,22 @@ static void launch_decommit(Ctx* ctx, const ProveJob& J) {
 }
 
 // ---- prove_begin: the pieces, in the order they run ----
-// BLOCK: the per-blob table, the row of every job and the first job of every seed group: one upload per call, ahead of every launch
-static int upload_block_table(Ctx* ctx, ProveJob& J) {
+// BLOCK: the per-blob table, the row of every job and the entry of every group of jobs: one upload per call, ahead of every launch
+static int upload_block_table(Ctx* ctx, ProveJob& J, const ProveForm& form) {
     const BlockTablePlan& T = J.lay.table;
-    const uint32_t n_block = (uint32_t)J.block.size(), n_seeds = J.n_seeds;
+    const uint32_t n_block = (uint32_t)J.block.size();
     uint8_t* hp = static_cast<uint8_t*>(ctx->pinned) + J.lay.pin_blk;
     k::SeedsBlobRow* rows = reinterpret_cast<k::SeedsBlobRow*>(hp);
-    uint32_t* job_row = reinterpret_cast<uint32_t*>(hp + T.o_job);
-    uint32_t* group_first = reinterpret_cast<uint32_t*>(hp + T.o_group);
-    const uint32_t gpb = T.group ? (n_seeds + T.group - 1) / T.group : 0;  // groups per blob: a short last one, none across two blobs
     for (uint32_t r = 0; r < n_block; r++) {
         const Encoded* e = J.block[r];
         rows[r] = k::SeedsBlobRow{e->eval(), e->tree(), e->d + e->o_root, e->skip_log, 0};
-        for (uint32_t sd = 0; sd < n_seeds; sd++) job_row[r * n_seeds + sd] = r;
-        for (uint32_t g = 0; g < gpb; g++) group_first[r * gpb + g] = r * n_seeds + g * T.group;
     }
+    memcpy(hp + T.o_job, form.job_row, sizeof(uint32_t) * J.count);
+    if (T.groups) memcpy(hp + T.o_group, form.groups, sizeof(uint32_t) * T.groups);
     uint8_t* d_blk = ctx->arena + J.lay.o_blk;
     FR_HIP(ctx, hipMemcpyAsync(d_blk, hp, T.bytes, hipMemcpyHostToDevice, ctx->stream));
     J.blk = k::SeedsBlock{reinterpret_cast<const k::SeedsBlobRow*>(d_blk), reinterpret_cast<const uint32_t*>(d_blk + T.o_job),
-                          T.group ? reinterpret_cast<const uint32_t*>(d_blk + T.o_group) : nullptr, n_block, n_seeds};
+                          T.groups ? reinterpret_cast<const uint32_t*>(d_blk + T.o_group) : nullptr, n_block, T.groups};
     return FRIEDA_OK;
 }
 
@@ -691,7 +694,7 @@ static void init_transcripts(Ctx* ctx, ProveJob& J, const uint64_t* seeds) {
     for (uint32_t b = 0; b < J.count; b++) {
         ProveJob::Blob& bl = J.blobs[b];
         bl.ch.init();
-        if (seeds) bl.ch.mix_u64(seeds[J.block.empty() ? b : b % J.n_seeds]);  // src/proof.rs:40-42
+        if (seeds) bl.ch.mix_u64(seeds[b]);  // src/proof.rs:40-42
         bl.roots.assign(1 + J.lay.n_inner, Hash32{});
         if (!J.dev_channel) continue;
         DevTranscript* ht = reinterpret_cast<DevTranscript*>(static_cast<uint8_t*>(ctx->pinned) + b * J.lay.tr_host_pitch);
@@ -857,7 +860,7 @@ static int run_host_channel(Ctx* ctx, ProveJob& J, const TwiddleSet& tw) {
     return FRIEDA_OK;
 }
 
-// `count` jobs of one shape (ProveForm); seeds: null or one per blob (PLAIN), one per job (SEEDS), the n_seeds of the one list (BLOCK)
+// `count` jobs of one shape (ProveForm); seeds: null or one per blob (PLAIN), one per job (SEEDS, BLOCK)
 static int prove_begin_impl(Ctx* ctx, const BlobsIn& in, uint32_t count, const uint64_t* seeds, frieda_pcs_config cfg, ProveForm form) {
     const auto t_entry = std::chrono::steady_clock::now();
     FR_NO_JOB(ctx);  // a proof or a commit batch in flight owns the arena and the pinned block
@@ -876,8 +879,8 @@ static int prove_begin_impl(Ctx* ctx, const BlobsIn& in, uint32_t count, const u
     J.first_skip_log = form.enc ? form.enc->skip_log : J.skip_log;
     if (form.kind == ProveForm::BLOCK) {
         J.block.assign(form.block, form.block + form.n_blobs);
-        J.n_seeds = count / form.n_blobs;
-        form.fold_group = ctx->tuning.seeds_fold_group;
+        J.row_first.assign(form.row_first, form.row_first + form.n_blobs + 1);
+        if (form.out_slot) J.out_slot.assign(form.out_slot, form.out_slot + count);
     }
     J.blobs.resize(count);
     J.lay = prove_layout(J.sh, cfg, count, in.on_device ? 0 : in.len, form);
@@ -909,7 +912,7 @@ static int prove_begin_impl(Ctx* ctx, const BlobsIn& in, uint32_t count, const u
         k::unpack30(J.launch(ctx), blob.bytes, blob.len, reinterpret_cast<uint32_t*>(ctx->arena + J.lay.o_coef), J.sh.cs.n_padded, blob.bstride);
     ctx->phase_ms[5] = ms_since(t_entry);  // set-up before the first launch (workspace plan, twiddle lookup, ...) + that launch call
     init_transcripts(ctx, J, seeds);
-    if (form.kind == ProveForm::BLOCK) rc = upload_block_table(ctx, J);
+    if (form.kind == ProveForm::BLOCK) rc = upload_block_table(ctx, J, form);
     if (rc == FRIEDA_OK) rc = J.dev_channel ? enqueue_device_channel(ctx, J, tw, blob) : run_host_channel(ctx, J, tw);
     if (rc) return rc;
     ctx->job = std::move(jp);
@@ -954,7 +957,78 @@ int prove_seeds_blobs_begin(Ctx* ctx, const Encoded* const* encs, uint32_t n_blo
     }
     if (cfg.log_blowup_factor != encs[0]->log_blowup) return ctx->fail(FRIEDA_ERR_ARG, "log_blowup_factor differs from the one the blobs were encoded with");
     if (n_blobs == 1) return prove_seeds_begin(ctx, encs[0], seeds, n_seeds, cfg);
-    return prove_begin_impl(ctx, BlobsIn{nullptr, 0, encs[0]->len, true, nullptr}, n_blobs * n_seeds, seeds, cfg, ProveForm{ProveForm::BLOCK, encs[0], encs, n_blobs});
+    // the rectangle is the list that names every blob under every seed, blob-major: sorted as it stands
+    const uint32_t n_jobs = n_blobs * n_seeds;
+    std::vector<uint32_t> blob_of(n_jobs);
+    std::vector<uint64_t> seed_of(n_jobs);
+    for (uint32_t y = 0; y < n_jobs; y++) blob_of[y] = y / n_seeds, seed_of[y] = seeds[y % n_seeds];
+    return prove_jobs_pass_begin(ctx, encs, blob_of.data(), seed_of.data(), n_jobs, n_blobs, nullptr, cfg);
+}
+
+// The list form: `n` jobs sorted by blob (sorted_blob[y] indexes encs and does not decrease), job y under sorted_seeds[y], in one launch
+// chain.  The table holds the distinct blobs of the list; plan_blobs >= that many: the rows the arena is sized for.  One row planned is
+// prove_seeds itself.  Every handle named was checked by the caller (prove_jobs_check, prove_seeds_blobs_begin)
+int prove_jobs_pass_begin(Ctx* ctx, const Encoded* const* encs, const uint32_t* sorted_blob, const uint64_t* sorted_seeds, uint32_t n, uint32_t plan_blobs,
+                          const uint32_t* out_slot, frieda_pcs_config cfg) {
+    if (n == 0 || n > PROVE_JOBS_PASS_MAX) return ctx->fail(FRIEDA_ERR_ARG, "n_jobs out of range");
+    if (plan_blobs == 1) return prove_seeds_begin(ctx, encs[sorted_blob[0]], sorted_seeds, n, cfg);  // (one blob: the stable sort moved nothing)
+    ProveJobsRows rows;
+    prove_jobs_rows(sorted_blob, n, rows);
+    std::vector<const Encoded*> block(rows.blobs.size());
+    for (size_t r = 0; r < block.size(); r++) block[r] = encs[rows.blobs[r]];
+    std::vector<uint32_t> groups;
+    prove_jobs_groups(rows.row_first, ctx->tuning.seeds_fold_group, groups);
+    ProveForm form{ProveForm::BLOCK, block[0], block.data(), (uint32_t)block.size()};
+    form.plan_blobs = std::max(plan_blobs, form.n_blobs);
+    form.job_row = rows.job_row.data();
+    form.row_first = rows.row_first.data();
+    form.groups = groups.data();
+    form.n_groups = (uint32_t)groups.size();
+    form.out_slot = out_slot;
+    return prove_begin_impl(ctx, BlobsIn{nullptr, 0, block[0]->len, true, nullptr}, n, sorted_seeds, cfg, form);
+}
+
+// the argument rules of a prove_jobs call, whole (a call cut into passes refuses what it refuses before its first pass)
+int prove_jobs_check(Ctx* ctx, const Encoded* const* encs, uint32_t n_blobs, const uint32_t* blob_index, const uint64_t* seeds, uint64_t n_jobs, frieda_pcs_config cfg) {
+    FR_NO_JOB(ctx);
+    if (!encs) return ctx->fail(FRIEDA_ERR_ARG, "null list of encoded blobs");
+    if (!blob_index) return ctx->fail(FRIEDA_ERR_ARG, "null blob_index");
+    if (!seeds) return ctx->fail(FRIEDA_ERR_ARG, "null seeds");
+    if (n_blobs == 0 || n_jobs == 0) return ctx->fail(FRIEDA_ERR_ARG, "n_blobs or n_jobs is 0");
+    for (uint32_t b = 0; b < n_blobs; b++) {
+        if (!encs[b] || !encs[b]->d) return ctx->fail(FRIEDA_ERR_ARG, "null encoded blob");
+        if (encs[b]->len != encs[0]->len || encs[b]->log_blowup != encs[0]->log_blowup) return ctx->fail(FRIEDA_ERR_ARG, "the encoded blobs of a block have one length and one blowup");
+        if (encs[b]->device != ctx->device) return ctx->fail(FRIEDA_ERR_ARG, "the encoded blob lives on another device");
+    }
+    if (cfg.log_blowup_factor != encs[0]->log_blowup) return ctx->fail(FRIEDA_ERR_ARG, "log_blowup_factor differs from the one the blobs were encoded with");
+    for (uint64_t j = 0; j < n_jobs; j++)
+        if (blob_index[j] >= n_blobs) return ctx->fail(FRIEDA_ERR_ARG, "blob_index out of range");
+    Shape sh;
+    const Refusal refused = check_prove(encs[0]->len, cfg, sh);
+    if (refused.code) return ctx->fail(refused.code, refused.text);
+    if (n_jobs > 1 && (cfg.log_last_layer_degree_bound + cfg.log_blowup_factor > k::TAIL_LOG || ctx->host_channel))
+        return ctx->fail(FRIEDA_ERR_ARG, "batches need the device channel (last layer <= 2^11 points, host channel policy off)");
+    return FRIEDA_OK;
+}
+
+// the list sorted (prove_jobs_plan.h): order, and the blob and the seed of every sorted job
+void prove_jobs_sorted(const uint32_t* blob_index, const uint64_t* seeds, size_t n_jobs, uint32_t n_blobs, std::vector<uint32_t>& order,
+                       std::vector<uint32_t>& sorted_blob, std::vector<uint64_t>& sorted_seeds) {
+    prove_jobs_sort(blob_index, n_jobs, n_blobs, order);
+    sorted_blob.resize(n_jobs);
+    sorted_seeds.resize(n_jobs);
+    for (size_t y = 0; y < n_jobs; y++) sorted_blob[y] = blob_index[order[y]], sorted_seeds[y] = seeds[order[y]];
+}
+
+// one pass of everything, sized by the handles given (frieda_prove_jobs_workspace_bytes); the finish writes the caller's order
+int prove_jobs_begin(Ctx* ctx, const Encoded* const* encs, uint32_t n_blobs, const uint32_t* blob_index, const uint64_t* seeds, uint32_t n_jobs, frieda_pcs_config cfg) {
+    int rc = prove_jobs_check(ctx, encs, n_blobs, blob_index, seeds, n_jobs, cfg);
+    if (rc) return rc;
+    if (n_jobs > PROVE_JOBS_PASS_MAX) return ctx->fail(FRIEDA_ERR_ARG, "n_jobs out of range");
+    std::vector<uint32_t> order, sorted_blob;
+    std::vector<uint64_t> sorted_seeds;
+    prove_jobs_sorted(blob_index, seeds, n_jobs, n_blobs, order, sorted_blob, sorted_seeds);
+    return prove_jobs_pass_begin(ctx, encs, sorted_blob.data(), sorted_seeds.data(), n_jobs, n_blobs, order.data(), cfg);
 }
 
 int prove_finish(Ctx* ctx, uint8_t out_commitment[32], ProofData& out) {
@@ -1065,10 +1139,12 @@ int host_decommit(Ctx* ctx, ProveJob& J, Openings& op) {
     const ProveLayout& Y = J.lay;
     const uint32_t n = J.sh.n, n_inner = J.lay.n_inner, count = J.count;
     const size_t N = J.sh.N;
-    // the rows of first layers the jobs read: none (the arena's own), the handle, or the block's; job y reads row y / row_jobs
+    // the rows of first layers the jobs read: none (the arena's own), the handle, or the block's; row r's jobs are [row_first[r], row_first[r + 1])
     const Encoded* const one_row[1] = {J.enc};
+    const uint32_t one_first[2] = {0, count};
     const Encoded* const* rows = J.block.empty() ? one_row : J.block.data();
-    const size_t n_rows = J.block.empty() ? (J.enc ? 1 : 0) : J.block.size(), row_jobs = J.block.empty() ? count : J.n_seeds;
+    const uint32_t* row_first = J.block.empty() ? one_first : J.row_first.data();
+    const size_t n_rows = J.block.empty() ? (J.enc ? 1 : 0) : J.block.size();
     // one complete copy per DISTINCT blob that needs one (a handle may be listed more than once), freed when the call leaves, by whichever path
     std::vector<DevBuf> row_full(n_rows);
     std::vector<const uint8_t*> row_tree(n_rows, nullptr);
@@ -1164,7 +1240,8 @@ int host_decommit(Ctx* ctx, ProveJob& J, Openings& op) {
     auto gather_all = [&](const uint64_t* widx, uint32_t* wout, const uint64_t* hidx_, uint8_t* hout) {
         if (!n_rows) k::gather(L1, reinterpret_cast<const uint32_t*>(A), widx, nw, wout, hidx_, nh, hout, nullptr, nullptr);
         for (size_t r = 0; r < n_rows; r++) {
-            const size_t j0 = r * row_jobs, j1 = j0 + row_jobs;
+            const size_t j0 = row_first[r], j1 = row_first[r + 1];
+            if (j0 == j1) continue;
             const size_t w0 = w_begin[j0], w1 = j1 < count ? w_begin[j1] : nw, h0 = h_begin[j0], h1 = j1 < count ? h_begin[j1] : nh;
             k::gather(L1, reinterpret_cast<const uint32_t*>(A), widx + w0, w1 - w0, wout + w0, hidx_ + h0, h1 - h0, hout + 32 * h0, rows[r]->eval(), row_tree[r]);
         }
@@ -1197,7 +1274,8 @@ void assemble_proofs(ProveJob& J, const Openings& op, uint8_t* out_commitments, 
     if (outs.size() != count) outs.assign(count, ProofData{});  // else: the caller's (recycled) objects, every field rewritten below
     for (uint32_t b = 0; b < count; b++) {
         ProveJob::Blob& bl = J.blobs[b];
-        ProofData& out = outs[b];
+        const size_t slot = J.out_slot.empty() ? b : J.out_slot[b];
+        ProofData& out = outs[slot];
         const Openings::LayerCounts* cnt = &op.counts[(size_t)b * (1 + n_inner)];
         const uint32_t* wv = op.words_of[b];
         const uint8_t* hv = op.hashes_of[b];
@@ -1224,7 +1302,7 @@ void assemble_proofs(ProveJob& J, const Openings& op, uint8_t* out_commitments, 
             hi += cnt[li].n_hashes;
             lp.column_witness.clear();
         }
-        memcpy(out_commitments + 32 * (size_t)b, bl.roots[0].data(), 32);
+        memcpy(out_commitments + 32 * slot, bl.roots[0].data(), 32);
     }
 }
 }  // namespace
@@ -1461,11 +1539,30 @@ size_t seeds_workspace_bytes(size_t len, frieda_pcs_config cfg, uint32_t n_seeds
 }
 
 // ... and for a prove_seeds_blobs job: the same plan at n_blobs * n_seeds jobs, then the block table (rows, a row number per job, the
-// first job of every seed group at its largest count).  One blob is prove_seeds, table and all
+// entry of every group of jobs at their largest count).  One blob is prove_seeds, table and all
 size_t seeds_blobs_workspace_bytes(size_t len, frieda_pcs_config cfg, uint32_t n_blobs, uint32_t n_seeds) {
     if (n_blobs == 0 || n_seeds == 0 || (uint64_t)n_blobs * n_seeds > 65535) return 0;
     if (n_blobs == 1) return seeds_workspace_bytes(len, cfg, n_seeds);
-    return prove_arena_bytes(len, cfg, n_blobs * n_seeds, ProveForm{ProveForm::BLOCK, nullptr, nullptr, n_blobs});
+    return prove_jobs_workspace_bytes(len, cfg, n_blobs, n_blobs * n_seeds);
+}
+
+// ... and for a pass of prove_jobs: a function of the two counts alone (the rectangle K x S is the list (K, K * S))
+size_t prove_jobs_workspace_bytes(size_t len, frieda_pcs_config cfg, uint32_t n_blobs, uint32_t n_jobs) {
+    if (n_blobs == 0 || n_jobs == 0 || n_jobs > PROVE_JOBS_PASS_MAX) return 0;
+    if (n_blobs == 1) return seeds_workspace_bytes(len, cfg, n_jobs);
+    ProveForm form{ProveForm::BLOCK, nullptr, nullptr, n_blobs};
+    form.plan_blobs = n_blobs;
+    return prove_arena_bytes(len, cfg, n_jobs, form);
+}
+
+// the pass rule of frieda_prove_jobs (prove_jobs_plan.h) under `limit` bytes; 0: a refused shape
+uint32_t prove_jobs_per_pass_under(size_t len, frieda_pcs_config cfg, uint32_t n_blobs, uint64_t n_jobs, uint64_t limit) {
+    if (!prove_jobs_workspace_bytes(len, cfg, 1, 1) || n_blobs == 0 || n_jobs == 0) return 0;
+    return prove_jobs_per_pass(n_jobs, n_blobs, limit, [&](uint32_t kb, uint32_t p) { return prove_jobs_workspace_bytes(len, cfg, kb, p); });
+}
+uint64_t prove_jobs_limit(const k::Tuning& t) {
+    const uint64_t budget = batch_budget_bytes(t);
+    return t.test_arena_limit && t.test_arena_limit < budget ? t.test_arena_limit : budget;
 }
 
 }  // namespace frieda

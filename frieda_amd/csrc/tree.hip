@@ -109,11 +109,10 @@ struct TreeArgs {
     size_t bstride;           // batch: bytes between consecutive blobs' workspaces (blob = blockIdx.y); tr is an array
     int shared_src;           // FOLD, prove_seeds: `cols` is the one encoded blob every blob (= seed) of the launch folds — no batch stride
     // FOLD with shared_src, prove_seeds_blobs (blk_table non-null): job y folds the evaluation of row blk_job[y] of the block's table;
-    // blk_group (the seed-looped kernel): the first job of workgroup row y, blk_seeds: seeds per blob
+    // blk_group (the seed-looped kernel): the jobs of workgroup row y, first job in the low 16 bits and job count in the high 16
     const SeedsBlobRow* blk_table;
     const uint32_t* blk_job;
     const uint32_t* blk_group;
-    uint32_t blk_seeds;
 };
 
 // the arguments of the blob this workgroup works on
@@ -363,15 +362,15 @@ __global__ __launch_bounds__(T5_THREADS) void tree5rs_fold_circle_kernel(TreeArg
     const uint32_t t = threadIdx.x;
     const size_t wg_base = (size_t)blockIdx.x * 1024;  // the launcher guarantees 2^level_a >= 1024
     const size_t g0 = wg_base + 4 * t;
-    // one blob: n_seeds jobs; a block: the jobs of this group's blob end at (row + 1) * blk_seeds (all uniform: scalar loads)
-    uint32_t seed0 = blockIdx.y * group, job_end = n_seeds;
+    // one blob: n_seeds jobs cut into groups of `group`; a block: the group's entry holds its first job and its length, and every job
+    // of a group is of one blob (all uniform: scalar loads)
+    uint32_t seed0 = blockIdx.y * group, seed1 = seed0 + group < n_seeds ? seed0 + group : n_seeds;
     if (a.blk_table) {
-        seed0 = a.blk_group[blockIdx.y];
-        const uint32_t row = a.blk_job[seed0];
-        job_end = (row + 1) * a.blk_seeds;
-        a.cols = a.blk_table[row].eval;
+        const uint32_t entry = a.blk_group[blockIdx.y];
+        seed0 = entry & 0xFFFFu;
+        seed1 = seed0 + (entry >> 16);
+        a.cols = a.blk_table[a.blk_job[seed0]].eval;
     }
-    const uint32_t seed1 = seed0 + group < job_end ? seed0 + group : job_end;
     if (TP) tree_prologue_priority();
     uint32_t f0[4][4], e[4][4];  // [pair][coordinate]
     {
@@ -1476,7 +1475,8 @@ void finish_tree(const Launch& L, const TreeArgs& a, uint32_t m, uint32_t cur, c
 // Builds the tree of a layer whose level A is produced by `mode`; finishes with the root (and the channel step when tr).
 // `layers` non-null = keep every level (leaves-first); else only the root survives and `scratch` (>= 2 * 32 * 2^(m-4) B) is used.
 void build_tree(const Launch& L, int mode, TreeArgs a, uint32_t m, uint8_t* layers, uint8_t* scratch, uint8_t* root_out,
-                DevTranscript* tr, const DevTranscript* tr_init = nullptr, size_t tr_init_pitch = 0, uint32_t seeds_group = 0) {
+                DevTranscript* tr, const DevTranscript* tr_init = nullptr, size_t tr_init_pitch = 0, uint32_t seeds_group = 0,
+                uint32_t blk_groups = 0) {
     a.level_a = m;
     a.tree_log = m;
     a.layers = layers;
@@ -1497,8 +1497,8 @@ void build_tree(const Launch& L, int mode, TreeArgs a, uint32_t m, uint8_t* laye
     // level kept, leaf hashes unwritten, 16-byte accesses; any other shape takes route A's kernel, which gives the same words
     if (seeds_group && mode == T_FOLD_CIRCLE && a.shared_src && a.store_all && a.skip_a &&
         tree_kernel_for(*L.tune, a.level_a, L.batch, tree_args_aligned16(a), true) == T_WIDE) {
-        // (a block: every blob's seeds are cut into groups of their own; a.blk_group has one entry per workgroup row)
-        const uint32_t groups = a.blk_table ? (L.batch / a.blk_seeds) * ((a.blk_seeds + seeds_group - 1) / seeds_group) : (L.batch + seeds_group - 1) / seeds_group;
+        // (a block: every blob's jobs are cut into groups of their own; a.blk_group has one entry per workgroup row)
+        const uint32_t groups = a.blk_table ? blk_groups : (L.batch + seeds_group - 1) / seeds_group;
         const dim3 grid((unsigned)(((size_t)1 << a.level_a) / T5_UNITS), groups);
         lv = T5_LEVELS;
         Scope scope(L, "tree5s_fold_circle", (32.0 * groups / L.batch + 48.0) * (double)((size_t)1 << a.level_a) + node_levels_bytes(a.level_a - 1, lv - 1));
@@ -1658,11 +1658,10 @@ void fold_and_tree(const Launch& L, bool circle, const uint32_t* src, size_t src
     if (blk && blk->table && shared_src && circle) {
         a.blk_table = blk->table;
         a.blk_job = blk->job_row;
-        a.blk_group = blk->group_first;
-        a.blk_seeds = blk->n_seeds;
-        if (!blk->group_first) seeds_group = 0;
+        a.blk_group = blk->groups;
+        if (!blk->groups) seeds_group = 0;
     }
-    build_tree(L, circle ? T_FOLD_CIRCLE : T_FOLD_LINE, a, m, layers, nullptr, nullptr, tr, nullptr, 0, seeds_group);
+    build_tree(L, circle ? T_FOLD_CIRCLE : T_FOLD_LINE, a, m, layers, nullptr, nullptr, tr, nullptr, 0, seeds_group, a.blk_table ? blk->n_groups : 0);
 }
 
 void channel_after_shared_root(const Launch& L, const uint8_t* d_root, DevTranscript* tr, const DevTranscript* tr_init, size_t tr_init_pitch,

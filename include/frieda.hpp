@@ -220,6 +220,22 @@ class Context {
         for (frieda_proof* p : ps) out.emplace_back(p);
         return out;
     }
+    // Any list of jobs in ONE call (frieda_prove_jobs): proof j == prove_seeds(*encs[blob_index[j]], {seeds[j]}, cfg)[0] byte for byte,
+    // in the caller's order; the call cuts itself into passes (frieda_prove_jobs_plan says how, frieda_prove_jobs_workspace_bytes sizes
+    // a pass); the split, one-pass form is frieda_prove_jobs_begin / frieda_prove_jobs_finish.
+    std::vector<Proof> prove_jobs(const std::vector<const Encoded*>& encs, const std::vector<uint32_t>& blob_index, const std::vector<uint64_t>& seeds,
+                                  const PcsConfig& cfg) {
+        if (blob_index.size() != seeds.size()) throw Error(FRIEDA_ERR_ARG, "prove_jobs: one seed per job");
+        std::vector<const frieda_encoded*> hs;
+        hs.reserve(encs.size());
+        for (const Encoded* e : encs) hs.push_back(e ? e->handle() : nullptr);
+        std::vector<frieda_proof*> ps(seeds.size(), nullptr);
+        check(frieda_prove_jobs(h_, hs.data(), (uint32_t)encs.size(), blob_index.data(), seeds.data(), (uint32_t)seeds.size(), cfg.c(), ps.data()), h_);
+        std::vector<Proof> out;
+        out.reserve(ps.size());
+        for (frieda_proof* p : ps) out.emplace_back(p);
+        return out;
+    }
     // The reconstructor's half of the README's sampling flow (/root/reference/README.md:56-69): any >= 2^log_coef + 2 distinct
     // (position, value) pairs of the bit-reversed codeword — e.g. pooled from api::verify_samples of proofs with different seeds —
     // give the blob's `len` bytes back (frieda_reconstruct_points_device: no linear system, every pair checked against the result;

@@ -593,13 +593,53 @@ int frieda_rebuild_encoded_blobs_from_stripe_bundles(frieda_ctx* ctx, const uint
  * frieda_prove_seeds_blobs_finish are one function: each completes whichever proving job is in flight and writes one proof per job.
  * Memory: the call is NOT cut into passes.  frieda_seeds_blobs_workspace_bytes(len, cfg, n_blobs, n_seeds) is what the call asks of
  * the context, the handles excluded; 0 for a refused shape; at n_blobs == 1 it equals frieda_seeds_workspace_bytes.  A call too
- * large for the GPU returns FRIEDA_ERR_NOMEM and leaves ctx usable: cut the seed list or the block. */
+ * large for the GPU returns FRIEDA_ERR_NOMEM and leaves ctx usable: cut the seed list or the block — or hand the same jobs to
+ * frieda_prove_jobs (below), which cuts them into passes itself. */
 int frieda_prove_seeds_blobs_begin(frieda_ctx* ctx, const frieda_encoded* const* encs, uint32_t n_blobs, const uint64_t* seeds, uint32_t n_seeds,
                                    frieda_pcs_config cfg);
 int frieda_prove_seeds_blobs_finish(frieda_ctx* ctx, frieda_proof** out_proofs);
 int frieda_prove_seeds_blobs(frieda_ctx* ctx, const frieda_encoded* const* encs, uint32_t n_blobs, const uint64_t* seeds, uint32_t n_seeds,
                              frieda_pcs_config cfg, frieda_proof** out_proofs);
 size_t frieda_seeds_blobs_workspace_bytes(size_t len, frieda_pcs_config cfg, uint32_t n_blobs, uint32_t n_seeds);
+
+/* ---- any list of (handle, seed) jobs in one call, cut into passes -------------------------------------------------------------
+ * A provider's request queue is no rectangle: one client asks for blobs 0, 3 and 7 under its seed, another for blob 3 under its own,
+ * a third for the whole block.  frieda_prove_jobs takes the queue as it is: job j is encs[blob_index[j]] under seeds[j].
+ * Result: out_proofs has n_jobs entries in the CALLER's order; out_proofs[j] serialises to exactly the bytes of
+ * frieda_prove_seeds(encs[blob_index[j]], &seeds[j], 1, cfg).  Any list is legal: a blob with many jobs or with one, a handle of the
+ * list that no job names, the same (blob, seed) pair twice (proved twice: nothing is de-duplicated), the same handle at two positions.
+ * Inside, the jobs run sorted by blob (a stable sort), so that the seed-looped first fold reads a blob's evaluation once per group of
+ * FRIEDA_SEEDS_FOLD_GROUP jobs of that blob; the rectangle of frieda_prove_seeds_blobs is the list that is sorted as it stands, and runs
+ * through the same code.
+ * Arguments: all pointers non-null, every handle non-null; n_blobs >= 1, n_jobs >= 1, every blob_index[j] < n_blobs; the handle rules,
+ * the channel rule (more than one job needs the transcript kernels) and the one-job-per-context rule are those of
+ * frieda_prove_seeds_blobs_begin; a breach returns FRIEDA_ERR_ARG.  No parameter is device memory.
+ * _begin / _finish are ONE pass: n_jobs <= 65535, frieda_prove_jobs_workspace_bytes(len, cfg, n_blobs, n_jobs) is what _begin asks of
+ * the context (0 for a refused shape; at n_blobs == 1 it equals frieda_seeds_workspace_bytes(len, cfg, n_jobs), at (K, K * S) it equals
+ * frieda_seeds_blobs_workspace_bytes(len, cfg, K, S): the table is the same table), and a call too large returns FRIEDA_ERR_NOMEM and
+ * leaves ctx usable.  frieda_prove_jobs_finish is the one finish frieda_prove_seeds_finish is.
+ * frieda_prove_jobs, the synchronous form, is cut into passes and has no cap on n_jobs.  The rule is what frieda_prove_jobs_plan
+ * returns: jobs_per_pass is the largest p in [1, min(n_jobs, 65535)] with frieda_prove_jobs_workspace_bytes(len, cfg, min(n_blobs, p), p)
+ * within the limit (1 when not even one job is), the limit being the batch policy's budget (FRIEDA_BATCH_BUDGET_MB, see below; ctx ==
+ * NULL: the default options) or the arena limit of the test hook when that is set and smaller; n_passes = ceil(n_jobs / jobs_per_pass),
+ * the pass sizes equal to within one.  A pass takes consecutive jobs of the sorted list — it may take only some of one blob's jobs —
+ * and its table holds only the blobs it names.  A pass that still meets FRIEDA_ERR_NOMEM (the device holds less than the budget)
+ * makes the call halve jobs_per_pass and go on from the first unfinished job, down to one job per pass; only then does the error
+ * reach the caller.  On any failure every proof already produced is freed and out_proofs is all null.
+ * Measured on MI355X on sparse queues (every client names a quarter of the blobs; blow-up 16, 20 queries, 20-bit proof of work; HIP-event
+ * medians of 21 alternated calls, profiles/r22_prove_jobs.txt) against the loop of frieda_prove_seeds per distinct blob and against
+ * frieda_prove_seeds_blobs on the bounding rectangle: 256 jobs over 64 handles of 1 KiB 5.29 against 16.91 and 19.67 ms, 128 jobs over 16
+ * handles of 128 KiB 6.62 against 13.84 and 22.80 ms, 16 jobs over 4 handles of a 2^22 domain 3.64 against 5.16 and 12.67 ms; the
+ * rectangle's own list costs 0.06 - 0.27 ms more through this call than through frieda_prove_seeds_blobs (host work per job), and an
+ * extra pass 0.4 - 0.7 ms.  Other shapes are not measured. */
+int frieda_prove_jobs_begin(frieda_ctx* ctx, const frieda_encoded* const* encs, uint32_t n_blobs, const uint32_t* blob_index,
+                            const uint64_t* seeds, uint32_t n_jobs, frieda_pcs_config cfg);
+int frieda_prove_jobs_finish(frieda_ctx* ctx, frieda_proof** out_proofs);
+int frieda_prove_jobs(frieda_ctx* ctx, const frieda_encoded* const* encs, uint32_t n_blobs, const uint32_t* blob_index, const uint64_t* seeds,
+                      uint32_t n_jobs, frieda_pcs_config cfg, frieda_proof** out_proofs);
+size_t frieda_prove_jobs_workspace_bytes(size_t len, frieda_pcs_config cfg, uint32_t n_blobs, uint32_t n_jobs);
+int frieda_prove_jobs_plan(const frieda_ctx* ctx, size_t len, frieda_pcs_config cfg, uint32_t n_blobs, uint32_t n_jobs, uint32_t* jobs_per_pass,
+                           uint32_t* n_passes);
 
 /* ---- batch policy: how a stream of equal-length blobs is cut into batched calls ("bytes in flight") -------------------------
  * Every kernel of a batched call covers all its blobs, so the launch / Fiat-Shamir latency chain is paid once per call: small
