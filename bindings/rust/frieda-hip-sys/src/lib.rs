@@ -69,6 +69,7 @@ extern "C" {
     pub fn frieda_ctx_test_set_grind_first_log(ctx: *mut frieda_ctx, log_first: u32) -> c_int;
     pub fn frieda_ctx_test_set_arena_limit(ctx: *mut frieda_ctx, bytes: u64) -> c_int;
     pub fn frieda_ctx_test_set_verify_pass_bytes(ctx: *mut frieda_ctx, bytes: u64) -> c_int;
+    pub fn frieda_ctx_test_set_verify_scratch_bytes(ctx: *mut frieda_ctx, bytes: u64) -> c_int;
     pub fn frieda_ctx_test_poison(ctx: *mut frieda_ctx, word: u32, sticky: c_int, out_bytes: *mut u64) -> c_int;
     pub fn frieda_test_near_cpus(sysfs_root: *const c_char, pci_bus_id: *const c_char, out_cpus: *mut c_int, cap: usize, n: *mut usize) -> c_int;
     pub fn frieda_test_parse_cpulist(text: *const c_char, out_cpus: *mut c_int, cap: usize, n: *mut usize) -> c_int;
@@ -138,6 +139,12 @@ extern "C" {
     pub fn frieda_verify_samples(proof: *const frieda_proof, seed: *const u64, ok: *mut c_int, out_positions: *mut u32, cap: usize, n_positions: *mut usize) -> c_int;
     /// many proofs verified in one call on the GPU: one status byte per proof (FRIEDA_VERIFY_*), each the result of frieda_verify
     pub fn frieda_verify_many(ctx: *mut frieda_ctx, proofs: *const *const frieda_proof, seeds: *const u64, count: u32, expected_commitment: *const u8, out_status: *mut u8) -> c_int;
+    /// The proofs of a block against a table of commitments: `commitments` is `[n_blobs][32]`, `blob_index` is `[count]` or null (proof i
+    /// belongs to commitment i, `count == n_blobs`).  `out_status[i]` is what `frieda_verify_many` gives for proof i alone with
+    /// `commitments[blob_index[i]]`; `out_accepted_per_blob` (`[n_blobs]`, may be null) counts the ACCEPTED proofs per blob.
+    /// `FRIEDA_ERR_ARG` before anything runs: an index >= `n_blobs`, null `blob_index` with `count != n_blobs`, `n_blobs == 0` with
+    /// `count > 0`, null `commitments`, a proof in flight on the context.
+    pub fn frieda_verify_blobs_many(ctx: *mut frieda_ctx, proofs: *const *const frieda_proof, seeds: *const u64, count: u32, commitments: *const u8, n_blobs: u32, blob_index: *const u32, out_status: *mut u8, out_accepted_per_blob: *mut u32) -> c_int;
     /// the same + the positions of every accepted proof (row i of out_positions: out_n_positions[i] entries, pitch apart)
     pub fn frieda_verify_samples_many(ctx: *mut frieda_ctx, proofs: *const *const frieda_proof, seeds: *const u64, count: u32, expected_commitment: *const u8, out_status: *mut u8, out_positions: *mut u32, pitch: usize, out_n_positions: *mut u32) -> c_int;
     /// verify, pool the verified samples, rebuild the blob and check it against the commitment

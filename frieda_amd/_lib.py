@@ -90,6 +90,7 @@ def lib():
         "frieda_ctx_test_set_grind_first_log": (C.c_int, [vp, u32]),
         "frieda_ctx_test_set_arena_limit": (C.c_int, [vp, u64]),
         "frieda_ctx_test_set_verify_pass_bytes": (C.c_int, [vp, u64]),
+        "frieda_ctx_test_set_verify_scratch_bytes": (C.c_int, [vp, u64]),
         "frieda_ctx_test_poison": (C.c_int, [vp, u32, C.c_int, u64p]),
         "frieda_workspace_bytes": (sz, [sz, u32, u32, C.c_int]),
         "frieda_batch_plan": (C.c_int, [vp, sz, u32, u32, C.c_int, u32, u32, C.POINTER(u32), sz, C.POINTER(u32)]),
@@ -150,6 +151,7 @@ def lib():
         "frieda_verify": (C.c_int, [vp, u64p, C.POINTER(C.c_int)]),
         "frieda_verify_samples": (C.c_int, [vp, u64p, C.POINTER(C.c_int), vp, sz, C.POINTER(sz)]),
         "frieda_verify_many": (C.c_int, [vp, pp, u64p, u32, vp, vp]),
+        "frieda_verify_blobs_many": (C.c_int, [vp, pp, u64p, u32, vp, u32, vp, vp, vp]),
         "frieda_verify_samples_many": (C.c_int, [vp, pp, u64p, u32, vp, vp, vp, sz, vp]),
         "frieda_reconstruct_from_proofs": (C.c_int, [vp, pp, u64p, u32, vp, sz, vp, vp, C.POINTER(sz)]),
         "frieda_verify_pairs": (C.c_int, [vp, u64p, C.POINTER(C.c_int), vp, vp, sz, C.POINTER(sz)]),

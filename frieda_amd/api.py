@@ -486,6 +486,33 @@ class Context:
         _check(self._L.frieda_verify_many(self._h, self._proof_array(proofs), self._seeds_array(seeds, count), count, com, status.ctypes.data), self._h)
         return status
 
+    def verify_blobs_many(self, proofs, commitments, blob_index=None, seeds=None):
+        """frieda_verify_blobs_many: the proofs of a block against a table of commitments.  Returns (status, accepted_per_blob): status[i]
+        is exactly what verify_many gives for proof i alone with expected_commitment = commitments[blob_index[i]] (VERIFY_WRONG_COMMITMENT
+        included, on every route); accepted_per_blob[b] (numpy uint32) is the number of ACCEPTED proofs that name blob b, so "proximity
+        checked" reads > 0.  blob_index None: proof i belongs to commitment i and len(proofs) must be len(commitments).  FriedaError
+        (ERR_ARG) before anything runs: an index >= len(commitments), blob_index None with a different count, proofs but no commitments,
+        a proof in flight on the context."""
+        import numpy as np
+
+        count, n_blobs = len(proofs), len(commitments)
+        if blob_index is not None and len(blob_index) != count:
+            raise ValueError("one blob index per proof")
+        if any(len(c) != 32 for c in commitments):
+            raise ValueError("a commitment is 32 bytes")
+        status = np.zeros(count, dtype=np.uint8)
+        accepted = np.zeros(n_blobs, dtype=np.uint32)
+        table = np.frombuffer(b"".join(bytes(c) for c in commitments) or b"\0", dtype=np.uint8).copy()
+        bidx = None if blob_index is None else np.ascontiguousarray(blob_index, dtype=np.uint32)
+        _check(
+            self._L.frieda_verify_blobs_many(
+                self._h, self._proof_array(proofs) if count else None, self._seeds_array(seeds, count), count, table.ctypes.data, n_blobs,
+                None if bidx is None else bidx.ctypes.data, status.ctypes.data, accepted.ctypes.data
+            ),
+            self._h,
+        )
+        return status, accepted
+
     def verify_samples_many(self, proofs, seeds=None, expected_commitment=None, pitch=None):
         """(status, positions): positions[i] is the numpy uint32 array verify_samples() returns for proof i, None unless it is accepted."""
         import numpy as np
@@ -1444,6 +1471,11 @@ def reconstruct_from_proof_pairs(proofs, seeds, expected_commitment, n_bytes):
 def verify_many(proofs, seeds=None, expected_commitment=None):
     """frieda_verify_many on the default context: one status byte per proof, verified in one call on the device."""
     return default_context().verify_many(proofs, seeds, expected_commitment)
+
+
+def verify_blobs_many(proofs, commitments, blob_index=None, seeds=None):
+    """frieda_verify_blobs_many on the default context: (status, accepted_per_blob), proof i against commitments[blob_index[i]]."""
+    return default_context().verify_blobs_many(proofs, commitments, blob_index, seeds)
 
 
 def verify_samples_many(proofs, seeds=None, expected_commitment=None):

@@ -238,6 +238,12 @@ int frieda_ctx_test_set_verify_pass_bytes(frieda_ctx* ctx, uint64_t bytes) {
     return FRIEDA_OK;
 }
 
+int frieda_ctx_test_set_verify_scratch_bytes(frieda_ctx* ctx, uint64_t bytes) {
+    if (!ctx) return FRIEDA_ERR_ARG;
+    ctx->c.tuning.test_verify_scratch_bytes = bytes;
+    return FRIEDA_OK;
+}
+
 size_t frieda_workspace_bytes(size_t len, uint32_t log_blowup_factor, uint32_t log_last_layer_degree_bound, int prove) {
     return workspace_bytes_per_blob(len, log_blowup_factor, log_last_layer_degree_bound, prove != 0, true);
 }

@@ -146,6 +146,7 @@ const KnobDesc KNOBS[] = {
     {"FRIEDA_HOST_DECOMMIT", 0, 1, [](Tuning& t, long v) { t.host_decommit = v != 0; return true; }},
     {"FRIEDA_GATHER_COPY", 0, 1, [](Tuning& t, long v) { t.gather_copy = v != 0; return true; }},
     {"FRIEDA_VERIFY_DEVICE_MIN", 0, 2147483648L, [](Tuning& t, long v) { t.verify_device_min = (uint32_t)v; return true; }},
+    {"FRIEDA_VERIFY_SPLIT_MAX", 0, 2147483648L, [](Tuning& t, long v) { t.verify_split_max = (uint32_t)v; return true; }},
     {"FRIEDA_OPEN_SMALL_MAX", 0, 512, [](Tuning& t, long v) { t.open_small_max = (uint32_t)v; return true; }},
     {"FRIEDA_TREE_SKIP_LOG", 10, 40, [](Tuning& t, long v) { t.tree_skip_log = (uint32_t)v; return true; }},
     {"FRIEDA_TREE_SKIP_LONE_LOG", 10, 40, [](Tuning& t, long v) { t.tree_skip_lone_log = (uint32_t)v; return true; }},

@@ -338,11 +338,14 @@ struct PairPool : DevPool {
     int upload_host_rows(Ctx* ctx);   // synchronous; a no-op without host-route proofs
 };
 // Many proofs in one call (verify_many.cpp, verify.hip): out_status[i] = a k::VerifyStatus, per proof the result of verify() whatever the
-// route (device passes for the shapes the kernel takes, from Tuning::verify_device_min eligible proofs on; verify() for the rest).
+// route (device passes for the shapes the kernel takes, from Tuning::verify_device_min eligible proofs on — one launch per pass, or the
+// two of verify_split.hip for a pass of at most Tuning::verify_split_max proofs; verify() for the rest).
 // samples: an accepted proof must also hold one evaluation per distinct query (frieda_verify_samples), else VERIFY_INVARIANT;
 // positions (optional): the sampled positions of every accepted proof.  Uses the arena and the pinned block (callers: FR_NO_JOB).
 // pairs (optional, with samples): the pairs mode above.
-int verify_many(Ctx* ctx, const ProofData* const* proofs, const uint64_t* seeds, uint32_t count, const uint8_t* expected_commitment, bool samples,
+// expected_commitments (optional): per proof the 32 bytes its first-layer commitment must equal (an entry may be null: not compared),
+// else VERIFY_WRONG_COMMITMENT; the one-commitment entry points pass the same pointer for every proof.
+int verify_many(Ctx* ctx, const ProofData* const* proofs, const uint64_t* seeds, uint32_t count, const uint8_t* const* expected_commitments, bool samples,
                 uint8_t* out_status, std::vector<std::vector<uint32_t>>* positions, PairPool* pairs = nullptr);
 // The point reconstruction with the pool already on the device, outside the arena: d_index[n_entries] next to
 // d_cells[n_entries][n_blobs][4][2^log_cell] — ONE reconstruction over 4 * n_blobs columns (one locator for all of them), then blob b

@@ -49,8 +49,13 @@ struct Tuning {
     uint32_t tail_run_log = 9;           // FRIEDA_TAIL_RUN_LOG: layers of more than 2^v points use the multi-workgroup kernels
     bool host_decommit = false;          // FRIEDA_HOST_DECOMMIT: openings by the host planner + gather launch
     bool gather_copy = false;            // FRIEDA_GATHER_COPY: fallback path stages lists and results through device memory + copies
-    uint32_t verify_device_min = 1;      // FRIEDA_VERIFY_DEVICE_MIN: frieda_verify_many* use the device from this many device-eligible proofs per call
-                                         // (0: always; 1 is the starting value, the device route is not measured yet: profiles/r09_verify_many.txt)
+    uint32_t verify_device_min = 2;      // FRIEDA_VERIFY_DEVICE_MIN: frieda_verify_many* use the device from this many device-eligible proofs per call
+                                         // (0: always).  Measured (profiles/r23_verify_split.txt): a lone proof takes 0.07 / 0.24 ms on one host core
+                                         // (1 KiB / 128 KiB blob) against 0.14 / 0.27 ms through the device; from 16 proofs on the device is 7 - 40 x faster
+    uint32_t verify_split_max = 256;     // FRIEDA_VERIFY_SPLIT_MAX: a verify pass of at most this many kernel-eligible proofs runs as two launches, a
+                                         // wave per proof for the value chain and a wave per (proof, layer) for the Merkle walks (verify_split.hip);
+                                         // 0 = never, 2^31 = always.  Measured (profiles/r23_verify_split.txt): 256 is the largest count at which the two
+                                         // launches beat the one by more than both rows' spread at both blob sizes; at 1024 and 4096 the difference is inside them
     uint32_t open_small_max = 512;       // FRIEDA_OPEN_SMALL_MAX: largest position list frieda_merkle_decommit* opens in one workgroup (0: every list multi-block)
     uint32_t test_grind_first_log = 0;   // test hook (frieda_ctx_test_set_grind_first_log): a short first nonce range (0 = off)
     // batch policy (host.h, "batch policy"): workspace bytes a batched call may keep in flight, and the fewest calls a context gets
@@ -77,6 +82,7 @@ struct Tuning {
                                          // four-columns-side-by-side fold2 kernel (ntt.hip), also against a later set_option
     uint64_t test_arena_limit = 0;       // test hook (frieda_ctx_test_set_arena_limit): ensure_arena refuses more than this many bytes (0 = off)
     uint64_t test_verify_pass_bytes = 0; // test hook (frieda_ctx_test_set_verify_pass_bytes): staging budget of one verify pass (0 = the default, 32 MB)
+    uint64_t test_verify_scratch_bytes = 0;  // test hook (frieda_ctx_test_set_verify_scratch_bytes): scratch cap of a split verify pass (0 = the default, 256 MiB)
     bool test_poison = false;            // test hook (frieda_ctx_test_poison, sticky): every allocation the context makes for itself is filled with
     uint32_t test_poison_word = 0;       // this word on the ctx stream before its first use (host side only: no kernel reads either field)
 };
@@ -419,6 +425,23 @@ struct VerifyArgs {
 size_t verify_many_lds_bytes(uint32_t q_cap);
 hipError_t verify_many_init(const CPoint (&gen_pow2)[31]);  // uploads the generator's doublings (once per device)
 void verify_many(const Launch& L, const VerifyArgs& a, uint32_t n_proofs);
+// ---- verify_split.hip: the same pass as two launches (FRIEDA_VERIFY_SPLIT_MAX) ----
+// verify_split_chain: one wave per proof does everything of verify_many_kernel that hashes no Merkle node — transcript, PoW, queries,
+// the value chain of every layer, the last-layer check — writes the same output row, except that word 0 is the KEY of its first event
+// (verify_pass.h, "the rule"), and leaves per layer it passed the assembled pairs in `pairs` and their number in `cnt`.
+// verify_split_walks: one wave per (proof, layer): pair hashes, the Merkle walk and the root compare; a failing wave lowers word 0 of
+// the proof's row to its own key.  Both go to L.stream back to back; the host decodes word 0 with verify_key_status.
+// Timer scopes: "verify_many" names the launches of a verify pass on either shape: one per pass on the one-kernel shape, two here.
+struct VerifySplitArgs {
+    VerifyArgs v;
+    uint32_t max_layers;  // the pass's largest layer count: the pitch of `cnt` and `pairs`, and the y extent of the walk grid
+    uint32_t* cnt;        // [n_proofs][max_layers]: pairs of the layer; 0 = not reached, or its value stage failed.  Written for every layer.
+    uint32_t* pairs;      // [n_proofs][max_layers] blocks of 9 * q_cap words: v[q_cap] | (l, r)[q_cap][8]; 16-byte aligned
+};
+size_t verify_chain_lds_bytes(uint32_t q_cap);
+size_t verify_walk_lds_bytes(uint32_t q_cap);
+hipError_t verify_split_init(const CPoint (&gen_pow2)[31]);  // this unit's copy of the generator's doublings (once per device)
+void verify_split(const Launch& L, const VerifySplitArgs& a, uint32_t n_proofs);
 // rows of a pass's pair buffer -> the call's pool.  d_tab[n_rows][3]: row (slot of the pass), entries (2 * pairs), first pool entry;
 // d_pool_pos[entry], d_pool_val[entry][4]: 16-byte aligned, as d_pair_val
 void verify_pairs_gather(const Launch& L, const uint32_t* d_tab, uint32_t n_rows, const uint32_t* d_pair_pos, const uint32_t* d_pair_val, uint32_t q_cap,

@@ -30,7 +30,9 @@ namespace qdev {
 // Queries::generate by a workgroup of THREADS threads (all of them call): the nq draws of `ch` masked to 2^log_domain go to q —
 // LDS, room for P = the next power of two >= max(2, nq) words, padded with 0xFFFFFFFF — are sorted there, and the distinct ones go
 // to u (LDS, nq words), ascending.  Returns their number, the same in every thread; q and u are ready for all threads on return.
-template <int THREADS>
+// RANK_UNROLL: how far the 64-lane rank loop is unrolled.  Fully (the default) it holds all 64 broadcast values in SGPRs at once; a
+// kernel that keeps many uniform values of its own across the call asks for less (verify_split.hip), for the same result.
+template <int THREADS, int RANK_UNROLL = 64>
 __device__ __forceinline__ uint32_t generate_queries(const Channel& ch, uint32_t log_domain, uint32_t nq, uint32_t* q, uint32_t* u) {
     static_assert(THREADS % 64 == 0, "whole waves");
     const uint32_t t = threadIdx.x, lane = t & 63;
@@ -71,7 +73,7 @@ __device__ __forceinline__ uint32_t generate_queries(const Channel& ch, uint32_t
         if (P <= 64) {  // the usual case: sort by rank
             const uint32_t v = q[lane < P ? lane : 0];
             uint32_t rank = 0;
-#pragma unroll
+#pragma unroll RANK_UNROLL
             for (int j = 0; j < 64; j++) {  // lanes >= P hold a copy of lane 0's value and are masked out
                 const uint32_t o = (uint32_t)__builtin_amdgcn_readlane((int)v, j);
                 rank += ((uint32_t)j < P && (o < v || (o == v && (uint32_t)j < lane))) ? 1u : 0u;

@@ -22,6 +22,7 @@
 #include "kernels.h"
 #include "queries_dev.h"
 #include "tree_dev.h"
+#include "verify_dev.h"
 #include "walk_dev.h"
 
 namespace frieda {
@@ -29,29 +30,8 @@ namespace k {
 
 namespace {
 
-constexpr uint32_t LAST_LOG_MAX = 11;  // log2 of DT_MAX_LAST_POLY
-static_assert((1u << LAST_LOG_MAX) == DT_MAX_LAST_POLY, "the last-layer fold keeps one stack entry per bit of a coefficient index");
-
-__constant__ CPoint c_gen_pow2[31];  // 2^b * G of the circle group's generator (host: point_from_index)
-
-__device__ __forceinline__ CPoint dev_point_from_index(uint32_t index) {
-    CPoint res{1, 0};
-    index &= 0x7fffffffu;
-    for (uint32_t b = 0; index; b++, index >>= 1)
-        if (index & 1u) res = cp_add(res, c_gen_pow2[b]);
-    return res;
-}
-
-// point index of entry `i` of line_coset(n, n - li) (li = 0: Coset::half_odds(n - 1) itself)
-__device__ __forceinline__ uint32_t coset_index(uint32_t n, uint32_t doublings, uint32_t i) {
-    const unsigned long long init = (1ull << (30 - n)) << doublings, step = (1ull << (32 - n)) << doublings;
-    return (uint32_t)((init + step * i) & 0x7fffffffull);
-}
-
 using walkdev::Group;
 using walkdev::group_of;
-
-__device__ __forceinline__ QM31 load_qm(const uint32_t* p) { return QM31{p[0], p[1], p[2], p[3]}; }
 
 // PAIRS: the first layer's opened pairs also go to the proof's row of a.pair_pos / a.pair_val (frieda_verify_pairs_many) — tentatively:
 // a later layer may still reject the proof, and nothing reads the row unless the final status is VERIFY_ACCEPTED.
@@ -204,40 +184,7 @@ __global__ __launch_bounds__(64) void verify_many_kernel(VerifyArgs a) {
         bool bad = false;
         for (uint32_t i = lane; i < c; i += 64) {
             const uint32_t x = dev_point_from_index(coset_index(n, nl, bit_reverse(s_pos[i], ml))).x;
-            // fold(coeffs, doublings) of LinePoly::eval_at_point, bottom up in one pass over the coefficients: bit b of a coefficient's
-            // index carries x doubled (plog - 1 - b) times; stk[b] holds the folded left half of an open 2^(b+1) block.  j is uniform
-            // over the wave, so the branches are scalar and the arrays stay in registers: np - 1 QM31 scalings per position.
-            uint32_t fb[LAST_LOG_MAX];
-            {
-                uint32_t xx = x;
-#pragma unroll
-                for (uint32_t b = 0; b < LAST_LOG_MAX; b++) fb[b] = 0;
-#pragma unroll
-                for (uint32_t d = 0; d < LAST_LOG_MAX; d++) {
-#pragma unroll
-                    for (uint32_t b = 0; b < LAST_LOG_MAX; b++)
-                        if (b + d + 1 == plog) fb[b] = xx;
-                    xx = double_x(xx);
-                }
-            }
-            QM31 stk[LAST_LOG_MAX], acc{0, 0, 0, 0};
-#pragma unroll
-            for (uint32_t b = 0; b < LAST_LOG_MAX; b++) stk[b] = QM31{0, 0, 0, 0};
-            for (uint32_t j = 0; j < np; j++) {
-                acc = load_qm(last_poly + 4 * (size_t)j);
-                bool open = true;
-#pragma unroll
-                for (uint32_t b = 0; b < LAST_LOG_MAX; b++) {
-                    if (open) {
-                        if ((j >> b) & 1u) {
-                            acc = qm_add(stk[b], qm_scale(acc, fb[b]));
-                        } else {
-                            stk[b] = acc;
-                            open = false;
-                        }
-                    }
-                }
-            }
+            const QM31 acc = last_poly_eval_at(last_poly, np, plog, x);
             if (!qm_eq(acc, load_qm(s_ev + 4 * i))) bad = true;  // LastLayerEvaluationsInvalid
         }
         if (__any(bad)) VK_FINISH(VERIFY_REJECTED);
@@ -268,7 +215,7 @@ __global__ __launch_bounds__(256) void pairs_gather_kernel(const uint32_t* __res
 
 size_t verify_many_lds_bytes(uint32_t q_cap) { return sizeof(uint32_t) * 14 * (size_t)q_cap; }
 
-hipError_t verify_many_init(const CPoint (&gen_pow2)[31]) { return hipMemcpyToSymbol(HIP_SYMBOL(c_gen_pow2), gen_pow2, sizeof(gen_pow2)); }
+hipError_t verify_many_init(const CPoint (&gen_pow2)[31]) { return upload_gen_pow2(gen_pow2); }
 
 void verify_many(const Launch& L, const VerifyArgs& a, uint32_t n_proofs) {
     Scope scope(L, "verify_many", 0.0);

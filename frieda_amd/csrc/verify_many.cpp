@@ -7,8 +7,9 @@
 // reference — a proof that is also short of evaluations panics first — so the kernel applies them, in the reference's order.)  Proofs of
 // a shape the kernel does not take (more than VERIFY_MAX_QUERIES queries, a last layer above DT_MAX_LAST_POLY, more than DT_MAX_LAYERS
 // layers, no queries at all) go through verify() inside the same call.  The rest is flattened into the context's pinned staging block
-// in passes bounded by PASS_BYTES — header, layer table, words — uploaded, verified by one launch per pass, and one status word and
-// the sampled positions per proof come back.  In pairs mode the kernel also leaves both members of every opened first-layer pair in a
+// in passes bounded by VERIFY_PASS_BYTES — header, layer table, words — uploaded, verified by one launch per pass (or, for a pass of at
+// most FRIEDA_VERIFY_SPLIT_MAX proofs, by the two launches of verify_split.hip: verify_pass.h has the cut and the status rule), and one
+// status word and the sampled positions per proof come back.  In pairs mode the kernel also leaves both members of every opened first-layer pair in a
 // per-pass buffer; once the statuses are known, a gather launch copies the rows of the accepted proofs into the call's PairPool.
 #include <string.h>
 
@@ -17,12 +18,11 @@
 
 #include "dev_transcript.h"
 #include "host.h"
+#include "verify_pass.h"
 
 namespace frieda {
 
 namespace {
-
-constexpr size_t PASS_BYTES = (size_t)32 << 20;  // staging budget of one upload (a lone larger proof is a pass of its own); test hook: Tuning::test_verify_pass_bytes
 
 size_t image_words(const ProofData& p) {
     size_t w = 4 * (p.inner_layers.size() + 1);
@@ -117,6 +117,7 @@ int init_device_tables(Ctx* ctx) {
     CPoint t[31];
     for (uint32_t b = 0; b < 31; b++) t[b] = point_from_index(1u << b);
     FR_HIP(ctx, k::verify_many_init(t));
+    FR_HIP(ctx, k::verify_split_init(t));
     done.push_back(ctx->device);
     return FRIEDA_OK;
 }
@@ -145,7 +146,7 @@ int PairPool::upload_host_rows(Ctx* ctx) {
     return FRIEDA_OK;
 }
 
-int verify_many(Ctx* ctx, const ProofData* const* proofs, const uint64_t* seeds, uint32_t count, const uint8_t* expected_commitment, bool samples,
+int verify_many(Ctx* ctx, const ProofData* const* proofs, const uint64_t* seeds, uint32_t count, const uint8_t* const* expected_commitments, bool samples,
                 uint8_t* out_status, std::vector<std::vector<uint32_t>>* positions, PairPool* pairs) {
     if (positions) positions->assign(count, {});
     if (pairs) {
@@ -168,7 +169,7 @@ int verify_many(Ctx* ctx, const ProofData* const* proofs, const uint64_t* seeds,
     std::vector<uint32_t> host;
     for (uint32_t i = 0; i < count; i++) {
         const ProofData& p = *proofs[i];
-        if (expected_commitment && memcmp(p.first_layer.commitment.data(), expected_commitment, 32) != 0) {
+        if (expected_commitments && expected_commitments[i] && memcmp(p.first_layer.commitment.data(), expected_commitments[i], 32) != 0) {
             out_status[i] = k::VERIFY_WRONG_COMMITMENT;
             continue;
         }
@@ -201,24 +202,25 @@ int verify_many(Ctx* ctx, const ProofData* const* proofs, const uint64_t* seeds,
     }
     hipStream_t s = ctx->stream;
     const size_t hdr_words = sizeof(k::VerifyHeader) / 4, head = pairs ? 3 : 2;  // (head: words of an output row before the queries)
-    const size_t pass_bytes = ctx->tuning.test_verify_pass_bytes ? (size_t)ctx->tuning.test_verify_pass_bytes : PASS_BYTES;
+    // (the staging budget of one upload; a lone larger proof is a pass of its own; test hook: Tuning::test_verify_pass_bytes)
+    const size_t pass_bytes = ctx->tuning.test_verify_pass_bytes ? (size_t)ctx->tuning.test_verify_pass_bytes : VERIFY_PASS_BYTES;
+    const size_t scratch_cap = ctx->tuning.test_verify_scratch_bytes ? (size_t)ctx->tuning.test_verify_scratch_bytes : VERIFY_SPLIT_SCRATCH_CAP;
+    auto item = [&](size_t e) {
+        const ProofData& p = *proofs[dev[e]];
+        return VerifyPassItem{hdr_words + image_words(p), p.pcs_config.n_queries, (uint32_t)p.inner_layers.size() + 1};
+    };
     for (size_t first = 0; first < dev.size();) {
-        // the proofs of this pass
-        size_t end = first, words = 0;
-        uint32_t q_cap = 64;
-        while (end < dev.size()) {
-            const size_t w = hdr_words + image_words(*proofs[dev[end]]);
-            if (end > first && 4 * (words + w) > pass_bytes) break;
-            words += w;
-            while (q_cap < proofs[dev[end]]->pcs_config.n_queries) q_cap <<= 1;
-            end++;
-        }
+        // the proofs of this pass and its launch shape (verify_pass.h)
+        const VerifyPassCut cut = verify_pass_cut(item, first, dev.size(), pass_bytes, ctx->tuning.verify_split_max, scratch_cap);
+        const size_t end = cut.end, words = cut.words;
+        const uint32_t q_cap = cut.q_cap;
         const size_t np = end - first, in_bytes = (4 * words + 255) & ~(size_t)255, out_bytes = 4 * np * (head + (size_t)q_cap);
         const size_t tab_bytes = pairs ? 12 * np : 0, row = 2 * (size_t)q_cap;  // (row: entries of a proof in the pass's pair buffer)
         if (words >= ((size_t)1 << 32)) return ctx->fail(FRIEDA_ERR_ARG, "verify_many: one proof beyond 2^32 words");
         ArenaPlan ap;
         const size_t a_in = ap.take(in_bytes), a_out = ap.take(out_bytes);
         const size_t a_pp = ap.take(pairs ? 4 * np * row : 0), a_pv = ap.take(pairs ? 16 * np * row : 0), a_tab = ap.take(tab_bytes);
+        const size_t a_cnt = ap.take(cut.split ? 4 * np * cut.max_layers : 0), a_sp = ap.take(cut.scratch_bytes);
         rc = ctx->ensure_arena(ap.off);
         if (rc) return rc;
         rc = ensure_pinned(ctx, in_bytes + out_bytes + tab_bytes);
@@ -240,7 +242,16 @@ int verify_many(Ctx* ctx, const ProofData* const* proofs, const uint64_t* seeds,
             va.pair_pos = reinterpret_cast<uint32_t*>(ctx->arena + a_pp);
             va.pair_val = reinterpret_cast<uint32_t*>(ctx->arena + a_pv);
         }
-        k::verify_many(ctx->launch(), va, (uint32_t)np);
+        if (cut.split) {
+            k::VerifySplitArgs sa;
+            sa.v = va;
+            sa.max_layers = cut.max_layers;
+            sa.cnt = reinterpret_cast<uint32_t*>(ctx->arena + a_cnt);
+            sa.pairs = reinterpret_cast<uint32_t*>(ctx->arena + a_sp);
+            k::verify_split(ctx->launch(), sa, (uint32_t)np);
+        } else {
+            k::verify_many(ctx->launch(), va, (uint32_t)np);
+        }
         FR_HIP(ctx, hipGetLastError());
         uint32_t* res = pin + in_bytes / 4;
         FR_HIP(ctx, hipMemcpyAsync(res, ctx->arena + a_out, out_bytes, hipMemcpyDeviceToHost, s));
@@ -250,8 +261,10 @@ int verify_many(Ctx* ctx, const ProofData* const* proofs, const uint64_t* seeds,
         for (size_t j = 0; j < np; j++) {
             const uint32_t i = dev[first + j];
             const uint32_t* r = res + j * (head + (size_t)q_cap);
-            uint8_t st = (uint8_t)r[0];
-            if (r[0] > k::VERIFY_INVARIANT) return ctx->fail(FRIEDA_ERR_INVARIANT, "verify_many: the kernel left no status");
+            // (split: the key of the first event; a word that is no key of this proof decodes to "no status")
+            const uint32_t word = !cut.split ? r[0] : verify_key_valid(r[0], (uint32_t)proofs[i]->inner_layers.size()) ? verify_key_status(r[0], k::VERIFY_ACCEPTED) : 0xFFFFFFFFu;
+            uint8_t st = (uint8_t)word;
+            if (word > k::VERIFY_INVARIANT) return ctx->fail(FRIEDA_ERR_INVARIANT, "verify_many: the kernel left no status");
             if (st == k::VERIFY_ACCEPTED && samples && r[1] != proofs[i]->evaluations.size()) st = k::VERIFY_INVARIANT;
             out_status[i] = st;
             if (positions && st == k::VERIFY_ACCEPTED) (*positions)[i].assign(r + head, r + head + r[1]);
@@ -284,8 +297,16 @@ using namespace frieda;
 
 extern "C" {
 
+// the commitment pointer per proof of the one-commitment entry points: the same for all, or none
+struct SameCommitment {
+    std::vector<const uint8_t*> v;
+    SameCommitment(const uint8_t* c, uint32_t count) : v(c ? count : 0, c) {}
+    const uint8_t* const* get() const { return v.empty() ? nullptr : v.data(); }
+};
+
+// commitments: NULL (nothing is compared) or per proof the 32 bytes its first-layer commitment must equal
 static int verify_many_common(frieda_ctx* ctx, const frieda_proof* const* proofs, const uint64_t* seeds, uint32_t count,
-                              const uint8_t* expected_commitment, bool samples, uint8_t* out_status, std::vector<std::vector<uint32_t>>* positions,
+                              const uint8_t* const* commitments, bool samples, uint8_t* out_status, std::vector<std::vector<uint32_t>>* positions,
                               PairPool* pairs = nullptr) {
     if (!ctx) return FRIEDA_ERR_ARG;
     if (count == 0) return FRIEDA_OK;
@@ -296,13 +317,37 @@ static int verify_many_common(frieda_ctx* ctx, const frieda_proof* const* proofs
     FR_GUARD_BEGIN
     std::vector<const ProofData*> ps(count);
     for (uint32_t i = 0; i < count; i++) ps[i] = &proofs[i]->p;
-    return verify_many(&ctx->c, ps.data(), seeds, count, expected_commitment, samples, out_status, positions, pairs);
+    return verify_many(&ctx->c, ps.data(), seeds, count, commitments, samples, out_status, positions, pairs);
     FR_GUARD_END(ctx)
 }
 
 int frieda_verify_many(frieda_ctx* ctx, const frieda_proof* const* proofs, const uint64_t* seeds, uint32_t count,
                        const uint8_t* expected_commitment, uint8_t* out_status) {
-    return verify_many_common(ctx, proofs, seeds, count, expected_commitment, false, out_status, nullptr);
+    return verify_many_common(ctx, proofs, seeds, count, SameCommitment(expected_commitment, count).get(), false, out_status, nullptr);
+}
+
+int frieda_verify_blobs_many(frieda_ctx* ctx, const frieda_proof* const* proofs, const uint64_t* seeds, uint32_t count, const uint8_t* commitments,
+                             uint32_t n_blobs, const uint32_t* blob_index, uint8_t* out_status, uint32_t* out_accepted_per_blob) {
+    if (!ctx) return FRIEDA_ERR_ARG;
+    if (!commitments) return ctx->c.fail(FRIEDA_ERR_ARG, "verify_blobs_many: no commitments");
+    if (count > 0 && n_blobs == 0) return ctx->c.fail(FRIEDA_ERR_ARG, "verify_blobs_many: proofs but no blobs");
+    if (!blob_index && count != n_blobs) return ctx->c.fail(FRIEDA_ERR_ARG, "verify_blobs_many: without blob_index proof i belongs to commitment i: count must be n_blobs");
+    if (count > 0 && !out_status) return FRIEDA_ERR_ARG;
+    for (uint32_t i = 0; blob_index && i < count; i++)
+        if (blob_index[i] >= n_blobs) return ctx->c.fail(FRIEDA_ERR_ARG, "blob_index " + std::to_string(i) + " beyond n_blobs");
+    FR_NO_JOB(&ctx->c);
+    FR_GUARD_BEGIN
+    std::vector<const uint8_t*> coms(count);
+    for (uint32_t i = 0; i < count; i++) coms[i] = commitments + 32 * (size_t)(blob_index ? blob_index[i] : i);
+    const int rc = verify_many_common(ctx, proofs, seeds, count, coms.data(), false, out_status, nullptr);
+    if (rc != FRIEDA_OK) return rc;
+    if (out_accepted_per_blob) {
+        std::fill(out_accepted_per_blob, out_accepted_per_blob + n_blobs, 0u);
+        for (uint32_t i = 0; i < count; i++)
+            if (out_status[i] == k::VERIFY_ACCEPTED) out_accepted_per_blob[blob_index ? blob_index[i] : i]++;
+    }
+    return FRIEDA_OK;
+    FR_GUARD_END(ctx)
 }
 
 int frieda_verify_samples_many(frieda_ctx* ctx, const frieda_proof* const* proofs, const uint64_t* seeds, uint32_t count,
@@ -317,7 +362,7 @@ int frieda_verify_samples_many(frieda_ctx* ctx, const frieda_proof* const* proof
     }
     FR_GUARD_BEGIN
     std::vector<std::vector<uint32_t>> pos;
-    const int rc = verify_many_common(ctx, proofs, seeds, count, expected_commitment, true, out_status, &pos);
+    const int rc = verify_many_common(ctx, proofs, seeds, count, SameCommitment(expected_commitment, count).get(), true, out_status, &pos);
     if (rc != FRIEDA_OK) return rc;
     for (uint32_t i = 0; i < count; i++) {
         out_n_positions[i] = (uint32_t)pos[i].size();
@@ -333,7 +378,7 @@ int frieda_reconstruct_from_proofs(frieda_ctx* ctx, const frieda_proof* const* p
     *n_points = 0;
     FR_GUARD_BEGIN
     std::vector<std::vector<uint32_t>> pos;
-    int rc = verify_many_common(ctx, proofs, seeds, count, expected_commitment, true, out_status, &pos);
+    int rc = verify_many_common(ctx, proofs, seeds, count, SameCommitment(expected_commitment, count).get(), true, out_status, &pos);
     if (rc != FRIEDA_OK) return rc;
     // pool the verified (position, evaluation) pairs: first occurrence of a position kept
     bool have_shape = false;
@@ -387,7 +432,7 @@ int frieda_verify_pairs_many(frieda_ctx* ctx, const frieda_proof* const* proofs,
     }
     FR_GUARD_BEGIN
     PairPool pool;
-    const int rc = verify_many_common(ctx, proofs, seeds, count, expected_commitment, true, out_status, nullptr, &pool);
+    const int rc = verify_many_common(ctx, proofs, seeds, count, SameCommitment(expected_commitment, count).get(), true, out_status, nullptr, &pool);
     if (rc != FRIEDA_OK) return rc;
     // the gathered rows of the kernel's proofs come back in one copy each (the entries between them, kept for host-route proofs, are not read)
     std::vector<uint32_t> pos, val;
@@ -416,7 +461,7 @@ int frieda_reconstruct_from_proof_pairs(frieda_ctx* ctx, const frieda_proof* con
     *n_points = 0;
     FR_GUARD_BEGIN
     PairPool pool;
-    int rc = verify_many_common(ctx, proofs, seeds, count, expected_commitment, true, out_status, nullptr, &pool);
+    int rc = verify_many_common(ctx, proofs, seeds, count, SameCommitment(expected_commitment, count).get(), true, out_status, nullptr, &pool);
     if (rc != FRIEDA_OK) return rc;
     rc = pool.upload_host_rows(&ctx->c);
     if (rc != FRIEDA_OK) return rc;

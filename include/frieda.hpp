@@ -270,7 +270,28 @@ class Context {
               h_);
         return status;
     }
-    // the same + the positions every accepted proof sampled (frieda_verify_samples_many; empty for a proof that is not accepted)
+    // The proofs of a block against a table of commitments (frieda_verify_blobs_many): status[i] is what verify_many gives for proof i alone
+    // with commitments[blob_index[i]] (FRIEDA_VERIFY_WRONG_COMMITMENT included); blob_index empty: proof i belongs to commitment i and
+    // there is one proof per commitment.  accepted_per_blob (optional) receives per blob the number of ACCEPTED proofs that name it.
+    // Error(FRIEDA_ERR_ARG) before anything runs: an index beyond the table, no index with proofs.size() != commitments.size(), proofs
+    // but no commitments, a proof in flight on the context.
+    std::vector<uint8_t> verify_blobs_many(const std::vector<const Proof*>& proofs, const std::vector<Commitment>& commitments,
+                                           const std::vector<uint32_t>& blob_index = {}, const std::vector<uint64_t>& seeds = {},
+                                           std::vector<uint32_t>* accepted_per_blob = nullptr) {
+        if (!seeds.empty() && seeds.size() != proofs.size()) throw Error(FRIEDA_ERR_ARG, "verify_blobs_many: one seed per proof");
+        if (!blob_index.empty() && blob_index.size() != proofs.size()) throw Error(FRIEDA_ERR_ARG, "verify_blobs_many: one blob index per proof");
+        std::vector<const frieda_proof*> hs;
+        for (const Proof* p : proofs) hs.push_back(p->handle());
+        std::vector<uint8_t> table(32 * commitments.size() + 1), status(hs.size());
+        for (size_t b = 0; b < commitments.size(); b++) std::copy(commitments[b].begin(), commitments[b].end(), table.begin() + 32 * b);
+        std::vector<uint32_t> acc(commitments.size());
+        check(frieda_verify_blobs_many(h_, hs.data(), seeds.empty() ? nullptr : seeds.data(), (uint32_t)hs.size(), table.data(),
+                                       (uint32_t)commitments.size(), blob_index.empty() ? nullptr : blob_index.data(), status.data(), acc.data()),
+              h_);
+        if (accepted_per_blob) *accepted_per_blob = acc;
+        return status;
+    }
+    // the same as verify_many + the positions every accepted proof sampled (frieda_verify_samples_many; empty for a proof that is not accepted)
     std::pair<std::vector<uint8_t>, std::vector<std::vector<uint32_t>>> verify_samples_many(const std::vector<const Proof*>& proofs,
                                                                                             const std::vector<uint64_t>& seeds = {},
                                                                                             const Commitment* expected_commitment = nullptr) {

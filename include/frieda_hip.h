@@ -138,7 +138,7 @@ int frieda_commit_and_generate_proof_device(frieda_ctx* ctx, const void* d_data,
  * context") and leaves the proof untouched: frieda_commit*, frieda_commit_batch*, a second _begin, frieda_merkle_root,
  * frieda_merkle_commit_layer, frieda_grind, frieda_reconstruct*_device, frieda_circle_interpolate_cells,
  * frieda_ctx_release_workspace, frieda_dev_gather, frieda_dev_gather_hashes, frieda_merkle_decommit (and
- * frieda_merkle_decommit_device beyond 512 positions), frieda_verify_many, frieda_verify_samples_many, frieda_reconstruct_from_proofs,
+ * frieda_merkle_decommit_device beyond 512 positions), frieda_verify_many, frieda_verify_blobs_many, frieda_verify_samples_many, frieda_reconstruct_from_proofs,
  * frieda_verify_pairs_many, frieda_reconstruct_from_proof_pairs (frieda_verify_pairs is host-only and takes no context),
  * frieda_open_cells, frieda_verify_cells_many, frieda_reconstruct_from_opened_cells (frieda_verify_cells is host-only and takes no context),
  * frieda_open_cells_blobs, frieda_verify_cells_blobs_many, frieda_reconstruct_blobs_from_opened_stripes (frieda_verify_cells_blobs is host-only
@@ -239,7 +239,7 @@ int frieda_verify_samples(const frieda_proof* proof, const uint64_t* seed, int* 
  *   FRIEDA_VERIFY_WRONG_COMMITMENT  expected_commitment (32 bytes; NULL: not compared) differs from the proof's first-layer
  *                                   commitment: not verified at all (api::verify never sees the commitment, a sampling client has it)
  * The option FRIEDA_VERIFY_DEVICE_MIN is the number of kernel-eligible proofs from which a call uses the GPU
- * (0: always, 2^31: never).  The calls stage through the context's workspace in passes of bounded size: FRIEDA_ERR_ARG while a
+ * (0: always, 2^31: never; the default is 2: a lone proof is no slower through frieda_verify, profiles/r23_verify_split.txt).  The calls stage through the context's workspace in passes of bounded size: FRIEDA_ERR_ARG while a
  * proof is in flight on the context. */
 #define FRIEDA_VERIFY_REJECTED 0
 #define FRIEDA_VERIFY_ACCEPTED 1
@@ -247,7 +247,22 @@ int frieda_verify_samples(const frieda_proof* proof, const uint64_t* seed, int* 
 #define FRIEDA_VERIFY_WRONG_COMMITMENT 3
 int frieda_verify_many(frieda_ctx* ctx, const frieda_proof* const* proofs, const uint64_t* seeds, uint32_t count,
                        const uint8_t* expected_commitment, uint8_t* out_status);
-/* The same, and WHERE every accepted proof sampled, exactly as frieda_verify_samples reports it: row i of out_positions (pitch
+/* The proofs of a block in one call: the one step a sampling client takes before it trusts any cell is one ordinary proof per
+ * commitment, and a block has n_blobs of them (what frieda_prove_seeds_blobs made for its K commitments).  commitments[n_blobs][32] is
+ * the table, blob_index[count] names the commitment of every proof; blob_index NULL: proof i belongs to commitment i, and count must be
+ * n_blobs.  out_status[i] is exactly what frieda_verify_many gives for proof i alone with expected_commitment =
+ * commitments[blob_index[i]], FRIEDA_VERIFY_WRONG_COMMITMENT included, whichever route the proof takes.  out_accepted_per_blob[n_blobs]
+ * (may be NULL) receives per blob the number of ACCEPTED proofs that name it: a client reads "proximity checked" as > 0.
+ * FRIEDA_ERR_ARG before anything runs, out_status and out_accepted_per_blob untouched: a blob_index entry >= n_blobs; NULL blob_index
+ * with count != n_blobs; n_blobs == 0 with count > 0; NULL commitments; a proof in flight on the context.
+ * Launch shapes (every entry point of this section): a pass of at most FRIEDA_VERIFY_SPLIT_MAX kernel-eligible proofs (DESIGN.md
+ * section 10; 0: never, 2^31: always) runs as two launches, one wave per proof for the value chain and one wave per (proof, layer) for
+ * the Merkle walks (verify_split.hip), for calls whose proof count is far below the number of waves the chip holds; statuses,
+ * positions and pair rows are the same on both. */
+int frieda_verify_blobs_many(frieda_ctx* ctx, const frieda_proof* const* proofs, const uint64_t* seeds, uint32_t count,
+                             const uint8_t* commitments, uint32_t n_blobs, const uint32_t* blob_index, uint8_t* out_status,
+                             uint32_t* out_accepted_per_blob);
+/* The same as frieda_verify_many, and WHERE every accepted proof sampled, exactly as frieda_verify_samples reports it: row i of out_positions (pitch
  * entries per row) holds out_n_positions[i] ascending positions, 0 for a proof that is not accepted.  A proof frieda_verify_samples
  * answers with FRIEDA_ERR_INVARIANT (accepted, but not one evaluation per distinct query) has status FRIEDA_VERIFY_INVARIANT here.
  * pitch < n_queries of any proof: FRIEDA_ERR_ARG before anything runs. */
