@@ -21,6 +21,10 @@ pub struct frieda_proof {
 pub struct frieda_encoded {
     _private: [u8; 0],
 }
+#[repr(C)]
+pub struct frieda_block_proof {
+    _private: [u8; 0],
+}
 
 /// stwo `PcsConfig { pow_bits, fri_config: FriConfig { log_blowup_factor, log_last_layer_degree_bound, n_queries } }`
 #[repr(C)]
@@ -118,6 +122,23 @@ extern "C" {
     pub fn frieda_prove_jobs_workspace_bytes(len: usize, cfg: frieda_pcs_config, n_blobs: u32, n_jobs: u32) -> usize;
     pub fn frieda_prove_jobs_plan(ctx: *const frieda_ctx, len: usize, cfg: frieda_pcs_config, n_blobs: u32, n_jobs: u32, jobs_per_pass: *mut u32, n_passes: *mut u32) -> c_int;
     pub fn frieda_prove_seeds_blobs(ctx: *mut frieda_ctx, encs: *const *const frieda_encoded, n_blobs: u32, seeds: *const u64, n_seeds: u32, cfg: frieda_pcs_config, out_proofs: *mut *mut frieda_proof) -> c_int;
+    /// block proofs: ONE FRI proof for all blobs of a block (a protocol of this project; include/frieda_hip.h, "block proofs")
+    pub fn frieda_block_challenge(commitments: *const u8, n_blobs: u32, out_rho: *mut u32) -> c_int;
+    pub fn frieda_aggregate_encoded(ctx: *mut frieda_ctx, encs: *const *const frieda_encoded, n_blobs: u32, out: *mut *mut frieda_encoded) -> c_int;
+    pub fn frieda_test_aggregate_with_rho(ctx: *mut frieda_ctx, encs: *const *const frieda_encoded, n_blobs: u32, rho: *const u32, out: *mut *mut frieda_encoded) -> c_int;
+    pub fn frieda_encoded_aggregate_of(enc: *const frieda_encoded) -> u32;
+    pub fn frieda_prove_block_seeds(ctx: *mut frieda_ctx, agg: *const frieda_encoded, encs: *const *const frieda_encoded, n_blobs: u32, seeds: *const u64, n_seeds: u32, cfg: frieda_pcs_config, out: *mut *mut frieda_block_proof) -> c_int;
+    pub fn frieda_verify_block(commitments: *const u8, n_blobs: u32, bp: *const frieda_block_proof, seed: *const u64, ok: *mut c_int, out_reason: *mut u32) -> c_int;
+    pub fn frieda_block_proof_free(bp: *mut frieda_block_proof);
+    pub fn frieda_block_proof_fri(bp: *const frieda_block_proof) -> *const frieda_proof;
+    pub fn frieda_block_proof_n_blobs(bp: *const frieda_block_proof) -> u32;
+    pub fn frieda_block_proof_n_stripes(bp: *const frieda_block_proof) -> u32;
+    pub fn frieda_block_proof_stripe_index(bp: *const frieda_block_proof) -> *const u32;
+    pub fn frieda_block_proof_values(bp: *const frieda_block_proof) -> *const u32;
+    pub fn frieda_block_proof_witness(bp: *const frieda_block_proof) -> *const u8;
+    pub fn frieda_block_proof_witness_hashes(bp: *const frieda_block_proof) -> u64;
+    pub fn frieda_block_proof_serialize(bp: *const frieda_block_proof, buf: *mut u8, cap: usize) -> usize;
+    pub fn frieda_block_proof_deserialize(buf: *const u8, len: usize, out: *mut *mut frieda_block_proof) -> c_int;
     pub fn frieda_seeds_blobs_workspace_bytes(len: usize, cfg: frieda_pcs_config, n_blobs: u32, n_seeds: u32) -> usize;
     pub fn frieda_commit_batch(ctx: *mut frieda_ctx, data: *const u8, stride: usize, len: usize, count: u32, log_blowup_factor: u32, out_roots: *mut u8) -> c_int;
     pub fn frieda_commit_batch_device(ctx: *mut frieda_ctx, d_data: *const c_void, stride: usize, len: usize, count: u32, log_blowup_factor: u32, out_roots: *mut u8) -> c_int;

@@ -20,6 +20,7 @@ CELL_REJECTED, CELL_ACCEPTED = 0, 1  # status bytes of frieda_verify_cells*
 MAX_LOG_OPEN_CELL = 10
 BUNDLE_REJECTED, BUNDLE_ACCEPTED, BUNDLE_MALFORMED = 0, 1, 2  # status bytes of frieda_verify_cell_bundles*
 MAX_BUNDLE_CELLS = 1024
+BLOCK_OK, BLOCK_SHAPE, BLOCK_FRI, BLOCK_INDICES, BLOCK_BUNDLE, BLOCK_COMBINATION = 0, 1, 2, 3, 4, 5  # out_reason of frieda_verify_block
 
 
 class PcsConfigC(C.Structure):
@@ -179,6 +180,22 @@ def lib():
         "frieda_rebuild_encoded_from_cell_bundles": (C.c_int, [vp, vp, u32, sz, u32, vp, vp, u32, vp, vp, vp, vp, vp, C.POINTER(sz), vp]),
         "frieda_rebuild_encoded_blobs_from_opened_stripes": (C.c_int, [vp, vp, u32, u32, sz, u32, vp, u32, vp, vp, vp, vp, C.POINTER(sz), vp]),
         "frieda_rebuild_encoded_blobs_from_stripe_bundles": (C.c_int, [vp, vp, u32, u32, sz, u32, vp, vp, u32, vp, vp, vp, vp, vp, C.POINTER(sz), vp]),
+        "frieda_block_challenge": (C.c_int, [vp, u32, C.POINTER(u32)]),
+        "frieda_aggregate_encoded": (C.c_int, [vp, vp, u32, pp]),
+        "frieda_test_aggregate_with_rho": (C.c_int, [vp, vp, u32, C.POINTER(u32), pp]),
+        "frieda_encoded_aggregate_of": (u32, [vp]),
+        "frieda_prove_block_seeds": (C.c_int, [vp, vp, vp, u32, u64p, u32, PcsConfigC, pp]),
+        "frieda_verify_block": (C.c_int, [vp, u32, vp, u64p, C.POINTER(C.c_int), C.POINTER(u32)]),
+        "frieda_block_proof_free": (None, [vp]),
+        "frieda_block_proof_fri": (vp, [vp]),
+        "frieda_block_proof_n_blobs": (u32, [vp]),
+        "frieda_block_proof_n_stripes": (u32, [vp]),
+        "frieda_block_proof_stripe_index": (vp, [vp]),
+        "frieda_block_proof_values": (vp, [vp]),
+        "frieda_block_proof_witness": (vp, [vp]),
+        "frieda_block_proof_witness_hashes": (u64, [vp]),
+        "frieda_block_proof_serialize": (sz, [vp, vp, sz]),
+        "frieda_block_proof_deserialize": (C.c_int, [vp, sz, pp]),
         "frieda_proof_free": (None, [vp]),
         "frieda_proof_clone": (C.c_int, [vp, pp]),
         "frieda_proof_proof_of_work": (u64, [vp]),

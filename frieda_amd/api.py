@@ -427,6 +427,30 @@ class Context:
         _check(self._L.frieda_prove_jobs(self._h, handles, n_blobs, bidx, seeds, n_jobs, pcs_config._c(), outs), self._h)
         return [Proof(C.c_void_p(outs[i])) for i in range(n_jobs)]
 
+    # ---- block proofs: one FRI proof for all blobs of a block (this project's own protocol: include/frieda_hip.h) ----
+    def aggregate_encoded(self, encs, rho=None):
+        """The seed-independent aggregate handle of a block: an Encoded whose evaluation is sum over k of rho^k * encs[k]'s, rho =
+        block_challenge of the handles' commitments.  rho given (four canonical M31 words): the testing hook, for the value edges."""
+        encs = list(encs)
+        handles = (C.c_void_p * max(1, len(encs)))(*[e._handle() for e in encs])
+        out = C.c_void_p()
+        if rho is None:
+            _check(self._L.frieda_aggregate_encoded(self._h, handles, len(encs), C.byref(out)), self._h)
+        else:
+            r = (C.c_uint32 * 4)(*[int(x) for x in rho])
+            _check(self._L.frieda_test_aggregate_with_rho(self._h, handles, len(encs), r, C.byref(out)), self._h)
+        return Encoded(out, encs[0].length, encs[0].log_blowup_factor)
+
+    def prove_block_seeds(self, agg, encs, seeds, pcs_config):
+        """[BlockProof], one per seed: the proof of the aggregate under that seed and the K blobs opened where it was queried."""
+        encs = list(encs)
+        seeds = [int(x) for x in seeds]
+        handles = (C.c_void_p * max(1, len(encs)))(*[e._handle() for e in encs])
+        arr = (C.c_uint64 * max(1, len(seeds)))(*seeds)
+        outs = (C.c_void_p * max(1, len(seeds)))()
+        _check(self._L.frieda_prove_block_seeds(self._h, agg._handle(), handles, len(encs), arr, len(seeds), pcs_config._c(), outs), self._h)
+        return [BlockProof(C.c_void_p(outs[i])) for i in range(len(seeds))]
+
     def commit_and_generate_proofs_for_seeds(self, data, seeds, pcs_config):
         """(commitment, [Proof]) for a caller that has every seed at once: encode, prove, free."""
         a = _as_bytes(data)
@@ -1011,6 +1035,11 @@ class Encoded:
         _check(_lib.lib().frieda_encoded_shape(self._handle(), C.byref(a), C.byref(b)))
         return int(a.value), int(b.value)
 
+    @property
+    def aggregate_of(self):
+        """the number of blobs an aggregate handle (Context.aggregate_encoded) combines; 0 for a blob's own handle"""
+        return int(_lib.lib().frieda_encoded_aggregate_of(self._handle()))
+
     def open_cells(self, ctx, log_cell, cell_index):
         """Cells of the codeword with their Merkle paths to `commitment` (frieda_open_cells, on `ctx`, which must be on the blob's
         device): (values uint32 [n, 4, 2^log_cell], paths uint8 [n, log_domain - log_cell, 32])."""
@@ -1156,6 +1185,111 @@ class Proof:
         out = C.c_void_p()
         _check(_lib.lib().frieda_proof_deserialize(a.ctypes.data, a.size, C.byref(out)))
         return Proof(out)
+
+
+from ._lib import BLOCK_BUNDLE, BLOCK_COMBINATION, BLOCK_FRI, BLOCK_INDICES, BLOCK_OK, BLOCK_SHAPE  # noqa: E402,F401  (frieda_verify_block's reasons)
+
+
+class BlockProof:
+    """frieda_block_proof: ONE FRI proof for all blobs of a block — the proof of the aggregate under a seed (`fri`) and the blobs opened
+    where it was queried, as one stripe bundle at log_cell 1 (`stripe_index`, `values`, `witness`, in the layouts of
+    verify_stripe_bundles).  A protocol of this project, not of the reference."""
+
+    def __init__(self, handle):
+        self._h = handle
+        self._L = _lib.lib()
+
+    def __del__(self):
+        try:
+            if self._h:
+                self._L.frieda_block_proof_free(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+    @property
+    def fri(self):
+        """a copy of the FRI part as an ordinary Proof"""
+        out = C.c_void_p()
+        _check(self._L.frieda_proof_clone(self._L.frieda_block_proof_fri(self._h), C.byref(out)))
+        return Proof(out)
+
+    @property
+    def n_blobs(self):
+        return int(self._L.frieda_block_proof_n_blobs(self._h))
+
+    @property
+    def n_stripes(self):
+        return int(self._L.frieda_block_proof_n_stripes(self._h))
+
+    @property
+    def witness_hashes(self):
+        """witness hashes per blob"""
+        return int(self._L.frieda_block_proof_witness_hashes(self._h))
+
+    def _array(self, ptr, ctype, dtype, count, shape):
+        if count == 0:
+            return np.zeros(shape, dtype=dtype)
+        return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(ctype)), shape=(count,)).copy().reshape(shape)
+
+    @property
+    def stripe_index(self):
+        n = self.n_stripes
+        return self._array(self._L.frieda_block_proof_stripe_index(self._h), C.c_uint32, np.uint32, n, (n,))
+
+    @property
+    def values(self):
+        """uint32 [n_stripes, n_blobs, 4, 2]"""
+        n, k = self.n_stripes, self.n_blobs
+        return self._array(self._L.frieda_block_proof_values(self._h), C.c_uint32, np.uint32, 8 * n * k, (n, k, 4, 2))
+
+    @property
+    def witness(self):
+        """uint8 [n_blobs, witness_hashes, 32]"""
+        k, w = self.n_blobs, self.witness_hashes
+        return self._array(self._L.frieda_block_proof_witness(self._h), C.c_uint8, np.uint8, 32 * k * w, (k, w, 32))
+
+    def serialize(self):
+        n = self._L.frieda_block_proof_serialize(self._h, None, 0)
+        buf = (C.c_uint8 * n)()
+        self._L.frieda_block_proof_serialize(self._h, buf, n)
+        return bytes(buf)
+
+    @staticmethod
+    def from_bytes(blob):
+        a = np.frombuffer(bytes(blob), dtype=np.uint8)
+        out = C.c_void_p()
+        _check(_lib.lib().frieda_block_proof_deserialize(a.ctypes.data if a.size else None, a.size, C.byref(out)))
+        return BlockProof(out)
+
+    @staticmethod
+    def from_parts(fri, stripe_index, values, witness):
+        """A block proof from its parts (a relay that re-bundles, a test that tampers): `fri` a Proof, values [n_stripes, n_blobs, 4, 2],
+        witness [n_blobs, W, 32] — assembled as the wire image and read back, so the rules of from_bytes apply."""
+        img = fri.serialize()
+        idx = np.ascontiguousarray(stripe_index, dtype="<u4").reshape(-1)
+        val = np.ascontiguousarray(values, dtype="<u4").reshape(len(idx), -1, 4, 2)
+        k = val.shape[1]
+        wit = np.ascontiguousarray(witness, dtype=np.uint8).reshape(-1)
+        head = np.array([0x31504246, 1, k, len(idx)], dtype="<u4").tobytes() + np.array([wit.size // (32 * max(k, 1)), len(img)], dtype="<u8").tobytes()
+        return BlockProof.from_bytes(head + img + idx.tobytes() + val.tobytes() + wit.tobytes())
+
+
+def block_challenge(commitments):
+    """rho of a block as four M31 words: a default channel, mix_u64(K), mix_root of every commitment in order, one draw_felt (host only)"""
+    tab = _commitment_table(commitments)
+    out = (C.c_uint32 * 4)()
+    _check(_lib.lib().frieda_block_challenge(tab.ctypes.data, len(tab) // 32, out))
+    return tuple(int(x) for x in out)
+
+
+def verify_block(commitments, block_proof, seed):
+    """(ok, reason): the client's check of a block proof against the block's commitments (host only); reason is BLOCK_OK or the first
+    failing step, BLOCK_SHAPE / _FRI / _INDICES / _BUNDLE / _COMBINATION."""
+    tab = _commitment_table(commitments)
+    ok, reason = C.c_int(0), C.c_uint32(0)
+    _check(_lib.lib().frieda_verify_block(tab.ctypes.data, len(tab) // 32, block_proof._h, _seed_ptr(seed), C.byref(ok), C.byref(reason)))
+    return bool(ok.value), int(reason.value)
 
 
 class MultiContext:
@@ -1582,6 +1716,17 @@ def prove_seeds_blobs(ctx, encs, seeds, pcs_config):
     """Every encoded blob of a block under every seed of one list in ONE call (frieda_prove_seeds_blobs on `ctx`): a list of
     len(encs) lists of len(seeds) Proofs."""
     return ctx.prove_seeds_blobs(encs, seeds, pcs_config)
+
+
+def aggregate_encoded(ctx, encs):
+    """The aggregate handle of a block (frieda_aggregate_encoded on `ctx`): once per block, whatever the seeds."""
+    return ctx.aggregate_encoded(encs)
+
+
+def prove_block_seeds(ctx, agg, encs, seeds, pcs_config):
+    """One BlockProof per seed for the whole block (frieda_prove_block_seeds on `ctx`): len(seeds) fold chains instead of
+    len(encs) * len(seeds)."""
+    return ctx.prove_block_seeds(agg, encs, seeds, pcs_config)
 
 
 def open_stripes(ctx, encs, log_cell, stripe_index):

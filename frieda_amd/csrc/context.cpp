@@ -155,6 +155,7 @@ const KnobDesc KNOBS[] = {
     {"FRIEDA_GRIND_FRONT_WGS", 0, 2048, [](Tuning& t, long v) { t.grind_front_wgs = (uint32_t)v; return true; }},
     {"FRIEDA_GRIND_ITERS", 0, 64, [](Tuning& t, long v) { t.grind_iters = (uint32_t)v; return true; }},
     {"FRIEDA_BATCH_BUDGET_MB", 0, 262144, [](Tuning& t, long v) { t.batch_budget_mb = (uint32_t)v; return true; }},
+    {"FRIEDA_AGG_SPLIT", 0, 2, [](Tuning& t, long v) { t.agg_split = (uint32_t)v; return true; }},
     {"FRIEDA_BATCH_CALLS_PER_CTX", 1, 64, [](Tuning& t, long v) { t.batch_calls_per_ctx = (uint32_t)v; return true; }},
 };
 }  // namespace

@@ -237,6 +237,9 @@ struct Encoded {
     uint8_t* d = nullptr;  // [evaluation: 4 x 2^n words][tree: merkle_layer_offset(n, 0) + 32 bytes][root: 32 bytes], each from a 256-byte boundary
     size_t bytes = 0, o_tree = 0, o_root = 0;
     uint8_t root[32] = {0};
+    // an aggregate handle (frieda_aggregate_encoded): of how many blobs (0: a blob's own handle) and under which challenge
+    uint32_t aggregate_of = 0;
+    QM31 aggregate_rho{0, 0, 0, 0};
     const uint32_t* eval() const { return reinterpret_cast<const uint32_t*>(d); }
     const uint8_t* tree() const { return d + o_tree; }
 };

@@ -74,6 +74,8 @@ struct Tuning {
     uint32_t seeds_fold_group = 0;       // FRIEDA_SEEDS_FOLD_GROUP: proofs of one encoded blob under many seeds (prove_seeds): seeds per workgroup of the
                                          // seed-looped first fold (route B: the evaluation is read once per group); 0 = route A, the batch kernels
                                          // with every seed re-reading the shared evaluation (measured: profiles/r08_prove_seeds.txt)
+    uint32_t agg_split = 0;              // FRIEDA_AGG_SPLIT: frieda_aggregate_encoded's kernel: 0 = by shape (the blob range split over a workgroup's
+                                         // waves for >= 8 blobs on domains below 2^18 points: fewer waves than the chip has SIMDs), 1 = never, 2 = always
     uint32_t batch_calls_per_ctx = 1;    // FRIEDA_BATCH_CALLS_PER_CTX: a stream is cut into at least this many calls per context in flight
                                          // (measured, profiles/r05_batch_policy_sweep.txt: 1 beats 2 by 3 % at 2^20 and 30 % at 1 KiB blobs, equal at 2^22 / 2^24)
     // facts about the context's device, recorded at creation (not knobs: tuning_set does not reach them)
@@ -575,6 +577,22 @@ void blob_image_check(const Launch& L, const uint32_t* d_coef, size_t n_words, s
 // Evaluation columns at one stride -> the slab layout of a block of handles: column c of blob b (2^n words at d_ev + (4 b + c) * ev_stride)
 // goes to d_slab + b * bstride + c * 4 * 2^n bytes.  n >= 2; ev_stride a multiple of 4 words, bstride of 16 bytes, both pointers 16-byte aligned.
 void eval_to_slab(const Launch& L, const uint32_t* d_ev, size_t ev_stride, uint32_t n, uint32_t n_blobs, uint8_t* d_slab, size_t bstride);
+
+// ---- aggregate.hip: the random linear combination of a block's codewords (frieda_aggregate_encoded) ----
+// out[4][2^log_n] = sum over k < n_blobs of rho^k * evals[k][4][2^log_n], coordinate columns read as QM31 values; every input word a
+// canonical M31, every output word canonical.  evals: a table of n_blobs device pointers in device memory (an entry may repeat); every
+// evaluation and `out` 16-byte aligned when log_n >= 2, and `out` none of the inputs.  split: the blob range over the AGG_SPLIT waves of a
+// workgroup (chunk = ceil(n_blobs / AGG_SPLIT) blobs each, rho_pow[x - 1] = the matrix of rho^(x * chunk)); the same words either way.
+constexpr uint32_t AGG_SPLIT = 4;
+struct AggregateArgs {
+    const uint32_t* const* evals;
+    uint32_t n_blobs, log_n;
+    uint32_t* out;
+    uint32_t chunk;
+    QM31Mat rho;
+    QM31Mat rho_pow[AGG_SPLIT - 1];
+};
+void aggregate(const Launch& L, const AggregateArgs& a, bool split);
 
 // ---- opening.hip: Level B openings (frieda_dev_gather*, frieda_merkle_decommit*) ----
 constexpr uint32_t OPEN_BAD_WORD = 0xFFFFFFFFu;   // gathered word of an out-of-range index (device forms only; not a canonical M31)

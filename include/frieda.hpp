@@ -138,11 +138,68 @@ class Encoded {
         check(frieda_encoded_shape(h_, &l, &n));
         return {l, n};
     }
+    // the number of blobs an aggregate handle (Context::aggregate_encoded) combines; 0 for a blob's own handle
+    uint32_t aggregate_of() const { return frieda_encoded_aggregate_of(h_); }
     const frieda_encoded* handle() const { return h_; }
 
   private:
     frieda_encoded* h_ = nullptr;
 };
+
+// A block proof (frieda_block_proof): ONE FRI proof for all blobs of a block — the proof of the aggregate handle under a seed and the
+// blobs opened where it was queried, as one stripe bundle at log_cell 1.  A protocol of this project, not of the reference
+// (include/frieda_hip.h, "block proofs").  Made by Context::prove_block_seeds or from its wire image; checked by verify_block.
+class BlockProof {
+  public:
+    BlockProof() = default;
+    explicit BlockProof(frieda_block_proof* h) : h_(h) {}
+    BlockProof(const BlockProof&) = delete;
+    BlockProof& operator=(const BlockProof&) = delete;
+    BlockProof(BlockProof&& o) noexcept : h_(o.h_) { o.h_ = nullptr; }
+    BlockProof& operator=(BlockProof&& o) noexcept {
+        std::swap(h_, o.h_);
+        return *this;
+    }
+    ~BlockProof() { frieda_block_proof_free(h_); }
+    // the FRI part: owned by the block proof (frieda_proof_clone for a copy)
+    const frieda_proof* fri() const { return frieda_block_proof_fri(h_); }
+    uint32_t n_blobs() const { return frieda_block_proof_n_blobs(h_); }
+    uint32_t n_stripes() const { return frieda_block_proof_n_stripes(h_); }
+    uint64_t witness_hashes() const { return frieda_block_proof_witness_hashes(h_); }  // per blob
+    // the opening part in the layouts of frieda_verify_stripe_bundles: [n_stripes], [n_stripes][n_blobs][4][2], [n_blobs][witness_hashes][32]
+    const uint32_t* stripe_index() const { return frieda_block_proof_stripe_index(h_); }
+    const uint32_t* values() const { return frieda_block_proof_values(h_); }
+    const uint8_t* witness() const { return frieda_block_proof_witness(h_); }
+    std::vector<uint8_t> serialize() const {
+        std::vector<uint8_t> b(frieda_block_proof_serialize(h_, nullptr, 0));
+        frieda_block_proof_serialize(h_, b.data(), b.size());
+        return b;
+    }
+    static BlockProof deserialize(const std::vector<uint8_t>& b) {
+        frieda_block_proof* h = nullptr;
+        check(frieda_block_proof_deserialize(b.data(), b.size(), &h));
+        return BlockProof(h);
+    }
+    const frieda_block_proof* handle() const { return h_; }
+
+  private:
+    frieda_block_proof* h_ = nullptr;
+};
+
+// rho of a block: the Fiat-Shamir challenge over all its commitments, in order (frieda_block_challenge; host only)
+inline QM31 block_challenge(const std::vector<Commitment>& commitments) {
+    QM31 rho{};
+    check(frieda_block_challenge(commitments.empty() ? nullptr : commitments.data()->data(), (uint32_t)commitments.size(), rho.v));
+    return rho;
+}
+// The client's check of a block proof (frieda_verify_block; host only): true when accepted; *reason (optional) receives FRIEDA_BLOCK_OK
+// or the first failing step, FRIEDA_BLOCK_SHAPE / _FRI / _INDICES / _BUNDLE / _COMBINATION.
+inline bool verify_block(const std::vector<Commitment>& commitments, const BlockProof& bp, std::optional<uint64_t> seed, uint32_t* reason = nullptr) {
+    int ok = 0;
+    uint64_t s = seed.value_or(0);
+    check(frieda_verify_block(commitments.empty() ? nullptr : commitments.data()->data(), (uint32_t)commitments.size(), bp.handle(), seed ? &s : nullptr, &ok, reason));
+    return ok != 0;
+}
 
 class Context {
   public:
@@ -218,6 +275,28 @@ class Context {
         std::vector<Proof> out;
         out.reserve(ps.size());
         for (frieda_proof* p : ps) out.emplace_back(p);
+        return out;
+    }
+    // Block proofs (include/frieda_hip.h, "block proofs"): the aggregate handle of a block — once per block, whatever the seeds — and
+    // one BlockProof per seed for the whole block: seeds.size() fold chains instead of encs.size() * seeds.size().
+    Encoded aggregate_encoded(const std::vector<const Encoded*>& encs) {
+        std::vector<const frieda_encoded*> hs;
+        hs.reserve(encs.size());
+        for (const Encoded* e : encs) hs.push_back(e ? e->handle() : nullptr);
+        frieda_encoded* g = nullptr;
+        check(frieda_aggregate_encoded(h_, hs.data(), (uint32_t)encs.size(), &g), h_);
+        return Encoded(g);
+    }
+    std::vector<BlockProof> prove_block_seeds(const Encoded& agg, const std::vector<const Encoded*>& encs, const std::vector<uint64_t>& seeds,
+                                              const PcsConfig& cfg) {
+        std::vector<const frieda_encoded*> hs;
+        hs.reserve(encs.size());
+        for (const Encoded* e : encs) hs.push_back(e ? e->handle() : nullptr);
+        std::vector<frieda_block_proof*> ps(seeds.size(), nullptr);
+        check(frieda_prove_block_seeds(h_, agg.handle(), hs.data(), (uint32_t)encs.size(), seeds.data(), (uint32_t)seeds.size(), cfg.c(), ps.data()), h_);
+        std::vector<BlockProof> out;
+        out.reserve(ps.size());
+        for (frieda_block_proof* p : ps) out.emplace_back(p);
         return out;
     }
     // Any list of jobs in ONE call (frieda_prove_jobs): proof j == prove_seeds(*encs[blob_index[j]], {seeds[j]}, cfg)[0] byte for byte,

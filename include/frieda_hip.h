@@ -145,7 +145,7 @@ int frieda_commit_and_generate_proof_device(frieda_ctx* ctx, const void* d_data,
  * and takes no context), frieda_open_cell_bundles, frieda_verify_cell_bundles_many, frieda_reconstruct_from_cell_bundles
  * (frieda_cell_bundle_witness_count and frieda_verify_cell_bundles are host-only and take no context), frieda_open_stripe_bundles,
  * frieda_verify_stripe_bundles_many, frieda_reconstruct_blobs_from_stripe_bundles (frieda_verify_stripe_bundles is host-only and takes no
- * context), frieda_encode_batch and the four frieda_rebuild_encoded_* calls.  Level B calls that only read the twiddle cache and caller
+ * context), frieda_encode_batch, the four frieda_rebuild_encoded_* calls, frieda_aggregate_encoded and frieda_prove_block_seeds.  Level B calls that only read the twiddle cache and caller
  * buffers stay available.
  * A blob passed to _begin_device must stay valid until _finish returns. */
 int frieda_prove_begin(frieda_ctx* ctx, const uint8_t* data, size_t len, const uint64_t* seed, frieda_pcs_config cfg);
@@ -655,6 +655,89 @@ int frieda_prove_jobs(frieda_ctx* ctx, const frieda_encoded* const* encs, uint32
 size_t frieda_prove_jobs_workspace_bytes(size_t len, frieda_pcs_config cfg, uint32_t n_blobs, uint32_t n_jobs);
 int frieda_prove_jobs_plan(const frieda_ctx* ctx, size_t len, frieda_pcs_config cfg, uint32_t n_blobs, uint32_t n_jobs, uint32_t* jobs_per_pass,
                            uint32_t* n_passes);
+
+/* ---- block proofs: ONE FRI proof for all blobs of a block ---------------------------------------------------------------------
+ * Everything above rests on one ordinary proof per commitment: n_blobs * n_seeds fold chains for the provider of a block, n_blobs
+ * proofs to download and verify for a client before it may trust one cell.  Batched FRI removes the factor n_blobs.  The blobs stay
+ * committed exactly as they are (commitments[k] = frieda_commit of blob k); a challenge rho in QM31 is drawn from ALL the commitments;
+ * ONE FRI instance runs over g = sum over k of rho^k * f_k, f_k the codeword of blob k read as QM31 values; where that proof queried g,
+ * every f_k is opened against its own commitment, and the client checks the linear combination there.  A provider owes n_seeds proofs
+ * per block instead of n_blobs * n_seeds; a client verifies one proof per block instead of n_blobs.
+ * THIS IS A PROTOCOL OF THIS PROJECT, not of the reference and not of stwo's FRI prover: the reference passes one column to
+ * FriProver::commit, and stwo batches equal-size columns in its PCS quotient step, which is out of scope here.
+ * Soundness is the usual random-linear-combination argument for FRI (if some f_k is far from the code, g is far from it for all but a
+ * negligible fraction of rho; rho is a Fiat-Shamir challenge over all the commitments, drawn from the 2^124-element field); the argument
+ * as applied here is UNREVIEWED.  A block proof is not a frieda Proof and no reference verifier takes it; its FRI
+ * part IS an ordinary proof, of a polynomial that is no blob's image.
+ * rho (frieda_block_challenge; host only, no context, no GPU): a default Blake2sChannel, mix_u64(n_blobs), mix_root(commitments[k]) for
+ * k = 0 .. n_blobs - 1 in order, one draw_felt.  commitments[n_blobs][32]; 1 <= n_blobs <= 65535.
+ * The aggregate handle (frieda_aggregate_encoded): an ordinary frieda_encoded of the blobs' shape in an allocation of its own, whose
+ * evaluation at every domain position p is sum over k of rho^k * f_k(p) — f_k(p) the four coordinate columns of encs[k] at p, rho from
+ * the handles' commitments — and whose tree and root are the tree build of a lone call over that evaluation.  It does not depend on any
+ * seed: make it once per block.  Every call that takes a handle takes it unchanged (frieda_prove_seeds, frieda_prove_jobs, the cell
+ * openers: they read the evaluation and the tree); frieda_encoded_shape is the blobs'; frieda_encoded_aggregate_of returns n_blobs (0 for
+ * a blob's own handle).  Its coefficients are no blob's image: it cannot come out of a frieda_rebuild_encoded_* call.  Handles as for
+ * frieda_prove_seeds_blobs_begin: one shape, on ctx's device, from any mix of slabs and tree-skip thresholds, an entry may repeat; the
+ * call only reads them.  One upload (the table of n_blobs evaluation pointers), the combination kernel (aggregate.hip: per position 16
+ * bytes read per blob and 16 written, one multiplication by rho and one addition per blob; for >= 8 blobs on domains below 2^18 points
+ * the blob range is split over the waves of a workgroup, option FRIEDA_AGG_SPLIT — identical words either way), the tree, one download,
+ * one synchronisation.  FRIEDA_ERR_ARG: a NULL entry, mixed shapes, n_blobs out of 1 .. 65535, another device, a proof in flight on ctx.
+ * Block proofs under many seeds (frieda_prove_block_seeds): out[n_seeds], out[s] under seeds[s], each released with
+ * frieda_block_proof_free.  A frieda_block_proof holds
+ *   the FRI part      exactly the frieda_proof that frieda_prove_seeds(agg, &seeds[s], 1, cfg) gives, and
+ *   the opening part  exactly what frieda_open_stripe_bundles(encs, n_blobs, log_cell = 1, idx, {0, k}, 1, ...) gives as one bundle,
+ *                     idx the strictly ascending distinct q >> 1 over the FRI part's first-layer queries q: FRI opens the bit-reversed
+ *                     evaluation in pairs {2 i, 2 i + 1}, and pair i is cell i at log_cell 1.
+ * Route: frieda_prove_seeds on agg (one pass, its limits; first synchronisation), the query positions of every proof by replaying its
+ * transcript on the host (nothing is verified to learn them), the n_seeds bundles in ONE frieda_open_stripe_bundles launch chain (second
+ * synchronisation).  Arguments: cfg.n_queries <= FRIEDA_MAX_BUNDLE_CELLS; agg an aggregate of exactly n_blobs blobs whose recorded rho
+ * equals frieda_block_challenge of these handles' commitments (nothing is aggregated again to check); otherwise the rules of the two
+ * calls it is made of.  On failure nothing is returned (out is all NULL), everything is freed and ctx stays usable.
+ * Accessors, in the layouts of frieda_verify_stripe_bundles (which can be applied to them directly with log_cell 1, one bundle,
+ * bundle_first {0, n_stripes}, witness_first {0, witness_hashes}): stripe_index[n_stripes], values[n_stripes][n_blobs][4][2],
+ * witness[n_blobs][witness_hashes][32]; pointers stay valid until frieda_block_proof_free.  frieda_block_proof_fri is owned by the
+ * block proof.  Wire image (little-endian): magic "FBP1", version 1, n_blobs, n_stripes (u32 each), witness_hashes, proof_bytes (u64
+ * each), the proof's image, then the three arrays; buf == NULL returns the size needed.  Deserialising applies the
+ * bundle's malformed rule to the indices on the proof's domain, requires witness_hashes to be the count they give and the image to have
+ * exactly the length its header gives: any violation, a bad proof image included, is FRIEDA_ERR_ARG.
+ * The client's check (frieda_verify_block; host only, one core): *ok is set exactly when, in this order, (a) n_blobs and the shape
+ * agree, (b) frieda_verify_pairs accepts the FRI part under seed, (c) the stripe indices are exactly the ascending distinct q >> 1 of
+ * that proof's queries, (d) frieda_verify_stripe_bundles gives ACCEPTED for every blob against commitments, (e) at every opened pair and
+ * both of its entries sum over k of rho^k * value_k equals the value frieda_verify_pairs returned there, rho =
+ * frieda_block_challenge(commitments, n_blobs).  *out_reason (may be NULL) names the first failing step, FRIEDA_BLOCK_OK when none does.
+ * FRIEDA_ERR_INVARIANT where frieda_verify_pairs returns it.  A device form for many block proofs does not exist yet.
+ * Measured on one MI355X in one run (profiles/r24_block_proof.txt, tools/block_proof_timing.py; blow-up 16, 20 queries, 20-bit proof of work;
+ * HIP-event medians of 21 alternated calls; records, not gates): frieda_prove_block_seeds against frieda_prove_seeds_blobs on the same
+ * handles and seeds: 64 blobs of 1 KiB x 4 seeds 0.46 against 5.15 ms, 16 blobs of 128 KiB x 8 seeds 1.10 against 6.36 ms, 4 blobs of a
+ * 2^22 domain x 4 seeds 1.45 against 3.71 ms; frieda_aggregate_encoded, once per block, 0.08 / 0.35 / 0.51 ms (its kernel alone 12 / 26 / 78
+ * us: 0.68 of the 8.0 TB/s HBM specification at 16 x 128 KiB, 0.54 at 4 x 2^22).  One serialised block proof against the K proofs of the same
+ * seed: 0.26 against 0.81 MB, 0.20 against 1.02 MB, 0.13 against 0.38 MB.  frieda_verify_block on one core against K x frieda_verify: 0.80
+ * against 4.88 ms, 0.59 against 4.04 ms, 0.43 against 1.35 ms.  The block form won at every measured shape: use it where a client can
+ * take this project's own proof; use frieda_prove_seeds_blobs where the proofs must be ones the reference's verifier accepts.  Other
+ * shapes are not measured. */
+#define FRIEDA_BLOCK_OK 0
+#define FRIEDA_BLOCK_SHAPE 1
+#define FRIEDA_BLOCK_FRI 2
+#define FRIEDA_BLOCK_INDICES 3
+#define FRIEDA_BLOCK_BUNDLE 4
+#define FRIEDA_BLOCK_COMBINATION 5
+typedef struct frieda_block_proof frieda_block_proof;
+int frieda_block_challenge(const uint8_t* commitments, uint32_t n_blobs, uint32_t out_rho[4]);
+int frieda_aggregate_encoded(frieda_ctx* ctx, const frieda_encoded* const* encs, uint32_t n_blobs, frieda_encoded** out);
+uint32_t frieda_encoded_aggregate_of(const frieda_encoded* enc);
+int frieda_prove_block_seeds(frieda_ctx* ctx, const frieda_encoded* agg, const frieda_encoded* const* encs, uint32_t n_blobs, const uint64_t* seeds,
+                             uint32_t n_seeds, frieda_pcs_config cfg, frieda_block_proof** out);
+int frieda_verify_block(const uint8_t* commitments, uint32_t n_blobs, const frieda_block_proof* bp, const uint64_t* seed, int* ok, uint32_t* out_reason);
+void frieda_block_proof_free(frieda_block_proof* bp);
+const frieda_proof* frieda_block_proof_fri(const frieda_block_proof* bp);
+uint32_t frieda_block_proof_n_blobs(const frieda_block_proof* bp);
+uint32_t frieda_block_proof_n_stripes(const frieda_block_proof* bp);
+const uint32_t* frieda_block_proof_stripe_index(const frieda_block_proof* bp);
+const uint32_t* frieda_block_proof_values(const frieda_block_proof* bp);
+const uint8_t* frieda_block_proof_witness(const frieda_block_proof* bp);
+uint64_t frieda_block_proof_witness_hashes(const frieda_block_proof* bp);
+size_t frieda_block_proof_serialize(const frieda_block_proof* bp, uint8_t* buf, size_t cap);
+int frieda_block_proof_deserialize(const uint8_t* buf, size_t len, frieda_block_proof** out);
 
 /* ---- batch policy: how a stream of equal-length blobs is cut into batched calls ("bytes in flight") -------------------------
  * Every kernel of a batched call covers all its blobs, so the launch / Fiat-Shamir latency chain is paid once per call: small
